@@ -1,6 +1,7 @@
 """bench.py -- mel-frames/s of one full ForwardTacotron train step on MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    (+ DIR/<name>.npy: what the last timed step computed)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -303,6 +304,39 @@ def fastpitch_bf16_record(steps=10, warmup=3):
                       'bf16 path'}
 
 
+DUMP_SAMPLE = 65536            # entries kept per state_dict tensor by --dump-outputs (larger tensors: a seeded sample)
+DUMP_LIMIT = 64 << 20          # bytes, all files of one --dump-outputs together
+
+
+def snapshot_outputs(out, model):
+    """Host copies of what the last timed step produced: every value step() returned (device scalars), and the model's
+    state after that step's update -- tensors of at most DUMP_SAMPLE entries whole, larger ones as a fixed sample of
+    DUMP_SAMPLE flat entries (numpy seed 0, drawn in state_dict order).  float64 for integer buffers, float32 else."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach().double().cpu().numpy()
+    rng = np.random.default_rng(0)
+    for k, v in model.state_dict().items():
+        flat = v.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(rng.choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays['state.' + k] = flat.to(torch.float32 if v.is_floating_point() else torch.float64).cpu().numpy()
+    return arrays
+
+
+def write_outputs(arrays, path):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})')
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -314,7 +348,11 @@ def main():
     ap.add_argument('--cpu-threads', type=int, default=16, help='torch threads of the CPU baseline')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-variants', action='store_true', help='skip the FastPitch bf16 record (N=1 only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
@@ -383,6 +421,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        # copied before the instrumented steps below move the model on
+        dumped = snapshot_outputs(o, ts.model) if args.dump_outputs and rank == 0 else None
         probes.remove()
         bank_ms = [ms for _, _, ms in probes.results()]
         fam = []
@@ -405,9 +445,9 @@ def main():
         flag = torch.tensor([ok], device=device)
         if world > 1:
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        return elapsed, o, bool(flag.item() > 0), bank_ms, fam
+        return elapsed, o, bool(flag.item() > 0), bank_ms, fam, dumped
 
-    dt, out, rnn_ok, bank_ms, fam = measure(build())
+    dt, out, rnn_ok, bank_ms, fam, dumped = measure(build())
     rnn_persistent = not (rehearsal and world > 1)
     if not rnn_ok:
         # a persistent recurrence timed out on some rank: the device skipped every update from then on, so the run
@@ -415,7 +455,7 @@ def main():
         # seed and measure again
         _ftlib.query('ft_rnn_set_persistent', 0)
         rnn_persistent = False
-        dt, out, rnn_ok, bank_ms, fam = measure(build())
+        dt, out, rnn_ok, bank_ms, fam, dumped = measure(build())
         if not rnn_ok:
             raise SystemExit('bench.py: recurrence status still bad with the per-step kernels')
     stats = torch.tensor([dt, float(n_frm), float(n_tok)], device=device, dtype=torch.float64)
@@ -430,6 +470,8 @@ def main():
         tot_frm, tot_tok = float(n_frm), float(n_tok)
     loss = float(out['loss'])
 
+    if dumped is not None:
+        write_outputs(dumped, args.dump_outputs)
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = tot_frm * args.steps / dt

@@ -126,3 +126,12 @@ def fp_state(d, prefix):
 
 TRAIN_CFG_MULTI = dict(dur_loss_factor=0.1, pitch_loss_factor=0.1, energy_loss_factor=0.1,
                        pitch_cond_loss_factor=0.1, clip_grad_norm=1.0)
+
+
+def sample_index(n, size, stride=1000003):
+    """flat indices of a fixed sample of a tensor of n entries: all of them when n <= size, else i * stride mod n for
+    i < size (stride prime and coprime with n, so the entries are distinct and spread over the whole tensor)"""
+    if n <= size:
+        return np.arange(n, dtype=np.int64)
+    assert np.gcd(stride, n) == 1, n
+    return np.arange(size, dtype=np.int64) * stride % n

@@ -2,7 +2,7 @@
 
 (a) BASELINE configs[1] itself -- singlespeaker.yaml widths, bs=32, Tx=128, Tm=841, seed-0 batch, all dropout 0: one
     HIP train step against oracle/ft_torch_cpu.CpuTrainer (the stock-op restatement, pinned to the reference's goldens
-    and -- at this very width -- to the live import, tests/test_refimport_full_size.py): mel / mel_post <= 1e-4 abs (the
+    and -- at this very width -- to the stored full-size step, tests/test_refimport_full_size.py): mel / mel_post <= 1e-4 abs (the
     north-star bar), the five loss terms, the gradient norm, EVERY parameter's gradient, the BatchNorm running statistics.
     Follows models/forward_tacotron.py:118-165 and trainer/forward_trainer.py:73-99 of the reference.
 (b) The decoder LSTM at its production width (H=512, B=32, input 512) in its DEFAULT persistent templates (4-wave forward,
