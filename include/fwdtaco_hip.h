@@ -550,6 +550,26 @@ int ft_gl_phase(const float* rebuilt, float* tprev, const float* S, float* proj,
                 int has_prev, void* stream);
 int ft_overlap_add(const float* frames, const float* inv_wss, float* ypad, int N, int n_fft, int hop, void* stream);
 
+/* ---- durations from a Tacotron attention (duration_extraction/duration_extractor.py:23-84 DurationExtractor ;
+ *      duration_extraction_pipe.py:56-62,173-183 ; utils/metrics.py:4-31 attention_score, r = 1) ---------------- */
+/* One workgroup per item b; every length is read on the device.  Inputs: attn [B,Tm,Tx] fp32 (rows = mel frames),
+ * mel [B,n_mels,Tmel] fp32, x [B,Tx_x] int64 tokens, x_len / mel_len [B] int64, sil_ids [n_sil] int64 (the token ids
+ * that count as silent: pad + punctuation).  Item b uses attn[b, :mel_len, :x_len] and mel[b, :, :mel_len].
+ * Frame i is silent if mean_c mel[c,i] < silence_threshold; if at least two frames are silent, the attention of every
+ * silent frame gets +shift on silent tokens and -shift on the others; then clamp [0,1] and cost = 1 - att.  The
+ * cheapest right / down / diagonal path from (0,0) to (mel_len-1, x_len-1) (an edge weighs the cost of the cell it
+ * enters, distances summed in fp64; exact ties: diagonal, then down, then right) gives each frame to the last token
+ * its row visits.  Outputs: durations [B,Tx_out] int64 (0 at j >= x_len); fstats [B,3] fp64 = (mean clamped attention
+ * along the path over non-silent frames -- NaN if every frame is silent --, align score = fraction of consecutive
+ * frames whose argmax token moves by <= 1 (fp32; NaN for one frame), path cost); istats [B,3] int64 = (max duration,
+ * longest run of ones, status: 0 ok, 1 bad x_len, 2 bad mel_len, 3 no workspace; a bad item writes zero durations).
+ * x_len <= min(Tx, Tx_x, Tx_out) and Tx <= 1024.  ws: ft_dur_workspace(B, Tm, Tx) bytes. */
+size_t ft_dur_workspace(int B, int Tm, int Tx);
+int ft_dur_extract(const float* attn, int Tm, int Tx, const float* mel, int n_mels, int Tmel, const long* x, int Tx_x,
+                   const long* x_len, const long* mel_len, const long* sil_ids, int n_sil, float silence_threshold,
+                   float silence_prob_shift, int B, long* durations, int Tx_out, double* fstats, long* istats,
+                   void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
