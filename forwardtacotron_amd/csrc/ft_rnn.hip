@@ -325,7 +325,8 @@ void launch_fwd(bool fast, dim3 grid, hipStream_t stream, const RnnFwdArgs& a) {
     hipLaunchKernelGGL((ft_rnn_fwd_step_kernel<G, NW, MT, false>), grid, dim3(NW * 64), 0, stream, a);
 }
 
-template <int G>
+// ND = 1: the forward direction alone (ft_lstm_fwd_uni; whh_r / bhh_r are then unused and may alias the forward ones)
+template <int G, int ND = 2>
 int rnn_fwd(const float* xp, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
             float* out, float* cst, float* gates, const long* lens, int B, int T, int H, void* ws,
             size_t ws_bytes, hipStream_t stream, const unsigned* gate = nullptr, int gate_cs = 0,
@@ -333,7 +334,7 @@ int rnn_fwd(const float* xp, const float* whh_f, const float* whh_r, const float
   RnnFwdArgs a;
   a.xp = xp; a.whh[0] = whh_f; a.whh[1] = whh_r; a.bhh[0] = bhh_f; a.bhh[1] = bhh_r;
   a.out = out; a.cst = cst; a.gates = gates; a.lens = lens;
-  a.B = B; a.T = T; a.H = H; a.ND = 2; a.Bld = B;
+  a.B = B; a.T = T; a.H = H; a.ND = ND; a.Bld = B;
   a.gate = gate; a.gate_cs = gate_cs;
   a.vec = (H % 4 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)whh_f % 16 == 0) && ((uintptr_t)whh_r % 16 == 0);
   const bool fast = a.vec && (H % 16 == 0);
@@ -374,12 +375,12 @@ int rnn_fwd(const float* xp, const float* whh_f, const float* whh_r, const float
     }
   }
   if (lens) {   // inactive positions must read as zeros
-    (void)hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * T * 2 * H, stream);
-    if (cst) (void)hipMemsetAsync(cst, 0, sizeof(float) * (size_t)B * T * 2 * H, stream);
+    (void)hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * T * ND * H, stream);
+    if (cst) (void)hipMemsetAsync(cst, 0, sizeof(float) * (size_t)B * T * ND * H, stream);
   }
   constexpr int UB = 16 / G;
   const bool two = B > 16;                        // 32 batch rows per workgroup when there are that many
-  dim3 grid(ft_cdiv(H, UB), ft_cdiv(B, two ? 32 : 16), 2);
+  dim3 grid(ft_cdiv(H, UB), ft_cdiv(B, two ? 32 : 16), ND);
   const int ngroups = ft_cdiv(H, 16);
   for (int s = 0; s < T; ++s) {
     a.s = s;
@@ -577,6 +578,13 @@ int ft_lstm_fwd(const float* xp, const float* whh_f, const float* whh_r, const f
   hipStream_t s = (hipStream_t)stream;
   return rnn_fwd<4>(xp, whh_f, whh_r, bhh_f, bhh_r, out_raw, cstate, gates, lens, B, T, H, workspace,
                     workspace_bytes, s);
+}
+
+int ft_lstm_fwd_uni(const float* xp, const float* whh, const float* bhh, float* out_raw, float* cstate, int B, int T,
+                    int H, void* workspace, size_t workspace_bytes, void* stream) {
+  FT_REQUIRE(B > 0 && T >= 0 && H > 0, "lstm_fwd_uni: bad dims");
+  return rnn_fwd<4, 1>(xp, whh, whh, bhh, bhh, out_raw, cstate, nullptr, nullptr, B, T, H, workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }
 
 int ft_lstm_bwd(const float* dout, const float* out_raw, const float* cstate, const float* gates,

@@ -1543,7 +1543,7 @@ int fwd_persistent(RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
   Geom geo;
   geo.nchunks = H / ((wide || gru_wide) ? 16 : 8);
   geo.nbg = ft_cdiv(B, MB);
-  geo.total = 2 * geo.nbg * geo.nchunks;
+  geo.total = a.ND * geo.nbg * geo.nchunks;      // ND = 1: the forward direction's groups only (the workspace keeps two)
   geo.xcd_aware = env_int("FT_RNN_XCDMAP", 1);
   geo.sig_per_wave = env_int("FT_RNN_SIG", 1);
   geo.max_spins = g_max_spins;

@@ -1,0 +1,449 @@
+// Tacotron teacher-forced attention recurrence for gfx950 (models/tacotron.py: Decoder.attn_rnn, LSA, context).
+//
+// Under teacher forcing the recurrence is closed over {h_attn, context, cumulative, attention}: the prenet and the
+// prenet half of the GRU input projection are known for all S steps in advance (P [S,B,768], b_ih included), and
+// nothing from the decoder LSTMs feeds back.  What is left per step is a fixed chain of three launches:
+//
+//   1. ft_taco_gru_kernel      grid (256/UB unit blocks, ceil(B/16) batch tiles), 256 threads
+//        GRUCell (gates r, z, n; h' = (1-z) n + z h) for 16 items x UB = 4 hidden units.  The 16 x 16 product
+//        [context | h] (K = 512) x [4 units x (r, z, n_ctx, n_h)] runs on v_mfma_f32_16x16x4_f32, K split over the
+//        four waves (the context half against W_ih[:, :256], the h half against W_hh); the r and z columns add both
+//        halves, the n gate keeps them apart (n = tanh(n_x + n_ctx + r * (n_h + b_hn))).  The 768 x 512 weights are
+//        spread over the 64 unit blocks, so each step reads them once per batch tile chip-wide.  The workgroup then
+//        forms its share of the LSA query, qp[ub][b][:] = W[:, u0:u0+UB] h'[b, u0:u0+UB] (no cross-workgroup
+//        reduction: the next kernel sums the 64 slabs in a fixed order, so the result does not depend on scheduling).
+//   2. ft_taco_energy_kernel   grid (ceil(Tx/TC) token chunks, B, 4 column quarters), 256 threads
+//        q = b_W + b_L + sum of the 64 slabs (the quarter's 64 columns); location conv (2 -> 32 filters, k = 31, zero
+//        padding at 0 and Tx) of [cumulative, attention] on the VALU into LDS; the [TC x 32] x [32 x 64] projection L
+//        on MFMA; per token the partial energy v . tanh(q + enc_proj + L conv) over the quarter's columns (hardware
+//        exp / rcp tanh, |error| <= ~2e-7 per term).
+//   3. ft_taco_context_kernel  grid (8 column chunks, B), 256 threads
+//        energies = sum of the 4 partials; softmax over all Tx columns (no mask, like the reference); chunk 0 writes attn[b, s, :], attention := p and
+//        cumulative += p; every chunk forms 32 columns of context = p @ enc_pq (each recomputes the softmax from the
+//        Tx energies, so no chunk waits for another).
+// Each kernel requests all of its global operands before its first dependent use: a step costs three launches and
+// one memory round trip per launch.
+//
+// Every sum runs in a fixed order and no atomics are used: the same inputs give the same bits, whether the call
+// keeps the histories (forward) or not (align).  The LSA state (cumulative, attention) lives in the workspace for the
+// duration of the call.  All arithmetic is fp32 (the f32 MFMA products are exact fp32).
+#include "ft_common.h"
+#include "fwdtaco_hip.h"
+
+namespace {
+
+constexpr int DA = 256;          // decoder / attention dims (the reference runs with no other value)
+constexpr int NG = 3 * DA;       // GRU gate rows
+constexpr int NF = 32;           // location filters
+constexpr int KW = 31;           // location kernel width (padding 15)
+constexpr int KP = KW / 2;
+constexpr int UB = 4;            // hidden units per GRU workgroup
+constexpr int NUB = DA / UB;     // query partial slabs
+constexpr int TC = 32;           // tokens per energy workgroup
+constexpr int NCQ = 4;           // attention-column quarters per energy workgroup grid (partial energies)
+constexpr int NAC = 8;           // context column chunks per item
+constexpr int TXMAX = 1024;
+constexpr int CLD = NF + 4;      // LDS row stride of the conv outputs (16-B aligned rows)
+
+struct AttendArgs {
+  const float* enc_proj;   // [B,Tx,256]
+  const float* enc_pq;     // [B,Tx,256]
+  const float* P;          // [S,B,768]
+  const float* wih;        // [768, ld_wih]: context columns 0..255
+  long ld_wih;
+  const float* whh;        // [768,256]
+  const float* bhh;        // [768]
+  const float* W;          // [256,256]
+  const float* bW;         // [256]
+  const float* cw;         // [32,2,31]
+  const float* L;          // [256,32]
+  const float* bL;         // [256]
+  const float* v;          // [256]
+  float* attn;             // [B,S,Tx]
+  float* qp;               // [NUB,B,256]
+  float* E;                // [B,NCQ,Tx] partial energies
+  float* cum;              // [B,Tx]
+  float* att;              // [B,Tx]
+  int B, Tx, S;
+  long ldh;                // row stride (floats) of the h / context state rows
+};
+
+__device__ __forceinline__ void mfma4(const float4& a, const float4& b, f32x4& acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+}
+
+// f32 16x16x4 operand convention used below: lane (i = lane & 15, q = lane >> 4) holds row i, k = 16c + 4q .. +3 of
+// both operands; the accumulator holds D[4q + e][i].
+
+// ---- 1. GRUCell + query partials ------------------------------------------------------------------------------------
+// 16 columns = UB (4) units x (r, z, n from the context, n from h); the four waves split K = 512 into quarters (waves
+// 0, 1: the context half against W_ih[:, :256]; waves 2, 3: the h half against W_hh), so a wave moves 8 KB of each
+// operand and issues 32 MFMAs.
+__global__ __launch_bounds__(256) void ft_taco_gru_kernel(AttendArgs a, int s, const float* __restrict__ hprev,
+                                                           const float* __restrict__ cprev, float* __restrict__ hout) {
+  __shared__ float red[4][16][17];
+  __shared__ float hs[16][UB];
+  const int ub = blockIdx.x, u0 = ub * UB, b0 = blockIdx.y * 16;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
+  const int B = a.B;
+
+  // cell operands (requested before the matmul): thread tid < 16 * UB owns item b0 + tid / UB, unit u0 + tid % UB
+  const int crow = tid / UB, cj = tid % UB, cb = b0 + crow, cu = u0 + cj;
+  const bool cact = tid < 16 * UB && cb < B;
+  float xr = 0.f, xz = 0.f, xn = 0.f, br = 0.f, bz = 0.f, bn = 0.f, hp = 0.f;
+  if (cact) {
+    const float* pr = a.P + ((long)s * B + cb) * NG;
+    xr = pr[cu]; xz = pr[DA + cu]; xn = pr[2 * DA + cu];
+    br = a.bhh[cu]; bz = a.bhh[DA + cu]; bn = a.bhh[2 * DA + cu];
+    if (s > 0) hp = hprev[(long)cb * a.ldh + cu];
+  }
+  // query-partial weights of this thread's row (consumed at the end): requested with the matmul operands
+  const float4 w0 = *reinterpret_cast<const float4*>(a.W + (long)tid * DA + u0);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (s > 0) {                          // step 0: h = context = 0, the products vanish
+    constexpr int KQ = DA / 2;          // K per wave
+    const int kh = wave >> 1, k0 = KQ * (wave & 1);
+    const int bA = min(b0 + l15, B - 1);          // rows past B read item B-1 and are never consumed
+    const float* arow = (kh == 0 ? cprev : hprev) + (long)bA * a.ldh + k0;
+    const int qn = l15 & 3, u = u0 + (l15 >> 2);
+    const int g = qn < 2 ? qn : 2;
+    const bool zero = (kh == 0 && qn == 3) || (kh == 1 && qn == 2);
+    const float* brow = (kh == 0 ? a.wih + (long)(g * DA + u) * a.ld_wih : a.whh + (long)(g * DA + u) * DA) + k0;
+    // the wave's whole K slice of both operands is requested before the first MFMA: one memory round trip
+    float4 av[KQ / 16], bv[KQ / 16];
+#pragma unroll
+    for (int c = 0; c < KQ / 16; ++c) {
+      av[c] = *reinterpret_cast<const float4*>(arow + 16 * c + 4 * q);
+      bv[c] = *reinterpret_cast<const float4*>(brow + 16 * c + 4 * q);
+    }
+#pragma unroll
+    for (int c = 0; c < KQ / 16; ++c) mfma4(av[c], zero ? make_float4(0.f, 0.f, 0.f, 0.f) : bv[c], acc);
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) red[wave][4 * q + e][l15] = acc[e];
+  __syncthreads();
+
+  if (tid < 16 * UB) {
+    float h = 0.f;
+    if (cact) {
+      const int c0 = 4 * cj;
+      const float sr = (red[0][crow][c0] + red[1][crow][c0]) + (red[2][crow][c0] + red[3][crow][c0]);
+      const float sz = (red[0][crow][c0 + 1] + red[1][crow][c0 + 1]) + (red[2][crow][c0 + 1] + red[3][crow][c0 + 1]);
+      const float nx = red[0][crow][c0 + 2] + red[1][crow][c0 + 2];
+      const float nh = red[2][crow][c0 + 3] + red[3][crow][c0 + 3];
+      const float r = ft_sigmoid(xr + sr + br);
+      const float z = ft_sigmoid(xz + sz + bz);
+      const float n = ft_tanh(xn + nx + r * (nh + bn));
+      h = (1.f - z) * n + z * hp;
+      hout[(long)cb * a.ldh + cu] = h;
+    }
+    hs[crow][cj] = h;
+  }
+  __syncthreads();
+
+  // query partial of this unit block: qp[ub][b][i] = sum_j W[i, u0 + j] h'[b, u0 + j]
+  const int i = tid;
+  for (int row = 0; row < 16 && b0 + row < B; ++row) {
+    const float* hr = hs[row];
+    float v = w0.x * hr[0];
+    v = fmaf(w0.y, hr[1], v); v = fmaf(w0.z, hr[2], v); v = fmaf(w0.w, hr[3], v);
+    a.qp[((long)ub * B + b0 + row) * DA + i] = v;
+  }
+}
+
+// ---- 2. LSA energies --------------------------------------------------------------------------------------------------
+// Workgroup = (TC tokens, item, NCQ-th of the 256 attention columns): it writes the partial energy of its 64 columns,
+// E[b][cq][t]; the context kernel adds the NCQ partials.  Every global operand of the workgroup (its columns of the 64
+// query slabs, the location window, the conv weights, its L rows, enc_proj at the lane's positions) is requested at
+// the top, so the kernel pays one memory round trip; the phases after it run from registers and LDS.
+__global__ __launch_bounds__(256) void ft_taco_energy_kernel(AttendArgs a) {
+  constexpr int NT = TC / 16;
+  constexpr int WIN = TC + KW - 1;
+  constexpr int CQ = DA / NCQ;                    // 64 columns: one 16-column tile per wave
+  constexpr int SG = 256 / CQ;                    // slab groups of the query sum
+  __shared__ float qsum[SG][CQ];
+  __shared__ float locw[2][WIN];
+  __shared__ float cws[NF][2 * KW + 1];           // odd row stride: the 32 filters of a wave hit 32 banks
+  __shared__ __attribute__((aligned(16))) float convs[TC][CLD];
+  __shared__ float esum[4][TC];
+  const int t0 = blockIdx.x * TC, b = blockIdx.y, cq = blockIdx.z;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
+  const int B = a.B, Tx = a.Tx;
+  const int col = CQ * cq + 16 * wave + l15;      // this lane's attention column in the MFMA / energy phases
+
+  float qv[NUB / SG];
+  {
+    const int qc = CQ * cq + tid % CQ, sg = tid / CQ;
+#pragma unroll
+    for (int j = 0; j < NUB / SG; ++j) qv[j] = a.qp[((long)(sg * (NUB / SG) + j) * B + b) * DA + qc];
+  }
+  for (int i = tid; i < 2 * WIN; i += 256) {
+    const int c = i / WIN, o = i - c * WIN, t = t0 - KP + o;
+    locw[c][o] = (t >= 0 && t < Tx) ? (c == 0 ? a.cum : a.att)[(long)b * Tx + t] : 0.f;
+  }
+  for (int i = tid; i < NF * 2 * KW; i += 256) cws[i / (2 * KW)][i % (2 * KW)] = a.cw[i];
+  // L row of the lane's column (MFMA B operand): k = 16c + 4q .. +3
+  float4 bv[NF / 16];
+#pragma unroll
+  for (int c = 0; c < NF / 16; ++c) bv[c] = *reinterpret_cast<const float4*>(a.L + (long)col * NF + 16 * c + 4 * q);
+  const float qb = a.bW[col] + a.bL[col], vv = a.v[col];
+  // enc_proj at the lane's accumulator positions: tokens 16tt + 4q + e
+  float epv[NT][4];
+#pragma unroll
+  for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int t = t0 + 16 * tt + 4 * q + e;
+      epv[tt][e] = a.enc_proj[((long)b * Tx + min(t, Tx - 1)) * DA + col];
+    }
+  {
+    float v = 0.f;
+#pragma unroll
+    for (int j = 0; j < NUB / SG; ++j) v += qv[j];
+    qsum[tid / CQ][tid % CQ] = v;
+  }
+  __syncthreads();
+
+  // location conv: thread -> filter tid % 32, tokens 4 (tid / 32) .. +3, window held in registers
+  {
+    const int f = tid & 31, tb = 4 * (tid >> 5);
+    float cv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      float win[4 + KW - 1];
+#pragma unroll
+      for (int j = 0; j < 4 + KW - 1; ++j) win[j] = locw[c][tb + j];
+#pragma unroll
+      for (int k = 0; k < KW; ++k) {
+        const float w = cws[f][c * KW + k];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cv[i] = fmaf(w, win[i + k], cv[i]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) convs[tb + i][f] = cv[i];
+  }
+  __syncthreads();
+
+  // L projection on MFMA: [TC tokens x 32 filters] x [32 x the wave's 16 columns]
+  f32x4 acc[NT];
+#pragma unroll
+  for (int tt = 0; tt < NT; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < NF / 16; ++c)
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt)
+      mfma4(*reinterpret_cast<const float4*>(&convs[16 * tt + l15][16 * c + 4 * q]), bv[c], acc[tt]);
+
+  // partial energies: v . tanh(q + enc_proj + L conv) over the 16 column lanes, then over the 4 waves
+  const int lc = 16 * wave + l15;
+  float qcol = qb;
+#pragma unroll
+  for (int g = 0; g < SG; ++g) qcol += qsum[g][lc];
+#pragma unroll
+  for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float sum = vv * ft_tanh_fast(qcol + epv[tt][e] + acc[tt][e]);
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
+      if (l15 == 0) esum[wave][16 * tt + 4 * q + e] = sum;
+    }
+  __syncthreads();
+  if (tid < TC && t0 + tid < Tx)
+    a.E[((long)b * NCQ + cq) * Tx + t0 + tid] = ((esum[0][tid] + esum[1][tid]) + esum[2][tid]) + esum[3][tid];
+}
+
+// ---- 3. softmax, LSA state, context ---------------------------------------------------------------------------------
+__device__ __forceinline__ float block_max(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+__global__ __launch_bounds__(256) void ft_taco_context_kernel(AttendArgs a, int s, float* __restrict__ cout) {
+  constexpr int CC = DA / NAC;               // context columns per workgroup
+  constexpr int TG = 256 / CC;               // token groups
+  constexpr int PF = 24;                     // enc_pq values per thread requested before the softmax (Tx <= PF * TG)
+  __shared__ float p[TXMAX];
+  __shared__ float red[256];
+  __shared__ float sh[4];
+  const int ac = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int Tx = a.Tx;
+  const int col = CC * ac + tid % CC, tg = tid / CC;
+  const float* pq = a.enc_pq + (long)b * Tx * DA + col;
+  float xv[PF];
+#pragma unroll
+  for (int j = 0; j < PF; ++j) {
+    const int t = tg + TG * j;
+    xv[j] = t < Tx ? pq[(long)t * DA] : 0.f;
+  }
+  const float* e = a.E + (long)b * NCQ * Tx;
+  float m = -INFINITY;
+  for (int t = tid; t < Tx; t += 256) {
+    const float v = (e[t] + e[Tx + t]) + (e[2 * Tx + t] + e[3 * Tx + t]);
+    p[t] = v;
+    m = fmaxf(m, v);
+  }
+  m = block_max(m, sh);
+  float z = 0.f;
+  for (int t = tid; t < Tx; t += 256) {
+    const float x = expf(p[t] - m);
+    p[t] = x;
+    z += x;
+  }
+  z = block_sum(z, sh);              // (its barriers also order the p[] writes above before the reads below)
+  for (int t = tid; t < Tx; t += 256) {
+    const float x = p[t] / z;
+    p[t] = x;
+    if (ac == 0) {
+      const long o = (long)b * Tx + t;
+      a.attn[((long)b * a.S + s) * Tx + t] = x;
+      a.att[o] = x;
+      a.cum[o] += x;
+    }
+  }
+  __syncthreads();
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < PF; ++j) {
+    const int t = tg + TG * j;
+    if (t < Tx) acc[j & 3] = fmaf(p[t], xv[j], acc[j & 3]);
+  }
+  int t = tg + TG * PF;
+  for (; t + 3 * TG < Tx; t += 4 * TG) {
+    float x[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = pq[(long)(t + i * TG) * DA];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = fmaf(p[t + i * TG], x[i], acc[i]);
+  }
+  for (; t < Tx; t += TG) acc[0] = fmaf(p[t], pq[(long)t * DA], acc[0]);
+  red[tid] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  __syncthreads();
+  if (tid < CC) {
+    float v = 0.f;
+#pragma unroll
+    for (int g = 0; g < TG; ++g) v += red[g * CC + tid];
+    cout[(long)b * a.ldh + col] = v;
+  }
+}
+
+// ---- teacher-forced prenet input frames -----------------------------------------------------------------------------
+__global__ void ft_taco_frames_kernel(const float* __restrict__ mel, int n_mels, int Tm, int r, int S, int B,
+                                      float* __restrict__ out) {
+  const long n = (long)S * B * n_mels;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % n_mels);
+    const long sb = i / n_mels;
+    const int b = (int)(sb % B), st = (int)(sb / B);
+    float v = 0.f;
+    if (st > 0) v = mel[((long)b * n_mels + c) * Tm + (long)st * r - 1];
+    out[i] = v;
+  }
+}
+
+__global__ void ft_taco_add_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out,
+                                   long n) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    out[i] = x[i] + y[i];
+}
+
+struct WsLayout {
+  size_t qp, E, cum, att, zero, ring, total;
+};
+WsLayout ws_layout(int B, int Tx) {
+  WsLayout w;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t o = 0;
+  w.qp = o;   o = al(o + sizeof(float) * (size_t)NUB * B * DA);
+  w.E = o;    o = al(o + sizeof(float) * (size_t)B * NCQ * Tx);
+  w.cum = o;  o = al(o + sizeof(float) * (size_t)B * Tx);       // cum | att | zero: one memset
+  w.att = o;  o = al(o + sizeof(float) * (size_t)B * Tx);
+  w.zero = o; o = al(o + sizeof(float) * (size_t)B * 2 * DA);
+  w.ring = o; o = al(o + sizeof(float) * (size_t)2 * B * 2 * DA);   // [parity][B][context | h] when no history
+  w.total = o;
+  return w;
+}
+
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+size_t ft_taco_attend_workspace(int B, int Tx) {
+  if (B < 1 || Tx < 1 || Tx > TXMAX) return 0;
+  return ws_layout(B, Tx).total;
+}
+
+int ft_taco_attend(const float* enc_proj, const float* enc_pq, const float* P, const float* w_ih, long ld_w_ih,
+                   const float* w_hh, const float* b_hh, const float* W, const float* b_W, const float* conv_w,
+                   const float* L, const float* b_L, const float* v, float* attn, float* hist, int B, int Tx, int S,
+                   void* ws, size_t ws_bytes, void* stream) {
+  FT_REQUIRE(B >= 1, "taco_attend: B must be >= 1 (got %d)", B);
+  FT_REQUIRE(Tx >= 1 && Tx <= TXMAX, "taco_attend: Tx must be in 1..%d (got %d)", TXMAX, Tx);
+  FT_REQUIRE(S >= 1, "taco_attend: S must be >= 1 (got %d)", S);
+  FT_REQUIRE(ld_w_ih >= DA && ld_w_ih % 4 == 0, "taco_attend: ld_w_ih must be a multiple of 4, >= 256");
+  FT_REQUIRE(enc_proj && enc_pq && P && w_ih && w_hh && b_hh && W && b_W && conv_w && L && b_L && v && attn,
+             "taco_attend: null operand");
+  FT_REQUIRE(al16(w_ih) && al16(w_hh) && al16(W) && al16(L) && al16(hist) && al16(ws),
+             "taco_attend: weights, history and workspace must be 16-byte aligned");
+  const WsLayout wl = ws_layout(B, Tx);
+  FT_REQUIRE(ws && ws_bytes >= wl.total, "taco_attend: workspace too small (%zu < %zu bytes)", ws_bytes, wl.total);
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)ws;
+  AttendArgs a;
+  a.enc_proj = enc_proj; a.enc_pq = enc_pq; a.P = P; a.wih = w_ih; a.ld_wih = ld_w_ih; a.whh = w_hh; a.bhh = b_hh;
+  a.W = W; a.bW = b_W; a.cw = conv_w; a.L = L; a.bL = b_L; a.v = v; a.attn = attn;
+  a.qp = (float*)(w + wl.qp); a.E = (float*)(w + wl.E); a.cum = (float*)(w + wl.cum); a.att = (float*)(w + wl.att);
+  a.B = B; a.Tx = Tx; a.S = S;
+  a.ldh = 2 * DA;
+  float* zero = (float*)(w + wl.zero);
+  float* ring = (float*)(w + wl.ring);
+  (void)hipMemsetAsync(w + wl.cum, 0, wl.ring - wl.cum, st);
+  const long slab = (long)B * 2 * DA;     // one step of [context | h] rows
+  auto state = [&](int step) -> float* { return hist ? hist + step * slab : ring + (step & 1) * slab; };
+  const dim3 g1(NUB, ft_cdiv(B, 16)), g2(ft_cdiv(Tx, TC), B, NCQ), g3(NAC, B);
+  for (int s = 0; s < S; ++s) {
+    const float* prev = s == 0 ? zero : state(s - 1);
+    float* cur = state(s);
+    hipLaunchKernelGGL(ft_taco_gru_kernel, g1, dim3(256), 0, st, a, s, prev + DA, prev, cur + DA);
+    hipLaunchKernelGGL(ft_taco_energy_kernel, g2, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(ft_taco_context_kernel, g3, dim3(256), 0, st, a, s, cur);
+  }
+  return ft_check_launch("taco_attend");
+}
+
+int ft_taco_frames(const float* mel, int B, int n_mels, int Tm, int r, int S, float* out, void* stream) {
+  FT_REQUIRE(B >= 1 && n_mels >= 1 && r >= 1 && S >= 1, "taco_frames: bad dims");
+  FT_REQUIRE((long)(S - 1) * r - 1 < Tm, "taco_frames: step %d reads frame %ld of %d", S - 1, (long)(S - 1) * r - 1, Tm);
+  const long n = (long)S * B * n_mels;
+  hipLaunchKernelGGL(ft_taco_frames_kernel, dim3((unsigned)(n < 256L * 1024 ? ft_cdiv(n, 256) : 1024)), dim3(256), 0,
+                     (hipStream_t)stream, mel, n_mels, Tm, r, S, B, out);
+  return ft_check_launch("taco_frames");
+}
+
+int ft_taco_add(const float* x, const float* y, float* out, long n, void* stream) {
+  FT_REQUIRE(n >= 0, "taco_add: bad size");
+  if (n == 0) return FT_OK;
+  hipLaunchKernelGGL(ft_taco_add_kernel, dim3((unsigned)(n < 256L * 1024 ? ft_cdiv(n, 256) : 1024)), dim3(256), 0,
+                     (hipStream_t)stream, x, y, out, n);
+  return ft_check_launch("taco_add");
+}
+
+}  // extern "C"

@@ -1,0 +1,318 @@
+"""MI355X-native Tacotron teacher: drop-in for models/tacotron.py (the model that produces the attentions durations
+are extracted from).  Same constructor, module tree, state_dict (254 entries for the singlespeaker config), buffers and
+seed-identical initialisation; the teacher-forced forward() and align() run on the package's HIP kernels.
+
+    reference (models/tacotron.py)                 here
+    Tacotron.forward(batch), teacher forcing        Tacotron.forward(batch): inference only (no grad, no training mode)
+    -- (train_tacotron.py:117-136 runs forward)     Tacotron.align(batch): encoder + attention recurrence only
+    Tacotron.generate                               not implemented (raises FtError)
+
+Under teacher forcing the attention recurrence (attn_rnn GRUCell + LSA + context) is closed over
+{h_attn, context, cumulative, attention}; nothing from the decoder LSTMs feeds back into it.  So:
+  1. encoder (Embedding -> PreNet -> CBHG, model.CBHG's eval path) and the two token projections, one GEMM each;
+  2. the decoder PreNet over all S = ceil(steps / r) teacher-forced frames (mel[:, :, i*r - 1], a zero frame at i = 0)
+     and the prenet half of the GRU input projection, as batched GEMMs;
+  3. ft_taco_attend: all S steps of the recurrence, three launches per step -> attn [B,S,Tx] and, for forward(), the
+     history [S,B,512] of [context | h_attn];
+  4. forward() only: rnn_input on the history, then each residual LSTMCell as one-direction LSTM recurrence
+     (ft_lstm_fwd_uni) behind one input-projection GEMM, the residual adds, mel_proj restricted to the 80 * r rows
+     the [:, :, :r] slice keeps, the postnet CBHG and post_proj.
+
+Dropout: the encoder PreNet and the decoder PreNet apply dropout 0.5 when their own `training` flag is set (extraction
+mode, train_tacotron.py:118-119, is `model.eval(); model.decoder.prenet.train()`); every other module must be in eval
+mode.  Each dropout site draws its seed from torch's default host generator, `torch.randint(0, 2**62, (1,))`, in this
+order: encoder.pre_net fc1, encoder.pre_net fc2 (only when encoder.pre_net is training), decoder.prenet fc1,
+decoder.prenet fc2 -- so torch.manual_seed(k) reproduces the masks, as it does for the reference's F.dropout.  A site's mask
+is ft_dropout's counter-based mask over the site's tensor in its storage order: [B,Tx,256] and [B,Tx,128] for the
+encoder, TIME-major [S,B,256] and [S,B,128] for the decoder (the mask of an element is hip.dropout(ones, 0.5, seed)
+at the same position).  One mask per site covers all S steps; the reference draws a fresh one per step from torch's
+RNG, which cannot be matched bit for bit either way.
+"""
+import math
+from pathlib import Path
+from typing import Any, Dict, Tuple, Union
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import hip as H
+from .hip import _p, _stream
+from .model import CBHG
+
+NUM_CHARS_DEFAULT = 135      # len(utils.text.symbols.phonemes)
+MAX_TX = 1024                # ft_taco_attend's token bound (the duration kernel's)
+
+FtError = _lib.FtError
+
+
+def dropout_seed() -> int:
+    """seed of one dropout site: one draw from torch's default host generator (see the module docstring)"""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+class Encoder(nn.Module):
+    """models/tacotron.py:11-26"""
+
+    def __init__(self, embed_dims, num_chars, cbhg_channels, K, num_highways, dropout):
+        super().__init__()
+        self.embedding = nn.Embedding(num_chars, embed_dims)
+        self.pre_net = PreNet(embed_dims)
+        self.cbhg = CBHG(K=K, in_channels=cbhg_channels, channels=cbhg_channels,
+                         proj_channels=[cbhg_channels, cbhg_channels], num_highways=num_highways)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B,Tx] int64 -> [B,Tx,2*cbhg_channels]"""
+        y = H.embedding_fwd(x.contiguous(), self.embedding.weight)
+        y = self.pre_net(y)
+        return self.cbhg(y)
+
+
+class PreNet(nn.Module):
+    """models/tacotron.py:29-45: fc1 -> ReLU -> dropout -> fc2 -> ReLU -> dropout, over the last dim"""
+
+    def __init__(self, in_dims, fc1_dims=256, fc2_dims=128, dropout=0.5):
+        super().__init__()
+        self.fc1 = nn.Linear(in_dims, fc1_dims)
+        self.fc2 = nn.Linear(fc1_dims, fc2_dims)
+        self.p = dropout
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = H.linear_fwd(x, self.fc1.weight, self.fc1.bias, relu=True)
+        if self.training and self.p > 0:
+            y = H.dropout(y, self.p, dropout_seed())
+        y = H.linear_fwd(y, self.fc2.weight, self.fc2.bias, relu=True)
+        if self.training and self.p > 0:
+            y = H.dropout(y, self.p, dropout_seed())
+        return y
+
+
+class LSA(nn.Module):
+    """models/tacotron.py:65-99 (parameter container; the recurrence is ft_taco_attend)"""
+
+    def __init__(self, attn_dim, kernel_size=31, filters=32):
+        super().__init__()
+        self.conv = nn.Conv1d(2, filters, padding=(kernel_size - 1) // 2, kernel_size=kernel_size, bias=False)
+        self.L = nn.Linear(filters, attn_dim, bias=True)
+        self.W = nn.Linear(attn_dim, attn_dim, bias=True)
+        self.v = nn.Linear(attn_dim, 1, bias=False)
+
+
+class Decoder(nn.Module):
+    """models/tacotron.py:102-174 (parameter container)"""
+    max_r = 20
+
+    def __init__(self, n_mels, decoder_dims, lstm_dims):
+        super().__init__()
+        self.register_buffer('r', torch.tensor(1, dtype=torch.int))
+        self.n_mels = n_mels
+        self.prenet = PreNet(n_mels)
+        self.attn_net = LSA(decoder_dims)
+        self.attn_rnn = nn.GRUCell(decoder_dims + decoder_dims // 2, decoder_dims)
+        self.rnn_input = nn.Linear(2 * decoder_dims, lstm_dims)
+        self.res_rnn1 = nn.LSTMCell(lstm_dims, lstm_dims)
+        self.res_rnn2 = nn.LSTMCell(lstm_dims, lstm_dims)
+        self.mel_proj = nn.Linear(lstm_dims, n_mels * self.max_r, bias=False)
+
+
+class Tacotron(nn.Module):
+    """Drop-in for models/tacotron.py:177-373 (teacher-forced forward and align; no training, no generate)."""
+
+    def __init__(self, embed_dims: int, num_chars: int, encoder_dims: int, decoder_dims: int, n_mels: int,
+                 postnet_dims: int, encoder_k: int, lstm_dims: int, postnet_k: int, num_highways: int,
+                 dropout: float, stop_threshold: float, speaker_emb_dim=256) -> None:
+        # the reference only runs with these (PreNet's 128 outputs and the postnet's [256, 80] projection are fixed);
+        # the attention kernel is specialised to them
+        if encoder_dims != 128 or decoder_dims != 256 or n_mels != 80:
+            raise FtError(f'Tacotron: encoder_dims, decoder_dims and n_mels must be 128, 256 and 80, as the reference '
+                          f'requires (got {encoder_dims}, {decoder_dims}, {n_mels})')
+        super().__init__()
+        self.n_mels = n_mels
+        self.lstm_dims = lstm_dims
+        self.decoder_dims = decoder_dims
+        self.encoder = Encoder(embed_dims, num_chars, encoder_dims, encoder_k, num_highways, dropout)
+        self.encoder_proj_query = nn.Linear(decoder_dims + speaker_emb_dim, decoder_dims, bias=False)
+        self.encoder_proj = nn.Linear(decoder_dims + speaker_emb_dim, decoder_dims, bias=False)
+        self.decoder = Decoder(n_mels, decoder_dims, lstm_dims)
+        self.postnet = CBHG(postnet_k, n_mels, postnet_dims, [256, 80], num_highways)
+        self.post_proj = nn.Linear(postnet_dims * 2, n_mels, bias=False)
+        self.speaker_emb_dim = speaker_emb_dim
+        self.init_model()
+        self.register_buffer('step', torch.zeros(1, dtype=torch.long))
+        self.register_buffer('stop_threshold', torch.tensor(stop_threshold, dtype=torch.float32))
+        self._packs = {}
+
+    def __repr__(self):
+        return f'Tacotron, num params: {sum(p.numel() for p in self.parameters())}'
+
+    @property
+    def r(self) -> int:
+        return self.decoder.r.item()
+
+    @r.setter
+    def r(self, value: int) -> None:
+        self.decoder.r = self.decoder.r.new_tensor(value, requires_grad=False)
+
+    def init_model(self):
+        for p in self.parameters():
+            if p.dim() > 1:
+                nn.init.xavier_uniform_(p)
+
+    def get_step(self):
+        return self.step.data.item()
+
+    def reset_step(self):
+        self.step = self.step.data.new_tensor(1)
+
+    @classmethod
+    def from_config(cls, config: Dict[str, Any]) -> 'Tacotron':
+        model_config = config['tacotron']['model']
+        model_config['num_chars'] = config.get('num_chars', NUM_CHARS_DEFAULT)     # reference: len(phonemes)
+        model_config['n_mels'] = config['dsp']['num_mels']
+        return Tacotron(**model_config)
+
+    @classmethod
+    def from_checkpoint(cls, path: Union[Path, str]) -> 'Tacotron':
+        checkpoint = torch.load(path, map_location=torch.device('cpu'), weights_only=True)
+        model = Tacotron.from_config(checkpoint['config'])
+        model.load_state_dict(checkpoint['model'])
+        return model
+
+    def generate(self, *args, **kwargs):
+        raise FtError('Tacotron.generate (autoregressive synthesis with a stop threshold) is not implemented here: '
+                      'this Tacotron runs the teacher-forced forward() and align() only')
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def _check(self, batch) -> Tuple[torch.Tensor, torch.Tensor, Any]:
+        dropout_ok = {id(m) for pn in (self.encoder.pre_net, self.decoder.prenet) for m in pn.modules()}
+        for name, m in self.named_modules():
+            if m.training and id(m) not in dropout_ok:
+                raise FtError(f'Tacotron: module {name or "<root>"} is in training mode; training the teacher is not '
+                              'implemented here (use model.eval(), optionally with model.decoder.prenet.train() for '
+                              'the extraction mode of train_tacotron.py)')
+        w = self.encoder.embedding.weight
+        if not w.is_cuda:
+            raise FtError('Tacotron runs on an MI355X (HIP) device only: move the model with .cuda()')
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            # as model._eval_needs_no_grad: refuse rather than hand back tensors that silently carry no gradient
+            raise FtError('Tacotron.forward / align is an inference path (no autograd graph): call it under '
+                          'torch.no_grad(), or with parameters that do not require grad')
+        x = batch['x'].to(w.device, non_blocking=True)
+        mel = batch['mel'].to(w.device, non_blocking=True)
+        if x.dim() != 2 or mel.dim() != 3 or mel.shape[0] != x.shape[0] or mel.shape[1] != self.n_mels:
+            raise FtError(f'Tacotron: expected x [B,Tx] and mel [B,{self.n_mels},steps], got {tuple(x.shape)} and '
+                          f'{tuple(mel.shape)}')
+        if not 1 <= x.shape[1] <= MAX_TX:
+            raise FtError(f'Tacotron: Tx must be in 1..{MAX_TX} (got {x.shape[1]})')
+        if mel.shape[2] < 1:
+            raise FtError('Tacotron: the mel has no frames')
+        semb = None
+        if self.speaker_emb_dim > 0:
+            semb = batch.get('speaker_emb')
+            if semb is None:
+                raise FtError(f'Tacotron: speaker_emb_dim = {self.speaker_emb_dim} needs batch["speaker_emb"] [B, '
+                              f'{self.speaker_emb_dim}]')
+            semb = semb.to(device=w.device, dtype=torch.float32, non_blocking=True).contiguous()
+            if semb.shape != (x.shape[0], self.speaker_emb_dim):
+                raise FtError(f'Tacotron: speaker_emb must be [B, {self.speaker_emb_dim}], got {tuple(semb.shape)}')
+        r = self.r
+        if not 1 <= r <= Decoder.max_r:
+            raise FtError(f'Tacotron: r must be in 1..{Decoder.max_r} (got {r})')
+        return x.to(torch.int64).contiguous(), mel.to(torch.float32).contiguous(), semb
+
+    def _pack(self, key, src: torch.Tensor, make):
+        """weight-derived operands, rebuilt when the source tensor changes (in-place updates bump _version)"""
+        tag = (src.data_ptr(), src._version, src.device)
+        hit = self._packs.get(key)
+        if hit is None or hit[0] != tag:
+            hit = (tag, make())
+            self._packs[key] = hit
+        return hit[1]
+
+    def _attend_inputs(self, x: torch.Tensor, mel: torch.Tensor, semb):
+        """encoder, the two token projections, the decoder prenet over the S teacher-forced frames and the prenet half
+        of the GRU input projection -> (enc_proj, enc_pq [B,Tx,256], P [S,B,768])"""
+        B, Tx = x.shape
+        r = self.r
+        steps = mel.shape[2]
+        S = math.ceil(steps / r)
+        dec = self.decoder
+        enc = self.encoder(x)                                                   # [B,Tx,256]
+        if semb is not None:
+            enc = H.concat_cols(enc, None, semb, B, Tx)                         # [B,Tx,256+S]
+        ep = H.linear_fwd(enc, self.encoder_proj.weight)
+        epq = H.linear_fwd(enc, self.encoder_proj_query.weight)
+        frames = torch.empty(S, B, self.n_mels, device=x.device, dtype=torch.float32)
+        _lib.call('ft_taco_frames', _p(mel), B, self.n_mels, steps, r, S, _p(frames), _stream())
+        pre = dec.prenet(frames)                                                # [S,B,128]
+        gru = dec.attn_rnn
+        D = self.decoder_dims
+        w_pre = self._pack('w_ih_prenet', gru.weight_ih,
+                           lambda: H.slice_cols(gru.weight_ih.detach()[None], D, D // 2)[0])   # W_ih[:, 256:]
+        return ep, epq, H.linear_fwd(pre, w_pre, gru.bias_ih)                  # P [S,B,768]
+
+    def _attend(self, ep: torch.Tensor, epq: torch.Tensor, P: torch.Tensor, keep_history: bool):
+        """ft_taco_attend -> (attn [B,S,Tx], history [S,B,512] of [context | h_attn], or None)"""
+        B, Tx = ep.shape[:2]
+        S = P.shape[0]
+        gru, lsa = self.decoder.attn_rnn, self.decoder.attn_net
+        attn = torch.empty(B, S, Tx, device=ep.device, dtype=torch.float32)
+        hist = torch.empty(S, B, 2 * self.decoder_dims, device=ep.device, dtype=torch.float32) if keep_history else None
+        ws = H.workspace(_lib.query('ft_taco_attend_workspace', B, Tx), ep.device)
+        _lib.call('ft_taco_attend', _p(ep), _p(epq), _p(P), _p(gru.weight_ih), gru.weight_ih.shape[1],
+                  _p(gru.weight_hh), _p(gru.bias_hh), _p(lsa.W.weight), _p(lsa.W.bias), _p(lsa.conv.weight),
+                  _p(lsa.L.weight), _p(lsa.L.bias), _p(lsa.v.weight), _p(attn), _p(hist), B, Tx, S, _p(ws), ws.numel(),
+                  _stream())
+        return attn, hist
+
+    def align(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """attn_scores [B, S, Tx] of forward(batch), bit for bit, from the encoder, the decoder prenet and the attention
+        recurrence alone (the mel path is not run)."""
+        x, mel, semb = self._check(batch)
+        attn, _ = self._attend(*self._attend_inputs(x, mel, semb), keep_history=False)
+        return attn
+
+    def _lstm(self, cell: nn.LSTMCell, x: torch.Tensor) -> torch.Tensor:
+        """nn.LSTMCell over the S steps of x [S,B,L] from zero states -> h [S,B,L]"""
+        S, B, Ld = x.shape
+        xp = H.linear_fwd(x, cell.weight_ih, cell.bias_ih)                     # [S,B,4L]
+        out = torch.empty(S, B, Ld, device=x.device, dtype=torch.float32)
+        cst = torch.empty(S, B, Ld, device=x.device, dtype=torch.float32)
+        ws, nb = H._rnn_workspace(4, B, Ld, x.device)
+        _lib.call('ft_lstm_fwd_uni', _p(xp), _p(cell.weight_hh), _p(cell.bias_hh), _p(out), _p(cst), B, S, Ld, _p(ws),
+                  nb, _stream())
+        return out
+
+    def _add(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        out = torch.empty_like(x)
+        _lib.call('ft_taco_add', _p(x), _p(y), _p(out), x.numel(), _stream())
+        return out
+
+    def forward(self, batch: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """models/tacotron.py:219-280 (teacher forcing) -> (mel_outputs [B,80,S*r], linear [B,80,S*r],
+        attn_scores [B,S,Tx])"""
+        x, mel, semb = self._check(batch)
+        attn, hist = self._attend(*self._attend_inputs(x, mel, semb), keep_history=True)
+        mel_out, linear = self._mel_path(hist)
+        return mel_out, linear, attn
+
+    def _mel_path(self, hist: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """history [S,B,512] -> (mel_outputs, linear) [B,80,S*r]"""
+        S, B = hist.shape[:2]
+        r = self.r
+        dec = self.decoder
+        h = H.linear_fwd(hist, dec.rnn_input.weight, dec.rnn_input.bias)     # [S,B,L]  rnn_input([context, h_attn])
+        h = self._add(h, self._lstm(dec.res_rnn1, h))
+        h = self._add(h, self._lstm(dec.res_rnn2, h))
+        # mel_proj rows n * 20 + k (k < r) -- the [:, :, :r] slice of the [B, 80, 20] view -- in the order k * 80 + n,
+        # so that row (i, b) of the product is frames i*r .. i*r + r-1 of item b, channels last
+        n_mels, max_r = self.n_mels, Decoder.max_r
+        w_mel = self._pack(('mel_proj', r), dec.mel_proj.weight,
+                           lambda: H.bt_transpose(dec.mel_proj.weight.detach().reshape(n_mels, max_r, -1), True)[:r]
+                           .reshape(r * n_mels, -1))
+        y = H.linear_fwd(h, w_mel)                                              # [S,B,r*80]
+        mel_cl = H.bt_transpose(y, False).reshape(B, S * r, n_mels)             # [B,S*r,80], frame i*r + k
+        post = self.postnet(mel_cl, time_major_out=True)                        # [S*r,B,2*postnet_dims]
+        lin = H.linear_fwd(post, self.post_proj.weight, x_tm_B=B, y_tm_B=0)     # [B,S*r,80]
+        T = S * r
+        return H.transpose_pad_fwd(mel_cl, T, 0.0), H.transpose_pad_fwd(lin, T, 0.0)

@@ -21,7 +21,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#define FWDTACO_ABI_VERSION 4
+#define FWDTACO_ABI_VERSION 5
 
 #ifdef __cplusplus
 extern "C" {
@@ -429,6 +429,12 @@ int ft_lstm_fwd(const float* xp, const float* whh_f, const float* whh_r, const f
 int ft_lstm_bwd(const float* dout, const float* out_raw, const float* cstate, const float* gates,
                 const float* whhT_f, const float* whhT_r, const long* lens, float* dgates, float* carry, int B, int T,
                 int H, void* workspace, size_t workspace_bytes, void* stream);
+/* One direction (models/tacotron.py Decoder.res_rnn1 / res_rnn2 under teacher forcing: nn.LSTMCell over T steps from
+ * zero states): xp [T,B,4H] (x W_ih^T + b_ih, time-major), out_raw / cstate [T,B,H]; b_hh added here.  Same kernels as
+ * ft_lstm_fwd with the direction count 1: the persistent form where it fits (workspace: ft_rnn_workspace(4, B, H)),
+ * the per-step kernels otherwise. */
+int ft_lstm_fwd_uni(const float* xp, const float* whh, const float* bhh, float* out_raw, float* cstate, int B, int T,
+                    int H, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- a recurrent LAYER's forward with the input projection overlapped with the recurrence (no reference counterpart:
  * nn.LSTM / nn.GRU, forward_tacotron.py:96-99,147-152 / common_layers.py:89,123, run the projection in front).
  * x [B,T,in_f] batch-major; xp [T,B,2*G*H] (scratch for the projection, G = 4 | 3); the other arguments as in
@@ -569,6 +575,26 @@ int ft_dur_extract(const float* attn, int Tm, int Tx, const float* mel, int n_me
                    const long* x_len, const long* mel_len, const long* sil_ids, int n_sil, float silence_threshold,
                    float silence_prob_shift, int B, long* durations, int Tx_out, double* fstats, long* istats,
                    void* ws, void* stream);
+
+/* ---- Tacotron teacher-forced attention recurrence (models/tacotron.py:124-146 Decoder.forward, :65-99 LSA) -------- */
+/* All S decoder steps of attn_rnn (GRUCell 384 -> 256, gates r, z, n) + LSA (location conv 2 -> 32, k = 31, pad 15, no
+ * bias; L 32 -> 256; W 256 -> 256; v 256 -> 1; softmax over all Tx columns, no mask) + context = scores @ enc_pq, three
+ * launches per step on `stream` (csrc/ft_taco.hip).  Inputs: enc_proj / enc_pq [B,Tx,256]; P [S,B,768] = the prenet
+ * half of the GRU input projection, b_ih included; w_ih = attn_rnn.weight_ih [768, ld_w_ih] (its columns 0..255, the
+ * context's, are read); w_hh [768,256], b_hh [768]; W [256,256], b_W, conv_w [32,2,31], L [256,32], b_L, v [256].
+ * Output attn [B,S,Tx].  hist (optional, NULL to skip) [S,B,512]: row (s,b) = [context_s | h_attn_s], the rnn_input
+ * operand of the mel path.  Zero initial states; the LSA state lives in the workspace for the call only.  Weights,
+ * hist and ws 16-byte aligned.  1 <= Tx <= 1024, S >= 1; ws: ft_taco_attend_workspace(B, Tx) bytes (0: bad dims). */
+size_t ft_taco_attend_workspace(int B, int Tx);
+int ft_taco_attend(const float* enc_proj, const float* enc_pq, const float* P, const float* w_ih, long ld_w_ih,
+                   const float* w_hh, const float* b_hh, const float* W, const float* b_W, const float* conv_w,
+                   const float* L, const float* b_L, const float* v, float* attn, float* hist, int B, int Tx, int S,
+                   void* ws, size_t ws_bytes, void* stream);
+/* teacher-forced prenet inputs: out [S,B,n_mels] (time-major), out[0] = 0, out[i] = mel[:, :, i*r - 1] of mel
+ * [B,n_mels,Tm]; requires (S-1)*r <= Tm */
+int ft_taco_frames(const float* mel, int B, int n_mels, int Tm, int r, int S, float* out, void* stream);
+/* out = x + y over n floats (the decoder's residual adds) */
+int ft_taco_add(const float* x, const float* y, float* out, long n, void* stream);
 
 #ifdef __cplusplus
 }

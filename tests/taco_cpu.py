@@ -1,0 +1,167 @@
+"""Restatement of the Tacotron teacher-forced forward (forwardtacotron_amd/tacotron.py), written from the math with
+stock torch ops, for the tests (float64 on the host) and for the stock-ops comparison of tools/bench_align.py (fp32 on
+the device).  It reads a state_dict by name and runs on whatever device / dtype that state_dict's tensors have.
+
+Model (eval mode everywhere except, optionally, the decoder prenet's dropout, given as multiplier masks):
+  encoder   Embedding -> Linear 256 + ReLU -> Linear 128 + ReLU -> CBHG(K = encoder_k, 128 -> 128) -> [B,Tx,256]
+  CBHG      bank of K convolutions (width k = 1..K, padding k//2, first T outputs, ReLU, BatchNorm with running
+            statistics) -> max over (t-1, t) -> conv3 + ReLU + BN -> conv3 + BN -> + input -> bias-free Linear ->
+            highways (g = sigmoid(W2 x + b2), y = g relu(W1 x + b1) + (1 - g) x) -> bidirectional GRU
+  tokens    enc = [encoder | speaker_emb]; ep = enc Wp^T, eq = enc Wq^T (no bias)
+  step i    (S = ceil(steps / r); input frame mel[:, :, i*r - 1], zeros at i = 0)
+            p = drop2(relu(drop1(relu(f W1^T + b1)) W2^T + b2))
+            h = GRUCell([ctx, p], h)                              r, z, n gates; h' = (1-z) n + z h
+            loc = conv1d([cum, att], Wc, padding 15) -> [B,Tx,32]; e = v . tanh(W h + bW + ep + L loc + bL)
+            att = softmax_Tx(e); cum += att; ctx = att @ eq
+            x = Wi [ctx, h] + bi; x += LSTMCell1(x); x += LSTMCell2(x)
+            frames i*r + k, k < r: channel n = (Wm x)[n * 20 + k]
+  after     postnet CBHG(K = postnet_k, 80 -> postnet_dims, projections [256, 80]) -> Linear 2 * postnet_dims -> 80
+"""
+import math
+from typing import Dict, Optional
+
+import torch
+import torch.nn.functional as F
+
+BN_EPS = 1e-5
+MAX_R = 20
+
+
+def _bn(y, P, pre):
+    rm, rv = P[pre + 'running_mean'], P[pre + 'running_var']
+    scale = P[pre + 'weight'] / torch.sqrt(rv + BN_EPS)
+    return (y - rm[None, :, None]) * scale[None, :, None] + P[pre + 'bias'][None, :, None]
+
+
+def _bnconv(x, P, pre, relu):
+    w = P[pre + 'conv.weight']
+    y = F.conv1d(x, w, padding=w.shape[2] // 2)[:, :, :x.shape[2]]
+    if relu:
+        y = torch.relu(y)
+    return _bn(y, P, pre + 'bnorm.')
+
+
+def _gru_seq(x, w_ih, w_hh, b_ih, b_hh, reverse):
+    """x [B,T,I] -> [B,T,H], zero initial state"""
+    B, T, _ = x.shape
+    Hd = w_hh.shape[1]
+    gx = x @ w_ih.t() + b_ih
+    h = x.new_zeros(B, Hd)
+    out = [None] * T
+    for t in (range(T - 1, -1, -1) if reverse else range(T)):
+        h = _gru_cell(gx[:, t], h, w_hh, b_hh)
+        out[t] = h
+    return torch.stack(out, 1)
+
+
+def _gru_cell(gx, h, w_hh, b_hh):
+    Hd = h.shape[1]
+    gh = h @ w_hh.t() + b_hh
+    r = torch.sigmoid(gx[:, :Hd] + gh[:, :Hd])
+    z = torch.sigmoid(gx[:, Hd:2 * Hd] + gh[:, Hd:2 * Hd])
+    n = torch.tanh(gx[:, 2 * Hd:] + r * gh[:, 2 * Hd:])
+    return (1 - z) * n + z * h
+
+
+def _lstm_cell(x, h, c, P, pre):
+    g = x @ P[pre + 'weight_ih'].t() + P[pre + 'bias_ih'] + h @ P[pre + 'weight_hh'].t() + P[pre + 'bias_hh']
+    i, f, gg, o = g.chunk(4, dim=1)
+    c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
+    return torch.sigmoid(o) * torch.tanh(c), c
+
+
+def cbhg(x, P, pre, K, num_highways):
+    """x [B,C,T] -> [B,T,2*channels]"""
+    bank = torch.cat([_bnconv(x, P, f'{pre}conv1d_bank.{k}.', True) for k in range(K)], 1)
+    prev = torch.cat([torch.full_like(bank[:, :, :1], -math.inf), bank[:, :, :-1]], 2)
+    y = torch.maximum(bank, prev)
+    y = _bnconv(y, P, pre + 'conv_project1.', True)
+    y = _bnconv(y, P, pre + 'conv_project2.', False) + x
+    y = y.transpose(1, 2) @ P[pre + 'pre_highway.weight'].t()
+    for i in range(num_highways):
+        hp = f'{pre}highways.{i}.'
+        a = torch.relu(y @ P[hp + 'W1.weight'].t() + P[hp + 'W1.bias'])
+        g = torch.sigmoid(y @ P[hp + 'W2.weight'].t() + P[hp + 'W2.bias'])
+        y = g * a + (1 - g) * y
+    rp = pre + 'rnn.'
+    f = _gru_seq(y, P[rp + 'weight_ih_l0'], P[rp + 'weight_hh_l0'], P[rp + 'bias_ih_l0'], P[rp + 'bias_hh_l0'], False)
+    b = _gru_seq(y, P[rp + 'weight_ih_l0_reverse'], P[rp + 'weight_hh_l0_reverse'], P[rp + 'bias_ih_l0_reverse'],
+                 P[rp + 'bias_hh_l0_reverse'], True)
+    return torch.cat([f, b], 2)
+
+
+def forward(P: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: dict, r: int,
+            masks: Optional[Dict[str, torch.Tensor]] = None, with_mel: bool = True):
+    """-> (mel_outputs [B,80,S*r], linear [B,80,S*r], attn [B,S,Tx]); with_mel=False skips the LSTMs, mel_proj and
+    postnet (returns None, None, attn).  cfg: encoder_k, postnet_k, num_highways, speaker_emb_dim.  masks (optional):
+    multipliers (0 or 1/(1-p)) 'dec1' [S,B,256] and 'dec2' [S,B,128] of the decoder prenet's two dropout sites,
+    'enc1' [B,Tx,256] and 'enc2' [B,Tx,128] of the encoder prenet's."""
+    masks = masks or {}
+    dt = P['encoder.embedding.weight'].dtype
+    dev = P['encoder.embedding.weight'].device
+    x = batch['x'].to(dev)
+    mel = batch['mel'].to(device=dev, dtype=dt)
+    B, Tx = x.shape
+    steps = mel.shape[2]
+    S = math.ceil(steps / r)
+
+    y = P['encoder.embedding.weight'][x]
+    y = torch.relu(y @ P['encoder.pre_net.fc1.weight'].t() + P['encoder.pre_net.fc1.bias'])
+    if 'enc1' in masks:
+        y = y * masks['enc1'].to(dev, dt)
+    y = torch.relu(y @ P['encoder.pre_net.fc2.weight'].t() + P['encoder.pre_net.fc2.bias'])
+    if 'enc2' in masks:
+        y = y * masks['enc2'].to(dev, dt)
+    enc = cbhg(y.transpose(1, 2), P, 'encoder.cbhg.', cfg['encoder_k'], cfg['num_highways'])
+    if cfg.get('speaker_emb_dim', 0) > 0:
+        semb = batch['speaker_emb'].to(device=dev, dtype=dt)
+        enc = torch.cat([enc, semb[:, None, :].expand(B, Tx, semb.shape[1])], 2)
+    ep = enc @ P['encoder_proj.weight'].t()
+    eq = enc @ P['encoder_proj_query.weight'].t()
+
+    D = P['decoder.attn_rnn.weight_hh'].shape[1]
+    w_ih = P['decoder.attn_rnn.weight_ih']
+    b_ih = P['decoder.attn_rnn.bias_ih']
+    w_hh, b_hh = P['decoder.attn_rnn.weight_hh'], P['decoder.attn_rnn.bias_hh']
+    Wc = P['decoder.attn_net.conv.weight']
+    Lw, Lb = P['decoder.attn_net.L.weight'], P['decoder.attn_net.L.bias']
+    Ww, Wb = P['decoder.attn_net.W.weight'], P['decoder.attn_net.W.bias']
+    v = P['decoder.attn_net.v.weight'][0]
+    Ld = P['decoder.res_rnn1.weight_hh'].shape[1] if with_mel else 0
+    n_mels = mel.shape[1]
+
+    h = mel.new_zeros(B, D)
+    ctx = mel.new_zeros(B, D)
+    cum = mel.new_zeros(B, Tx)
+    att = mel.new_zeros(B, Tx)
+    h1 = c1 = h2 = c2 = mel.new_zeros(B, Ld)
+    attns, frames = [], []
+    for i in range(S):
+        f = mel[:, :, i * r - 1] if i > 0 else mel.new_zeros(B, n_mels)
+        p = torch.relu(f @ P['decoder.prenet.fc1.weight'].t() + P['decoder.prenet.fc1.bias'])
+        if 'dec1' in masks:
+            p = p * masks['dec1'][i].to(dev, dt)
+        p = torch.relu(p @ P['decoder.prenet.fc2.weight'].t() + P['decoder.prenet.fc2.bias'])
+        if 'dec2' in masks:
+            p = p * masks['dec2'][i].to(dev, dt)
+        h = _gru_cell(torch.cat([ctx, p], 1) @ w_ih.t() + b_ih, h, w_hh, b_hh)
+        loc = F.conv1d(torch.stack([cum, att], 1), Wc, padding=Wc.shape[2] // 2).transpose(1, 2)
+        e = torch.tanh((h @ Ww.t() + Wb)[:, None, :] + ep + loc @ Lw.t() + Lb) @ v
+        att = torch.softmax(e, dim=1)
+        cum = cum + att
+        ctx = (att[:, None, :] @ eq)[:, 0]
+        attns.append(att)
+        if with_mel:
+            xm = torch.cat([ctx, h], 1) @ P['decoder.rnn_input.weight'].t() + P['decoder.rnn_input.bias']
+            h1, c1 = _lstm_cell(xm, h1, c1, P, 'decoder.res_rnn1.')
+            xm = xm + h1
+            h2, c2 = _lstm_cell(xm, h2, c2, P, 'decoder.res_rnn2.')
+            xm = xm + h2
+            frames.append((xm @ P['decoder.mel_proj.weight'].t()).view(B, n_mels, MAX_R)[:, :, :r])
+    attn = torch.stack(attns, 1)
+    if not with_mel:
+        return None, None, attn
+    mel_out = torch.cat(frames, 2)
+    post = cbhg(mel_out, P, 'postnet.', cfg['postnet_k'], cfg['num_highways'])
+    linear = (post @ P['post_proj.weight'].t()).transpose(1, 2)
+    return mel_out, linear, attn
