@@ -447,3 +447,361 @@ int ft_taco_add(const float* x, const float* y, float* out, long n, void* stream
 }
 
 }  // extern "C"
+
+// =====================================================================================================================
+// Autoregressive generate (models/tacotron.py:283-349 Tacotron.generate, B = 1, eval mode).
+//
+// Step s reads the last frame step s-1 produced, so the prenet, the decoder LSTMs and mel_proj move inside the
+// recurrence.  Each step is a fixed chain of eight launches; ft_taco_gen_steps enqueues every one from C:
+//
+//   1. ft_taco_gen_prenet_kernel  grid 24, 1024 threads: frame s*r - 1 (zeros at s = 0) -> fc1 + ReLU (four threads
+//        per row) -> fc2 + ReLU (wave per row) -> P[s] = W_ih[:, 256:] p + b_ih, 32 of the 768 rows per workgroup
+//        (each workgroup recomputes the 80 -> 256 -> 128 prenet: L2 reads instead of two more launches).
+//   2-4. ft_taco_gru_kernel, ft_taco_energy_kernel, ft_taco_context_kernel, unchanged (B = 1, AttendArgs.S = S):
+//        hist[s] = [context | h_attn], attn[0, s, :].
+//   5. ft_taco_gen_rnnin_kernel   grid ceil(L/4): xin = Wi hist[s] + bi, one wave per output row.
+//   6, 7. ft_taco_gen_lstm_kernel grid ceil(L/4): one LSTMCell step per wave and hidden unit (its 4 gate rows of W_ih
+//        and W_hh, gate order i, f, g, o), then the residual add x + h'.  h and c ping-pong on the parity of s.
+//   8. ft_taco_gen_mel_kernel     grid ceil(80 r/4): mel_proj rows n*20 + k (k < r, the [:, :, :r] slice), one wave
+//        per row -> frames[s*r + k][n] (channels last); the stop test (every value < stop_threshold, s*r > 10) is an
+//        OR of per-workgroup "not below" flags, read by the last workgroup to finish (a ticket counter: the atomics
+//        count and flag, they never carry values), which records S_out = s + 1 the first time the test holds.
+//
+// Dot products run one wave per row: each lane accumulates k = 4 lane + 256 c .. +3 in ascending c, then a fixed xor
+// butterfly sums the 64 lanes (every lane ends with the same bits).  At lstm_dims = 512 the chunk count is a template
+// constant and every load of a wave is issued before its first FMA; other sizes take the same order in a loop.
+// Steps past the stop still run when they were already enqueued; they write slots past S_out only.
+namespace {
+
+constexpr int GNM = 80;          // n_mels (the reference runs with no other value)
+constexpr int GF1 = 256;         // prenet fc1
+constexpr int GF2 = 128;         // prenet fc2
+constexpr int GMAXR = 20;        // Decoder.max_r
+constexpr int GPB = 24;          // prenet workgroups (NG / GPB rows of P each)
+
+struct GenArgs {
+  const float *fc1w, *fc1b, *fc2w, *fc2b;     // [256,80] [256] [128,256] [128]
+  const float* wih;                           // attn_rnn.weight_ih [768, ld_wih]: prenet columns 256..383
+  long ld_wih;
+  const float* bih;                           // [768]
+  const float *wi, *bi;                       // rnn_input [L,512] [L]
+  const float *l1ih, *l1hh, *l1bih, *l1bhh;   // res_rnn1 [4L,L] [4L,L] [4L] [4L]
+  const float *l2ih, *l2hh, *l2bih, *l2bhh;   // res_rnn2
+  const float* wmel;                          // mel_proj [1600, L]
+  float thr;
+  float* P;         // [S,768]
+  float* hist;      // [S,512]
+  float* frames;    // [S*r,80]
+  int* sout;
+  float *xin, *x1, *x2;         // [L]
+  float *h1, *c1, *h2, *c2;     // [2][L]
+  unsigned *flag, *ticket;
+  int L, r, S;
+};
+
+__device__ __forceinline__ float wave_allsum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float fma4(const float4& a, const float4& b, float acc) {
+  acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc);
+  return fmaf(a.w, b.w, acc);
+}
+
+// NR dot products of length K, one wave: out[i] = w[i] . v[i], the same bits in every lane.  KC > 0: K == 256 KC.
+template <int NR, int KC>
+__device__ __forceinline__ void wave_dots(const float* const (&w)[NR], const float* const (&v)[NR], int K,
+                                          float (&out)[NR]) {
+  const int lane = threadIdx.x & 63;
+  float acc[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) acc[i] = 0.f;
+  if constexpr (KC > 0) {
+    float4 a[NR][KC], b[NR][KC];
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        a[i][c] = ld4(w[i] + 256 * c + 4 * lane);
+        b[i][c] = ld4(v[i] + 256 * c + 4 * lane);
+      }
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) acc[i] = fma4(a[i][c], b[i][c], acc[i]);
+  } else if ((K & 3) == 0) {
+    for (int k = 4 * lane; k < K; k += 256) {
+      float4 a[NR], b[NR];
+#pragma unroll
+      for (int i = 0; i < NR; ++i) { a[i] = ld4(w[i] + k); b[i] = ld4(v[i] + k); }
+#pragma unroll
+      for (int i = 0; i < NR; ++i) acc[i] = fma4(a[i], b[i], acc[i]);
+    }
+  } else {
+    for (int k0 = 4 * lane; k0 < K; k0 += 256)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int k = k0 + e;
+        if (k < K) {
+#pragma unroll
+          for (int i = 0; i < NR; ++i) acc[i] = fmaf(w[i][k], v[i][k], acc[i]);
+        }
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < NR; ++i) out[i] = wave_allsum(acc[i]);
+}
+
+// ---- 1. decoder prenet + prenet half of the GRU input projection ----------------------------------------------------
+// 16 waves.  Every weight the workgroup reads (a quarter row of fc1 per thread, 8 fc2 rows per wave, 2 rows of
+// W_ih[:, 256:] per wave) is requested with the frame, so the three dependent products cost one memory round trip.
+__global__ __launch_bounds__(1024) void ft_taco_gen_prenet_kernel(GenArgs g, int s) {
+  constexpr int RPB = NG / GPB;                 // P rows per workgroup
+  constexpr int RPW = RPB / 16;                 // per wave
+  constexpr int R2 = GF2 / 16;                  // fc2 rows per wave
+  constexpr int KQ = GNM / 4;                   // fc1 K quarter
+  static_assert(RPW * 16 == RPB && R2 * 16 == GF2 && GF2 == 128 && GF1 == 256 && KQ % 4 == 0, "prenet shape");
+  __shared__ __attribute__((aligned(16))) float f[GNM];
+  __shared__ float part[4][GF1];
+  __shared__ __attribute__((aligned(16))) float p1[GF1];
+  __shared__ __attribute__((aligned(16))) float p2[GF2];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (s == 0 && blockIdx.x == 0 && tid == 0) *g.sout = g.S;
+  const int row1 = tid & (GF1 - 1), q1 = tid >> 8;
+  float4 w1[KQ / 4];
+#pragma unroll
+  for (int c = 0; c < KQ / 4; ++c) w1[c] = ld4(g.fc1w + (long)row1 * GNM + KQ * q1 + 4 * c);
+  float4 w2[R2];
+#pragma unroll
+  for (int i = 0; i < R2; ++i) w2[i] = ld4(g.fc2w + (long)(wave * R2 + i) * GF1 + 4 * lane);
+  const int r3 = blockIdx.x * RPB + wave * RPW;
+  float4 w3[RPW];
+#pragma unroll
+  for (int i = 0; i < RPW; ++i)
+    w3[i] = lane < GF2 / 4 ? ld4(g.wih + (long)(r3 + i) * g.ld_wih + DA + 4 * lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float b1 = g.fc1b[row1];
+  const float b2 = lane < R2 ? g.fc2b[wave * R2 + lane] : 0.f;
+  const float b3 = lane < RPW ? g.bih[r3 + lane] : 0.f;
+  if (tid < GNM) f[tid] = s > 0 ? g.frames[((long)s * g.r - 1) * GNM + tid] : 0.f;
+  __syncthreads();
+  {
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < KQ / 4; ++c) acc = fma4(w1[c], ld4(f + KQ * q1 + 4 * c), acc);
+    part[q1][row1] = acc;
+  }
+  __syncthreads();
+  if (tid < GF1) p1[tid] = fmaxf(((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid] + b1, 0.f);
+  __syncthreads();
+  {
+    const float4 v = ld4(p1 + 4 * lane);
+    float o = 0.f;
+#pragma unroll
+    for (int i = 0; i < R2; ++i) {
+      const float d = wave_allsum(fma4(w2[i], v, 0.f));
+      o = lane == i ? d : o;
+    }
+    if (lane < R2) p2[wave * R2 + lane] = fmaxf(o + b2, 0.f);
+  }
+  __syncthreads();
+  {
+    const float4 v = lane < GF2 / 4 ? ld4(p2 + 4 * lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float o = 0.f;
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+      const float d = wave_allsum(fma4(w3[i], v, 0.f));
+      o = lane == i ? d : o;
+    }
+    if (lane < RPW) g.P[(long)s * NG + r3 + lane] = o + b3;
+  }
+}
+
+// ---- 5. rnn_input ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ft_taco_gen_rnnin_kernel(GenArgs g, int s) {
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= g.L) return;
+  const float* w[1] = {g.wi + (long)j * 2 * DA};
+  const float* v[1] = {g.hist + (long)s * 2 * DA};
+  float o[1];
+  wave_dots<1, 2>(w, v, 2 * DA, o);
+  if ((threadIdx.x & 63) == 0) g.xin[j] = o[0] + g.bi[j];
+}
+
+// ---- 6, 7. residual LSTMCell ----------------------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(256) void ft_taco_gen_lstm_kernel(GenArgs g, int s, int layer) {
+  const int L = g.L;
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= L) return;
+  const float *wih = layer ? g.l2ih : g.l1ih, *whh = layer ? g.l2hh : g.l1hh;
+  const float *bih = layer ? g.l2bih : g.l1bih, *bhh = layer ? g.l2bhh : g.l1bhh;
+  const float* x = layer ? g.x1 : g.xin;
+  float* xo = layer ? g.x2 : g.x1;
+  float* hb = layer ? g.h2 : g.h1;
+  float* cb = layer ? g.c2 : g.c1;
+  const float* hp = hb + (long)(s & 1) * L;
+  const float* w[8];
+  const float* v[8];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    w[q] = wih + (long)(q * L + j) * L; v[q] = x;
+    w[4 + q] = whh + (long)(q * L + j) * L; v[4 + q] = hp;
+  }
+  // cell operands, requested with the dot-product operands
+  float bi_[4], bh_[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { bi_[q] = bih[q * L + j]; bh_[q] = bhh[q * L + j]; }
+  const float cprev = cb[(long)(s & 1) * L + j], xj = x[j];
+  float o[8];
+  wave_dots<8, KC>(w, v, L, o);
+  if ((threadIdx.x & 63) == 0) {
+    float gt[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) gt[q] = ((o[q] + bi_[q]) + o[4 + q]) + bh_[q];
+    const float c = ft_sigmoid(gt[1]) * cprev + ft_sigmoid(gt[0]) * ft_tanh(gt[2]);
+    const float h = ft_sigmoid(gt[3]) * ft_tanh(c);
+    hb[(long)((s + 1) & 1) * L + j] = h;
+    cb[(long)((s + 1) & 1) * L + j] = c;
+    xo[j] = xj + h;
+  }
+}
+
+// ---- 8. mel_proj + stop test ----------------------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(256) void ft_taco_gen_mel_kernel(GenArgs g, int s) {
+  __shared__ int above[4];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int i = blockIdx.x * 4 + wave;             // output row: frame k = i / 80, channel n = i % 80
+  int notbelow = 0;
+  if (i < GNM * g.r) {
+    const int k = i / GNM, n = i - k * GNM;
+    const float* w[1] = {g.wmel + (long)(n * GMAXR + k) * g.L};
+    const float* v[1] = {g.x2};
+    float o[1];
+    wave_dots<1, KC>(w, v, g.L, o);
+    if ((tid & 63) == 0) g.frames[((long)s * g.r + k) * GNM + n] = o[0];
+    notbelow = !(o[0] < g.thr);                    // NaN is never below
+  }
+  if ((tid & 63) == 0) above[wave] = notbelow;
+  __syncthreads();
+  if (tid == 0) {
+    if (above[0] | above[1] | above[2] | above[3]) atomicOr(g.flag, 1u);
+    __threadfence();
+    if (atomicAdd(g.ticket, 1u) == gridDim.x - 1) {          // last workgroup of the step
+      const unsigned nb = atomicOr(g.flag, 0u);
+      if (!nb && (long)s * g.r > 10 && *g.sout > s) *g.sout = s + 1;
+      atomicExch(g.flag, 0u);
+      atomicExch(g.ticket, 0u);
+    }
+  }
+}
+
+struct GenWs {
+  WsLayout at;
+  size_t xin, x1, x2, h1, c1, h2, c2, flag, total;
+};
+GenWs gen_layout(int Tx, int L) {
+  GenWs w;
+  w.at = ws_layout(1, Tx);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t v = sizeof(float) * (size_t)L;
+  size_t o = w.at.total;
+  w.xin = o; o = al(o + v);
+  w.x1 = o;  o = al(o + v);
+  w.x2 = o;  o = al(o + v);
+  w.h1 = o;  o = al(o + 2 * v);
+  w.c1 = o;  o = al(o + 2 * v);
+  w.h2 = o;  o = al(o + 2 * v);
+  w.c2 = o;  o = al(o + 2 * v);
+  w.flag = o; o = al(o + 2 * sizeof(unsigned));
+  w.total = o;
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ft_taco_gen_workspace(int Tx, int lstm_dims, int r) {
+  if (Tx < 1 || Tx > TXMAX || lstm_dims < 1 || r < 1 || r > GMAXR) return 0;
+  return gen_layout(Tx, lstm_dims).total;
+}
+
+int ft_taco_gen_steps(const float* enc_proj, const float* enc_pq, const float* fc1_w, const float* fc1_b,
+                      const float* fc2_w, const float* fc2_b, const float* w_ih, long ld_w_ih, const float* b_ih,
+                      const float* w_hh, const float* b_hh, const float* W, const float* b_W, const float* conv_w,
+                      const float* L, const float* b_L, const float* v, const float* rnn_in_w, const float* rnn_in_b,
+                      const float* r1_w_ih, const float* r1_w_hh, const float* r1_b_ih, const float* r1_b_hh,
+                      const float* r2_w_ih, const float* r2_w_hh, const float* r2_b_ih, const float* r2_b_hh,
+                      const float* mel_w, float stop_threshold, float* P, float* hist, float* attn, float* frames,
+                      int* s_out, int Tx, int lstm_dims, int r, int S, int s0, int n, void* ws, size_t ws_bytes,
+                      void* stream) {
+  FT_REQUIRE(Tx >= 1 && Tx <= TXMAX, "taco_gen_steps: Tx must be in 1..%d (got %d)", TXMAX, Tx);
+  FT_REQUIRE(lstm_dims >= 1, "taco_gen_steps: lstm_dims must be >= 1 (got %d)", lstm_dims);
+  FT_REQUIRE(r >= 1 && r <= GMAXR, "taco_gen_steps: r must be in 1..%d (got %d)", GMAXR, r);
+  FT_REQUIRE(S >= 1 && s0 >= 0 && n >= 0 && (long)s0 + n <= S,
+             "taco_gen_steps: steps [%d, %d) must lie in [0, S = %d)", s0, s0 + n, S);
+  FT_REQUIRE(ld_w_ih >= DA + GF2 && ld_w_ih % 4 == 0, "taco_gen_steps: ld_w_ih must be a multiple of 4, >= 384");
+  FT_REQUIRE(enc_proj && enc_pq && fc1_w && fc1_b && fc2_w && fc2_b && w_ih && b_ih && w_hh && b_hh && W && b_W &&
+             conv_w && L && b_L && v && rnn_in_w && rnn_in_b && r1_w_ih && r1_w_hh && r1_b_ih && r1_b_hh && r2_w_ih &&
+             r2_w_hh && r2_b_ih && r2_b_hh && mel_w && P && hist && attn && frames && s_out,
+             "taco_gen_steps: null operand");
+  const bool v4 = lstm_dims % 4 == 0;
+  FT_REQUIRE(al16(fc1_w) && al16(fc2_w) && al16(w_ih) && al16(w_hh) && al16(W) && al16(L) && al16(rnn_in_w) &&
+             al16(hist) && al16(ws) && (!v4 || (al16(r1_w_ih) && al16(r1_w_hh) && al16(r2_w_ih) && al16(r2_w_hh) &&
+                                                al16(mel_w))),
+             "taco_gen_steps: weights, history and workspace must be 16-byte aligned");
+  const GenWs wl = gen_layout(Tx, lstm_dims);
+  FT_REQUIRE(ws && ws_bytes >= wl.total, "taco_gen_steps: workspace too small (%zu < %zu bytes)", ws_bytes, wl.total);
+  if (n == 0) return FT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)ws;
+  AttendArgs a;
+  a.enc_proj = enc_proj; a.enc_pq = enc_pq; a.P = P; a.wih = w_ih; a.ld_wih = ld_w_ih; a.whh = w_hh; a.bhh = b_hh;
+  a.W = W; a.bW = b_W; a.cw = conv_w; a.L = L; a.bL = b_L; a.v = v; a.attn = attn;
+  a.qp = (float*)(w + wl.at.qp); a.E = (float*)(w + wl.at.E); a.cum = (float*)(w + wl.at.cum);
+  a.att = (float*)(w + wl.at.att);
+  a.B = 1; a.Tx = Tx; a.S = S;
+  a.ldh = 2 * DA;
+  GenArgs g;
+  g.fc1w = fc1_w; g.fc1b = fc1_b; g.fc2w = fc2_w; g.fc2b = fc2_b; g.wih = w_ih; g.ld_wih = ld_w_ih; g.bih = b_ih;
+  g.wi = rnn_in_w; g.bi = rnn_in_b;
+  g.l1ih = r1_w_ih; g.l1hh = r1_w_hh; g.l1bih = r1_b_ih; g.l1bhh = r1_b_hh;
+  g.l2ih = r2_w_ih; g.l2hh = r2_w_hh; g.l2bih = r2_b_ih; g.l2bhh = r2_b_hh;
+  g.wmel = mel_w; g.thr = stop_threshold;
+  g.P = P; g.hist = hist; g.frames = frames; g.sout = s_out;
+  g.xin = (float*)(w + wl.xin); g.x1 = (float*)(w + wl.x1); g.x2 = (float*)(w + wl.x2);
+  g.h1 = (float*)(w + wl.h1); g.c1 = (float*)(w + wl.c1); g.h2 = (float*)(w + wl.h2); g.c2 = (float*)(w + wl.c2);
+  g.flag = (unsigned*)(w + wl.flag); g.ticket = g.flag + 1;
+  g.L = lstm_dims; g.r = r; g.S = S;
+  // s0 == 0: LSA state, LSTM states, stop flag and ticket from zero (S_out := S by the first prenet launch); the GRU
+  // kernel takes h = context = 0 at s = 0 itself
+  if (s0 == 0) (void)hipMemsetAsync(w + wl.at.cum, 0, wl.total - wl.at.cum, st);
+  const dim3 g1(NUB, 1), g2(ft_cdiv(Tx, TC), 1, NCQ), g3(NAC, 1);
+  const dim3 gl(ft_cdiv(lstm_dims, 4)), gm(ft_cdiv(GNM * r, 4));
+  const bool fast = lstm_dims == 512;
+  for (int s = s0; s < s0 + n; ++s) {
+    const float* prev = hist + (long)(s > 0 ? s - 1 : 0) * 2 * DA;
+    float* cur = hist + (long)s * 2 * DA;
+    hipLaunchKernelGGL(ft_taco_gen_prenet_kernel, dim3(GPB), dim3(1024), 0, st, g, s);
+    hipLaunchKernelGGL(ft_taco_gru_kernel, g1, dim3(256), 0, st, a, s, prev + DA, prev, cur + DA);
+    hipLaunchKernelGGL(ft_taco_energy_kernel, g2, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(ft_taco_context_kernel, g3, dim3(256), 0, st, a, s, cur);
+    hipLaunchKernelGGL(ft_taco_gen_rnnin_kernel, gl, dim3(256), 0, st, g, s);
+    if (fast) {
+      hipLaunchKernelGGL(ft_taco_gen_lstm_kernel<2>, gl, dim3(256), 0, st, g, s, 0);
+      hipLaunchKernelGGL(ft_taco_gen_lstm_kernel<2>, gl, dim3(256), 0, st, g, s, 1);
+      hipLaunchKernelGGL(ft_taco_gen_mel_kernel<2>, gm, dim3(256), 0, st, g, s);
+    } else {
+      hipLaunchKernelGGL(ft_taco_gen_lstm_kernel<0>, gl, dim3(256), 0, st, g, s, 0);
+      hipLaunchKernelGGL(ft_taco_gen_lstm_kernel<0>, gl, dim3(256), 0, st, g, s, 1);
+      hipLaunchKernelGGL(ft_taco_gen_mel_kernel<0>, gm, dim3(256), 0, st, g, s);
+    }
+  }
+  return ft_check_launch("taco_gen_steps");
+}
+
+}  // extern "C"

@@ -5,7 +5,7 @@ seed-identical initialisation; the teacher-forced forward() and align() run on t
     reference (models/tacotron.py)                 here
     Tacotron.forward(batch), teacher forcing        Tacotron.forward(batch): inference only (no grad, no training mode)
     -- (train_tacotron.py:117-136 runs forward)     Tacotron.align(batch): encoder + attention recurrence only
-    Tacotron.generate                               not implemented (raises FtError)
+    Tacotron.generate(x, speaker_emb, steps)        Tacotron.generate: B = 1, eval mode, numpy outputs as the reference
 
 Under teacher forcing the attention recurrence (attn_rnn GRUCell + LSA + context) is closed over
 {h_attn, context, cumulative, attention}; nothing from the decoder LSTMs feeds back into it.  So:
@@ -17,6 +17,12 @@ Under teacher forcing the attention recurrence (attn_rnn GRUCell + LSA + context
   4. forward() only: rnn_input on the history, then each residual LSTMCell as one-direction LSTM recurrence
      (ft_lstm_fwd_uni) behind one input-projection GEMM, the residual adds, mel_proj restricted to the 80 * r rows
      the [:, :, :r] slice keeps, the postnet CBHG and post_proj.
+
+generate() feeds each step's last frame back into the next step's prenet, so the prenet, rnn_input, both LSTMCells and
+mel_proj run inside the recurrence: ft_taco_gen_steps enqueues eight launches per decoder step (the prenet and its GRU
+input projection, ft_taco_attend's three kernels, rnn_input, res_rnn1, res_rnn2, mel_proj with the stop test) for
+GEN_CHUNK steps per call; the host reads the stop step S_out back once per chunk, then runs the postnet on the
+S_out * r frames.
 
 Dropout: the encoder PreNet and the decoder PreNet apply dropout 0.5 when their own `training` flag is set (extraction
 mode, train_tacotron.py:118-119, is `model.eval(); model.decoder.prenet.train()`); every other module must be in eval
@@ -42,6 +48,7 @@ from .model import CBHG
 
 NUM_CHARS_DEFAULT = 135      # len(utils.text.symbols.phonemes)
 MAX_TX = 1024                # ft_taco_attend's token bound (the duration kernel's)
+GEN_CHUNK = 32               # decoder steps per ft_taco_gen_steps call in generate (outputs do not depend on it)
 
 FtError = _lib.FtError
 
@@ -178,9 +185,91 @@ class Tacotron(nn.Module):
         model.load_state_dict(checkpoint['model'])
         return model
 
-    def generate(self, *args, **kwargs):
-        raise FtError('Tacotron.generate (autoregressive synthesis with a stop threshold) is not implemented here: '
-                      'this Tacotron runs the teacher-forced forward() and align() only')
+    def generate(self, x: torch.Tensor, speaker_emb: torch.Tensor = None, steps=2000) -> Tuple[Any, Any, Any]:
+        """models/tacotron.py:283-349 at B = 1 -> numpy (mel_outputs [80, S_out*r], linear [80, S_out*r],
+        attn_scores [S_out, Tx]).  Runs under torch.no_grad(); eval() on entry and train() on return, as the reference.
+        The decoder steps run in chunks of GEN_CHUNK (ft_taco_gen_steps), S_out is read back once per chunk."""
+        w = self.encoder.embedding.weight
+        if not w.is_cuda:
+            raise FtError('Tacotron.generate runs on an MI355X (HIP) device only: move the model with .cuda()')
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] != 1:
+            raise FtError(f'Tacotron.generate: x must be [1, Tx] (batch size 1, as the reference), got '
+                          f'{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}')
+        if not 1 <= x.shape[1] <= MAX_TX:
+            raise FtError(f'Tacotron.generate: Tx must be in 1..{MAX_TX} (got {x.shape[1]})')
+        steps = int(steps)
+        if steps < 1:
+            raise FtError(f'Tacotron.generate: steps must be >= 1 (got {steps})')
+        if self.speaker_emb_dim > 0 and speaker_emb is not None and tuple(speaker_emb.shape) != (1, self.speaker_emb_dim):
+            raise FtError(f'Tacotron.generate: speaker_emb must be [1, {self.speaker_emb_dim}], got '
+                          f'{tuple(speaker_emb.shape)}')
+        r = self.r
+        if not 1 <= r <= Decoder.max_r:
+            raise FtError(f'Tacotron.generate: r must be in 1..{Decoder.max_r} (got {r})')
+        self.eval()
+        try:
+            with torch.no_grad():
+                if speaker_emb is None and self.speaker_emb_dim > 0:
+                    speaker_emb = torch.rand((1, self.speaker_emb_dim))           # the reference's draw
+                return self._generate(x.to(w.device, torch.int64).contiguous(), speaker_emb, steps, r)
+        finally:
+            self.train()
+
+    def _generate(self, x: torch.Tensor, semb, steps: int, r: int):
+        dev = x.device
+        Tx = x.shape[1]
+        S = math.ceil(steps / r)
+        D, Ld, n_mels = self.decoder_dims, self.lstm_dims, self.n_mels
+        dec = self.decoder
+        enc = self.encoder(x)                                                   # [1,Tx,256]
+        if self.speaker_emb_dim > 0:
+            semb = semb.to(device=dev, dtype=torch.float32).contiguous()
+            enc = H.concat_cols(enc, None, semb, 1, Tx)
+        ep = H.linear_fwd(enc, self.encoder_proj.weight)
+        epq = H.linear_fwd(enc, self.encoder_proj_query.weight)
+        f32 = dict(device=dev, dtype=torch.float32)
+        P = torch.empty(S, 3 * D, **f32)
+        hist = torch.empty(S, 2 * D, **f32)
+        attn = torch.empty(1, S, Tx, **f32)
+        frames = torch.empty(1, S * r, n_mels, **f32)
+        s_out = torch.empty(1, device=dev, dtype=torch.int32)
+        nbytes = _lib.query('ft_taco_gen_workspace', Tx, Ld, r)
+        if nbytes == 0:
+            raise FtError(f'Tacotron.generate: no workspace for Tx = {Tx}, lstm_dims = {Ld}, r = {r}')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        gru, lsa, pn = dec.attn_rnn, dec.attn_net, dec.prenet
+        l1, l2 = dec.res_rnn1, dec.res_rnn2
+        ops = (_p(ep), _p(epq), _p(pn.fc1.weight), _p(pn.fc1.bias), _p(pn.fc2.weight), _p(pn.fc2.bias),
+               _p(gru.weight_ih), gru.weight_ih.shape[1], _p(gru.bias_ih), _p(gru.weight_hh), _p(gru.bias_hh),
+               _p(lsa.W.weight), _p(lsa.W.bias), _p(lsa.conv.weight), _p(lsa.L.weight), _p(lsa.L.bias),
+               _p(lsa.v.weight), _p(dec.rnn_input.weight), _p(dec.rnn_input.bias),
+               _p(l1.weight_ih), _p(l1.weight_hh), _p(l1.bias_ih), _p(l1.bias_hh),
+               _p(l2.weight_ih), _p(l2.weight_hh), _p(l2.bias_ih), _p(l2.bias_hh), _p(dec.mel_proj.weight),
+               float(self.stop_threshold), _p(P), _p(hist), _p(attn), _p(frames), _p(s_out), Tx, Ld, r, S)
+        # chunk c is enqueued before chunk c-1's S_out is waited for: at most one host wait per chunk
+        host = torch.empty(2, dtype=torch.int32, pin_memory=True)
+        events = [torch.cuda.Event(), torch.cuda.Event()]
+        s0, c, n_out = 0, 0, S
+        while s0 < S:
+            n = min(GEN_CHUNK, S - s0)
+            _lib.call('ft_taco_gen_steps', *ops, s0, n, _p(ws), ws.numel(), _stream())
+            host[c % 2:c % 2 + 1].copy_(s_out, non_blocking=True)
+            events[c % 2].record()
+            s0 += n
+            if c > 0:
+                events[(c - 1) % 2].synchronize()
+                n_out = int(host[(c - 1) % 2])
+                if n_out < S:
+                    break
+            c += 1
+        else:
+            events[(c - 1) % 2].synchronize()
+            n_out = int(host[(c - 1) % 2])
+        self._gen_steps_run = s0                                                # for tools/bench_taco_generate.py
+        T = n_out * r
+        mel_cl = frames[:, :T]
+        mel_out, lin = self._post(mel_cl)
+        return mel_out[0].cpu().numpy(), lin[0].cpu().numpy(), attn[0, :n_out].cpu().numpy()
 
     # ------------------------------------------------------------------------------------------------------------------
     def _check(self, batch) -> Tuple[torch.Tensor, torch.Tensor, Any]:
@@ -312,7 +401,11 @@ class Tacotron(nn.Module):
                            .reshape(r * n_mels, -1))
         y = H.linear_fwd(h, w_mel)                                              # [S,B,r*80]
         mel_cl = H.bt_transpose(y, False).reshape(B, S * r, n_mels)             # [B,S*r,80], frame i*r + k
-        post = self.postnet(mel_cl, time_major_out=True)                        # [S*r,B,2*postnet_dims]
-        lin = H.linear_fwd(post, self.post_proj.weight, x_tm_B=B, y_tm_B=0)     # [B,S*r,80]
-        T = S * r
+        return self._post(mel_cl)
+
+    def _post(self, mel_cl: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """frames [B,T,80] (channels last) -> (mel_outputs, linear) [B,80,T]: the postnet CBHG and post_proj"""
+        B, T = mel_cl.shape[:2]
+        post = self.postnet(mel_cl, time_major_out=True)                        # [T,B,2*postnet_dims]
+        lin = H.linear_fwd(post, self.post_proj.weight, x_tm_B=B, y_tm_B=0)     # [B,T,80]
         return H.transpose_pad_fwd(mel_cl, T, 0.0), H.transpose_pad_fwd(lin, T, 0.0)

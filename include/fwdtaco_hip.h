@@ -21,7 +21,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#define FWDTACO_ABI_VERSION 5
+#define FWDTACO_ABI_VERSION 6
 
 #ifdef __cplusplus
 extern "C" {
@@ -595,6 +595,34 @@ int ft_taco_attend(const float* enc_proj, const float* enc_pq, const float* P, c
 int ft_taco_frames(const float* mel, int B, int n_mels, int Tm, int r, int S, float* out, void* stream);
 /* out = x + y over n floats (the decoder's residual adds) */
 int ft_taco_add(const float* x, const float* y, float* out, long n, void* stream);
+
+/* ---- Tacotron autoregressive generate (models/tacotron.py:283-349 Tacotron.generate, :124-174 Decoder.forward) --- */
+/* Decoder steps [s0, s0 + n) of generate at B = 1 in eval mode (no dropout, no zoneout), eight launches per step on
+ * `stream` (csrc/ft_taco.hip), all enqueued here: decoder prenet (fc1 80 -> 256, fc2 256 -> 128, ReLU) of the last
+ * frame of step s-1 (zeros at s = 0) and the prenet half of the GRU input projection -> P[s]; the attention GRU, LSA
+ * and context (ft_taco_attend's kernels); rnn_input; res_rnn1 and res_rnn2 (nn.LSTMCell, gates i, f, g, o, each plus
+ * its input); mel_proj rows n*20 + k, k < r (the [:, :, :r] slice).  s0 == 0 starts from zero states and sets
+ * *s_out = S; a later call continues from the workspace, which must not be touched in between.  Stop rule (:336): the
+ * first step s whose 80 r frames are all < stop_threshold (fp32, NaN never is) with s*r > 10 sets *s_out = s + 1;
+ * steps after it still run but only write slots >= *s_out.
+ * Inputs: enc_proj / enc_pq [1,Tx,256]; fc1_w [256,80], fc1_b, fc2_w [128,256], fc2_b; w_ih = attn_rnn.weight_ih
+ * [768, ld_w_ih] (context columns 0..255, prenet columns 256..383), b_ih, w_hh [768,256], b_hh; the LSA weights as
+ * ft_taco_attend; rnn_in_w [L,512], rnn_in_b [L]; r*_w_ih / r*_w_hh [4L,L], r*_b_ih / r*_b_hh [4L]; mel_w [1600,L]
+ * (L = lstm_dims).  Outputs, slots for all S = ceil(steps / r) steps: P [S,768]; hist [S,512] = [context | h_attn];
+ * attn [1,S,Tx]; frames [S*r,80] (channels last, frame s*r + k); s_out one device int.  Weights, hist and ws 16-byte
+ * aligned.  1 <= Tx <= 1024, 1 <= r <= 20, 0 <= s0, s0 + n <= S; ws: ft_taco_gen_workspace(Tx, lstm_dims, r) bytes
+ * (0: bad dims).  Fixed summation order, no atomics on values: one input gives one output bit pattern, whatever the
+ * split into calls. */
+size_t ft_taco_gen_workspace(int Tx, int lstm_dims, int r);
+int ft_taco_gen_steps(const float* enc_proj, const float* enc_pq, const float* fc1_w, const float* fc1_b,
+                      const float* fc2_w, const float* fc2_b, const float* w_ih, long ld_w_ih, const float* b_ih,
+                      const float* w_hh, const float* b_hh, const float* W, const float* b_W, const float* conv_w,
+                      const float* L, const float* b_L, const float* v, const float* rnn_in_w, const float* rnn_in_b,
+                      const float* r1_w_ih, const float* r1_w_hh, const float* r1_b_ih, const float* r1_b_hh,
+                      const float* r2_w_ih, const float* r2_w_hh, const float* r2_b_ih, const float* r2_b_hh,
+                      const float* mel_w, float stop_threshold, float* P, float* hist, float* attn, float* frames,
+                      int* s_out, int Tx, int lstm_dims, int r, int S, int s0, int n, void* ws, size_t ws_bytes,
+                      void* stream);
 
 #ifdef __cplusplus
 }
