@@ -2,6 +2,7 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    (+ DIR/<name>.npy: what the last timed step computed)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                (+ the measurements that take runs of their own)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,16 +11,20 @@ when N > 1) on the LJSpeech-shaped synthetic batch of SURVEY.md section 8d (bs=3
 Tm=841, 19,320 valid frames on rank 0's seed), singlespeaker.yaml model, fp32, dropout at config values,
 inputs resident in HBM before the timed region.  Weak scaling: every rank draws its own bs=32 batch.
 
-Rank 0 prints ONE JSON line (driver contract) with two extra objects:
+Rank 0 prints ONE JSON line (driver contract).  A plain run does only what that line needs: set-up, W warm-up steps,
+K timed steps, --dump-outputs, the line.  Its extra object costs no work outside the timed steps:
   roofline     : the dominant GEMM launch (postnet conv bank forward) timed LIVE with a HIP event pair on its launch
                  stream inside every timed step -- algorithmic fp32 TFLOP/s against the f32 MFMA peak, the executed bf16
                  rate against the dense bf16 peak, HBM traffic per launch read from the committed PMC summary named in
-                 `traffic_source` -- plus `families`: the weight-gradient GEMM in isolation, the TIME-dominant kernel family (the persistent recurrences,
-                 latency-bound) and the LengthRegulator (HBM-bound), timed with event pairs in a short instrumented pass
-                 AFTER the timed region (32 extra event records per step would perturb it), and whole-step TFLOP/s
+                 `traffic_source` -- and whole-step TFLOP/s
+With --full (N=1 only; each can be left out with its own option) the line also carries what needs runs of its own:
+  roofline.families : the weight-gradient GEMM in isolation, the TIME-dominant kernel family (the persistent
+                 recurrences, latency-bound) and the LengthRegulator (HBM-bound), timed with event pairs in a short
+                 instrumented pass AFTER the timed region (32 extra event records per step would perturb it)
+  variants     : the FastPitch bf16 train step (BASELINE configs[2]), measured in a child process
   cpu_baseline : the reference step restated on stock fused torch CPU ops (oracle/ft_torch_cpu.py, pinned to the
-                 reference goldens by tests/test_cpu_baseline.py) on the SAME bs=32 seed-0 batch, on this box's host cores
-                 (rank 0, N=1 only), three whole steps (more if they fit the --cpu-budget) after a small warm-up
+                 reference goldens by tests/test_cpu_baseline.py) on the SAME bs=32 seed-0 batch, on the host's cores
+                 (rank 0), three whole steps (more if they fit the --cpu-budget) after a small warm-up
 The event pairs are owned by this file: it wraps the package's launch wrappers (forwardtacotron_amd.hip.*) for the
 duration of a measurement; the product carries no timing hook.
 """
@@ -342,12 +347,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--family-steps', type=int, default=3, help='instrumented steps after the timed region (rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline measurement, also measure the kernel families, the FastPitch bf16 record '
+                         'and the CPU baseline (N=1 only; minutes, most of them the CPU baseline)')
+    ap.add_argument('--family-steps', type=int, default=3,
+                    help='instrumented steps after the timed region (rank 0, --full only)')
     ap.add_argument('--cpu-budget', type=float, default=150.0,
-                    help='seconds of CPU baseline work beyond which no 4th / 5th step is started (3 are always timed)')
-    ap.add_argument('--cpu-threads', type=int, default=16, help='torch threads of the CPU baseline')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-variants', action='store_true', help='skip the FastPitch bf16 record (N=1 only)')
+                    help='seconds of CPU baseline work beyond which no 4th / 5th step is started (3 are always timed; '
+                         '--full only)')
+    ap.add_argument('--cpu-threads', type=int, default=16, help='torch threads of the CPU baseline (--full only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU baseline of --full')
+    ap.add_argument('--no-variants', action='store_true', help='skip the FastPitch bf16 record of --full')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
@@ -431,7 +441,8 @@ def main():
             ok = 1.0
         except _ftlib.FtError:
             ok = 0.0
-        if ok and world == 1 and args.family_steps > 0:      # (extra steps on one rank only would hang the all-reduce)
+        # (extra steps on one rank only would hang the all-reduce)
+        if ok and args.full and world == 1 and args.family_steps > 0:
             fp = Probes(_hip)
             install_family_probes(fp, batch)
             for _ in range(args.family_steps):
@@ -477,7 +488,8 @@ def main():
         value = tot_frm * args.steps / dt
         step_tflops = data.train_flops(tot_tok, tot_frm) / (dt / args.steps) / 1e12
         roof = dominant_kernel_roofline(bank_ms)
-        roof['families'] = fam
+        if args.full:
+            roof['families'] = fam
         roof['step'] = {'algorithmic_tflops': round(step_tflops, 2),
                         'frac_of_f32_mfma_peak': round(step_tflops / (F32_MFMA_PEAK_TFLOPS * world), 4),
                         'frac_of_bf16_dense_peak': round(step_tflops / (BF16_MFMA_PEAK_TFLOPS * world), 4),
@@ -501,9 +513,9 @@ def main():
             'rnn_modes': dict(zip(('xcd_local_groups', 'agent_scope_groups'), _hip.rnn_mode_counts())),
             'roofline': roof,
         }
-        if world == 1 and not args.no_variants:
+        if args.full and world == 1 and not args.no_variants:
             line['variants'] = {'fastpitch_bf16_train': fastpitch_bf16_record()}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(model_cfg, train_cfg, args.cpu_budget, args.cpu_threads)
         print(json.dumps(line), flush=True)
     if world > 1:
