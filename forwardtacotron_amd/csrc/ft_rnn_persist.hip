@@ -4,8 +4,8 @@
 // from Infinity Cache every step (measured 14.8 MB/step, profiles/r01_pmc_rnn_step.txt).  Here every wave keeps its
 // W_hh fragments in REGISTERS for the whole sequence and only h (forward) or d(gates) (backward) travels between
 // workgroups, through a small exchange buffer:
-//   exchange layout  xb[parity][group = (dir, batch group of 16)][k/4][16][4]   (k = contraction index; a storing wave
-//                    owns whole [16][4] blocks = two full 128-B lines, written by ONE store instruction)
+//   exchange layout  xb[parity][group = (dir, batch group of MB = 16 or 8 rows)][k/4][MB][4]   (k = contraction index; a
+//                    storing wave owns whole [MB][4] blocks = MB/8 full 128-B lines, written by ONE store instruction)
 //   producer: write-through (sc1) stores FIRST -> that wave's s_waitcnt vmcnt(0) -> its lane 0 adds 1 to the
 //             arrival-counter shard of the block (agent scope).  The step's other outputs (h / c / saved gates,
 //             d(pre-activations)) are plain stores issued AFTER the signal, off the critical path.
@@ -34,6 +34,11 @@
 // MFMA 0.6, LDS reduce + barrier 0.6, cell 0.6, store drain 0.4, top 0.4) shaped this version:
 //   * a workgroup covers 16 batch rows (not 32): the operand volume per CU per step (rows x K x 4 B, streamed
 //     through one 64 B/clk L1 path) halves, and a (dir, 16-row) group has half as many producers to wait for;
+//   * the LSTM-512 forward and reduce-scatter BPTT also come in 8 rows per workgroup (template MB, host rows_per_wg):
+//     a group fills one XCD, so at B = 32 the 16-row form runs 4 groups on 4 of the 8 XCDs; 8 rows run 8 groups, one
+//     per XCD, each CU with half the operand bytes, partials and exchange stores per step (MFMA tiles stay 16 rows
+//     tall, rows 8..15 repeat 0..7 and are discarded) -- bit-identical results, 3.10 -> 2.68 / 3.22 -> 2.86 us per step
+//     inside the train step (profiles/r04_rows_ab.txt);
 //   * the x-projection / saved-activation operands of step s+1 are requested during step s (loads return in order, so
 //     a same-step request would sit in front of the exchange loads with its HBM latency);
 //   * 1-D grid with an XCD-aware decode: the 8 XCDs take contiguous ranges of (group, chunk), so a group's exchange
@@ -52,7 +57,7 @@ namespace {
 constexpr int NSH = 16;                // arrival-counter shards per group
 constexpr int CSTRIDE = 32;            // one counter per 128-B line
 constexpr unsigned MAX_SPINS_DEFAULT = 1u << 18;
-constexpr int MB = 16;                 // batch rows per workgroup
+constexpr int MB16 = 16;               // batch rows per workgroup (the forward and the reduce-scatter BPTT also have 8)
 constexpr int NFLAG = 256;             // XCD-local mode: flag words per group (one per signalling wave)
 constexpr int NXCC = 64;               // published XCC ids per group (one per workgroup)
 
@@ -259,10 +264,10 @@ __device__ __forceinline__ bool decode(const Geom& g, int& d, int& bgp, int& chu
 }
 
 // ---------------------------------------------------------------------------------------------------
-// forward: workgroup = 16 batch rows x UB hidden units (all G gates = G*UB/16 column tiles), K = H over NW waves.
+// forward: workgroup = MB batch rows x UB hidden units (all G gates = G*UB/16 column tiles), K = H over NW waves.
 // UB = 8, or 16 for the 512-wide LSTM (32 workgroups per group = one XCD) and the 256-wide GRU: see fwd_persistent
 // ---------------------------------------------------------------------------------------------------
-template <int G, int NW, bool B3, int UB, int BC>
+template <int G, int NW, bool B3, int UB, int BC, int MB>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_kernel(RnnFwdArgs a, Geom geo, float* xb, unsigned* cnt,
                                                                      unsigned* fault, unsigned xb_bytes) {
   // UB hidden units (all G gates) per workgroup: G*UB columns = NT tiles of 16; cell waves = UB / 4 (one [16][4]
@@ -273,6 +278,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
   // (LSTM-512 on 4 waves) takes it too since round 3 (FT_RNN_GRAN4=0: flag words)
   constexpr bool GRAN = B3 && BC <= 2;
   static_assert(UB % 4 == 0 && CW <= NW, "cell waves");
+  static_assert(MB == 16 || MB == 8, "rows per workgroup");
   // partial tiles, double-buffered by step parity: in XCD-local mode no barrier separates a step's readers (cell
   // threads) from the next step's writers
   __shared__ float red2[2 * NW * NT * 16 * RLD];
@@ -282,6 +288,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
   const int u0 = chunk * UB, b0 = bgp * MB;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int q = lane >> 4, l15 = lane & 15;
+  // A-operand row of this lane: with MB = 8, rows 8..15 of every A tile repeat rows 0..7 (same addresses, no extra
+  // lines); their products land in partial rows that no cell thread reads, and rows 0..7 come out bit for bit as in
+  // the 16-row form (an MFMA result element depends on its own A row only)
+  const int ar = l15 & (MB - 1);
   const int H = a.H, T = a.T, nq = H / 4;
   const long ldo = (long)a.ND * H;
   const long ldx = (long)a.ND * G * H;
@@ -340,11 +350,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
   const int pq0 = B3 ? 8 * kb0 : 4 * g0, pnq = B3 ? 8 * max(kb1 - kb0, 0) : 4 * max(g1 - g0, 0);
   const unsigned* pollf = lane < pnq ? myflags + pq0 + lane : nullptr;
 
-  // ---- cell threads (waves 0 .. CW-1): wave jq owns units 4*jq..4*jq+3 of the chunk = one [16][4] exchange block
+  // ---- cell threads (waves 0 .. CW-1): wave jq owns units 4*jq..4*jq+3 of the chunk = one [MB][4] exchange block
+  //      (MB = 8: lanes of rows 8..15 have no row)
   const int jq = tid >> 6, ci = (tid >> 2) & 15, jj = tid & 3;
   const int cu = 4 * jq + jj;
   const int cb = b0 + ci, cun = u0 + cu;
-  const bool sthr = tid < 64 * CW;
+  const bool cwave = tid < 64 * CW;
+  const bool sthr = cwave && ci < MB;
   const bool cthr = sthr && cb < a.B;
   const int L = cthr ? clamp_len(a.lens, cb, T) : 0;
   float bg[G];
@@ -436,8 +448,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
     const unsigned gbase = (unsigned)(((long)2 * par_floats * 4) + ((long)((s - 1) & 1) * par_floats + base_floats) * 8);
     auto goffs = [&](int c, unsigned& oa, unsigned& ob) {
       const long quad = 8 * (kb0 + c) + 2 * q;
-      oa = gbase + (unsigned)((quad * MB + l15) * 4 * 8);
-      ob = gbase + (unsigned)(((quad + 1) * MB + l15) * 4 * 8);
+      oa = gbase + (unsigned)((quad * MB + ar) * 4 * 8);
+      ob = gbase + (unsigned)(((quad + 1) * MB + ar) * 4 * 8);
     };
     Gran gr[2];
     if (s > 0 && !gm) {
@@ -470,7 +482,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
         for (int c = 0; c < GCH; ++c)
           if (g0 + c < g1) {
             const long quad = 4 * (g0 + c) + q;
-            av[c] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + l15) * 4) * 4));
+            av[c] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + ar) * 4) * 4));
           }
         request_xn();
 #pragma unroll
@@ -493,8 +505,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
           for (int c = 0; c < BCH; ++c)
             if (kb0 + c < kb1) {                      // lane (row l15, q): k = 32 blk + 8 q .. +7 = two exchange quads
               const long quad = 8 * (kb0 + c) + 2 * q;
-              aw[c][0] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + l15) * 4) * 4));
-              aw[c][1] = ld_sc1_b128(rs, (unsigned)((rbase + ((quad + 1) * MB + l15) * 4) * 4));
+              aw[c][0] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + ar) * 4) * 4));
+              aw[c][1] = ld_sc1_b128(rs, (unsigned)((rbase + ((quad + 1) * MB + ar) * 4) * 4));
             }
           request_xn();
         }
@@ -565,7 +577,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
         sg[0] = ig; sg[1] = fg; sg[2] = gg; sg[3] = og;
       }
       hprev = hnew;
-      // exchange block [CW*chunk + jq][16][4] of parity s&1, before anything else
+      // exchange block [CW*chunk + jq][MB][4] of parity s&1, before anything else
       const long xe = (long)(s & 1) * par_floats + base_floats + (((long)CW * chunk + jq) * MB + ci) * 4 + jj;
       if (local && GRAN && geo.gran) {  // (granule mode: stored below, for EVERY row)
       } else if (local) {
@@ -586,7 +598,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
                            __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
     } else if (geo.sig_per_wave) {
-      if (sthr) {                                          // the cell waves, wave-uniform
+      if (cwave) {                                         // the cell waves, wave-uniform
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) {
           if (local)
@@ -633,6 +645,7 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs 
                                                                      unsigned* fault, unsigned xb_bytes) {
   __shared__ float red2[2 * NW * 16 * RLD];            // double-buffered by step parity (see the forward kernel)
   __shared__ int s_ok;
+  constexpr int MB = MB16;
   int d, bgp, chunk, grp;
   if (!decode(geo, d, bgp, chunk, grp)) return;
   const int u0 = chunk * 16, b0 = bgp * MB;
@@ -939,21 +952,21 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// backward, reduce-scatter form (bf16-split only): the same workgroup = 16 batch rows x 16 hidden units, but the
+// backward, reduce-scatter form (bf16-split only): the same workgroup = MB batch rows x 16 hidden units, but the
 // recurrent product is formed on the PRODUCER side.  The all-gather form above makes every workgroup pull all G*H
 // d(gates) of its 16 rows each step (LSTM-512: 128 KB per workgroup per step through one L1, plus the 3-way split of
 // 32 K values) to contract them with its W_hh columns.  Here a workgroup contracts only ITS OWN 16 units' d(gates)
 // ([16 rows] x [16 G k's], padded to 64) with its W_hh ROWS -- resident in registers, same 128 KB -- which yields a
 // partial of ALL H outputs, and hands tile c' (16 units) of it to workgroup c':
-//   exchange layout  xb[parity][group][consumer c'][producer p][unit 16][row 16]   (1 KB blocks; an MFMA result lane
-//                    holds 4 rows of one unit = one 16-B write-through store per tile)
-//   consumer: after the arrival wait its 256 cell threads each read ONE float per producer (p-th block + tid,
+//   exchange layout  xb[parity][group][consumer c'][producer p][unit 16][row MB]   (1 KB / 512 B blocks; an MFMA result
+//                    lane holds 4 rows of one unit = one 16-B write-through store per tile)
+//   consumer: after the arrival wait its 16 x MB cell threads each read ONE float per producer (p-th block + tid,
 //             fully coalesced) and add them in producer order -> d(h) of (row, unit); cell math; the new d(gates)
 //             go to LDS, every wave splits them (1 K values, not 32 K) and multiplies its output tiles.
 // Per step a workgroup reads nchunks KB (32) instead of G*H*64 B (128 KB) and splits 1/32 of the values; the cross-
 // workgroup hand-off (stores -> vmcnt(0) -> per-wave arrival -> poll -> loads) is the same as above.
 // ---------------------------------------------------------------------------------------------------
-template <int G, int NW, int NT>
+template <int G, int NW, int NT, int MB>
 __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Geom geo, float* xb, unsigned* cnt,
                                                                 unsigned* fault, unsigned xb_bytes) {
   constexpr int ALD = 68;                             // LDS row stride of the local d(gates) tile [16][64]
@@ -969,10 +982,14 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
   // issued right after the step's hand-off loads have landed (barrier A), a whole MFMA phase before the next ones.
   constexpr bool PF = NW >= 8;
   constexpr int NIN = 7;                              // gates[4], dout, c (LSTM), previous h (GRU) / c (LSTM)
-  __shared__ __attribute__((aligned(16))) float adg2[2 * 16 * ALD];   // double-buffered by step parity
+  // MB = 8 rows: exchange tiles of [16 units][8 rows] (512 B), 128 cell threads (waves 0 and 1); the A tiles of the
+  // products repeat rows 0..7 in rows 8..15, whose results are not stored (see the forward kernel)
+  static_assert(MB == 16 || MB == 8, "rows per workgroup");
+  constexpr int TS = 16 * MB;                         // floats per exchange tile = cell threads
+  __shared__ __attribute__((aligned(16))) float adg2[2 * MB * ALD];   // double-buffered by step parity
   // per-wave partial sums of the incoming tiles (wave w adds the tiles of producers w*TPW .. w*TPW+TPW-1), [wave][unit][row]
-  __shared__ __attribute__((aligned(16))) float rsum[GWV * 256];
-  __shared__ float inb[PF ? 2 * NIN * 256 : 1];       // next-step inputs of the 256 cell threads, by step parity
+  __shared__ __attribute__((aligned(16))) float rsum[GWV * TS];
+  __shared__ float inb[PF ? 2 * NIN * TS : 1];        // next-step inputs of the TS cell threads, by step parity
   __shared__ int s_ok;
   int d, bgp, chunk, grp;
   if (!decode(geo, d, bgp, chunk, grp)) return;
@@ -982,7 +999,7 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
   const int H = a.H, T = a.T, K = G * H, P = geo.nchunks;
   const long ldg = (long)a.ND * K;
   const long ldo = (long)a.ND * H;
-  const long grp_floats = (long)P * P * 256;
+  const long grp_floats = (long)P * P * TS;
   const long par_floats = (long)2 * geo.nbg * grp_floats;
   const long base_floats = (long)grp * grp_floats;
   unsigned* mycnt = cnt + (long)grp * NSH * CSTRIDE;
@@ -1015,25 +1032,27 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
              bw[nt][blk][0], bw[nt][blk][1], bw[nt][blk][2]);
     }
   }
-  for (int i = tid; i < 2 * 16 * ALD; i += NW * 64) adg2[i] = 0.f;  // (GRU: k 48..63 stay zero)
+  for (int i = tid; i < 2 * MB * ALD; i += NW * 64) adg2[i] = 0.f;  // (GRU: k 48..63 stay zero)
 
   // XCD-local mode: cell wave w gathers the tiles the producer chunks p = w*TPW + i (i < TPW) computed for this
   // consumer chunk; such a tile came from producer wave chunk / NT -> flag NW*p + chunk/NT
   const unsigned* pollf =
       (wave < GWV && lane < TPW && wave * TPW + lane < P) ? myflags + NW * (wave * TPW + lane) + chunk / NT : nullptr;
 
-  // ---- cell threads (first 256): thread = (unit cj, row ci), the order of an exchange block
-  const int cj = tid >> 4, ci = tid & 15;
+  // ---- cell threads (first TS): thread = (unit cj, row ci), the order of an exchange block
+  const int cj = tid / MB, ci = tid % MB;
   const int cb = b0 + ci, cun = u0 + cj;
-  const bool sthr = tid < 256;
+  const bool sthr = tid < TS;
   const bool cthr = sthr && cb < a.B;
   const int L = cthr ? clamp_len(a.lens, cb, T) : 0;
   float carry = 0.f;
   // ---- fetching lanes (PF: wave 4): lane = (row fr, unit quad fq) -> 16 bytes = units u0 + 4 fq .. + 3 of row fr
+  //      (MB = 8: the lanes of rows 8..15 fetch nothing)
   const bool fwave = PF && wave == 4;
   const int fr = lane >> 2, fq = lane & 3;
+  const bool flane = fwave && fr < MB;
   const int fb = b0 + fr;
-  const int FL = (fwave && fb < a.B) ? clamp_len(a.lens, fb, T) : 0;
+  const int FL = (flane && fb < a.B) ? clamp_len(a.lens, fb, T) : 0;
 
   float gv[4] = {0.f, 0.f, 0.f, 0.f}, dov = 0.f, cc = 0.f, prev = 0.f;
   auto request = [&](int sn, float (&rgv)[4], float& rdo, float& rcc, float& rprev) {
@@ -1066,7 +1085,7 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
   auto fetch = [&](int sn) {
 #pragma unroll
     for (int i = 0; i < NIN; ++i) fv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (fwave && sn < FL) {
+    if (flane && sn < FL) {
       const int ct = d == 0 ? FL - 1 - sn : sn;
       const int tprev = d == 0 ? ct - 1 : ct + 1;
       const bool has_prev = tprev >= 0 && tprev < FL;
@@ -1085,11 +1104,11 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
     }
   };
   auto publish = [&](int sn) {            // fetching wave: fv -> inb[parity of step sn][value][unit][row]
-    if (fwave) {
-      float* ib = inb + (sn & 1) * (NIN * 256) + (4 * fq) * 16 + fr;
+    if (flane) {
+      float* ib = inb + (sn & 1) * (NIN * TS) + (4 * fq) * MB + fr;
 #pragma unroll
       for (int i = 0; i < NIN; ++i) {
-        ib[i * 256] = fv[i].x; ib[i * 256 + 16] = fv[i].y; ib[i * 256 + 32] = fv[i].z; ib[i * 256 + 48] = fv[i].w;
+        ib[i * TS] = fv[i].x; ib[i * TS + MB] = fv[i].y; ib[i * TS + 2 * MB] = fv[i].z; ib[i * TS + 3 * MB] = fv[i].w;
       }
     }
   };
@@ -1106,7 +1125,7 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
     PROF(0);
     const bool cact = cthr && s < L;
     const int ct = d == 0 ? L - 1 - s : s;
-    float* adg = adg2 + (s & 1) * (16 * ALD);
+    float* adg = adg2 + (s & 1) * (MB * ALD);
     float rec = 0.f;
     if (s > 0) {
       if (local) {       // every wave waits for the producers of its own slice; a timeout is acted on at the next barrier
@@ -1131,37 +1150,37 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
         }
       }
       PROF(1);
-      // The P incoming tiles, [unit 16][row 16] floats each.  Each cell wave takes TPW of them with one 16-byte load per
-      // lane and tile (a whole 1-KB tile per wave instruction), adds them in producer order and leaves its partial in
-      // LDS; the cell threads then add the four partials in wave order.
-      if (wave < GWV) {
-        const long rbase = (long)((s - 1) & 1) * par_floats + base_floats + (long)chunk * P * 256 + 4 * lane;
+      // The P incoming tiles, [unit 16][row MB] floats each.  Each gathering wave takes TPW of them with one 16-byte load
+      // per lane and tile (a whole tile per wave instruction; MB = 8: lanes 0..31), adds them in producer order and
+      // leaves its partial in LDS; the cell threads then add the four partials in wave order.
+      if (wave < GWV && 4 * lane < TS) {
+        const long rbase = (long)((s - 1) & 1) * par_floats + base_floats + (long)chunk * P * TS + 4 * lane;
         float4 v[TPW];
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
           const int pp = wave * TPW + i;
-          v[i] = pp < P ? ld_sc1_b128(rs, (unsigned)((rbase + (long)pp * 256) * 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
+          v[i] = pp < P ? ld_sc1_b128(rs, (unsigned)((rbase + (long)pp * TS) * 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         float4 acc4 = v[0];
 #pragma unroll
         for (int i = 1; i < TPW; ++i) {
           acc4.x += v[i].x; acc4.y += v[i].y; acc4.z += v[i].z; acc4.w += v[i].w;
         }
-        *reinterpret_cast<float4*>(rsum + wave * 256 + 4 * lane) = acc4;
+        *reinterpret_cast<float4*>(rsum + wave * TS + 4 * lane) = acc4;
       }
       __syncthreads();
       if (sthr) {
 #pragma unroll
-        for (int w = 0; w < GWV; ++w) rec += rsum[w * 256 + tid];
+        for (int w = 0; w < GWV; ++w) rec += rsum[w * TS + tid];
       }
     }
     if constexpr (PF) {
       fetch(s + 1);     // (behind barrier A: this step's hand-off loads have landed)
       if (sthr) {       // this step's saved activations, fetched during the previous step
-        const float* ib = inb + (s & 1) * (NIN * 256) + tid;
+        const float* ib = inb + (s & 1) * (NIN * TS) + tid;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) gv[g] = ib[g * 256];
-        dov = ib[4 * 256]; cc = ib[5 * 256]; prev = ib[6 * 256];
+        for (int g = 0; g < 4; ++g) gv[g] = ib[g * TS];
+        dov = ib[4 * TS]; cc = ib[5 * TS]; prev = ib[6 * TS];
       }
     }
     float ngv[4] = {0.f, 0.f, 0.f, 0.f}, ndo = 0.f, ncc = 0.f, nprev = 0.f;
@@ -1211,12 +1230,12 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
       bf16x8 a3[2][3];
 #pragma unroll
       for (int blk = 0; blk < 2; ++blk) {
-        const float* ap = adg + l15 * ALD + 32 * blk + 8 * q;
+        const float* ap = adg + (l15 & (MB - 1)) * ALD + 32 * blk + 8 * q;
         split8(*reinterpret_cast<const float4*>(ap), *reinterpret_cast<const float4*>(ap + 4), a3[blk][0], a3[blk][1],
                a3[blk][2]);
       }
       PROF(5);
-      const long wbase = (long)(s & 1) * par_floats + base_floats + (long)chunk * 256 + l15 * 16 + 4 * q;
+      const long wbase = (long)(s & 1) * par_floats + base_floats + (long)chunk * TS + l15 * MB + 4 * q;
       // (issuing the products term-major over the NT independent tiles instead of tile by tile -- no chain of dependent
       //  MFMAs -- measured 3.24 -> 3.37 us per step: the phase is not bound by the accumulator latency)
 #pragma unroll
@@ -1225,9 +1244,9 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
         mfma6(a3[0], bw[nt][0], acc);
         mfma6(a3[1], bw[nt][1], acc);
         const int cons = wave * NT + nt;
-        if (cons < P) {
+        if (cons < P && 4 * q < MB) {                     // (MB = 8: result rows 8..15 are the repeated ones)
           u32x4 v = {__float_as_uint(acc[0]), __float_as_uint(acc[1]), __float_as_uint(acc[2]), __float_as_uint(acc[3])};
-          const unsigned off = (unsigned)((wbase + (long)cons * P * 256) * 4);
+          const unsigned off = (unsigned)((wbase + (long)cons * P * TS) * 4);
           if (local) __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);       // plain: stays in the XCD's L2
           else __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 16);            // write-through (sc1)
         }
@@ -1309,26 +1328,37 @@ struct PersistWs {
 // forms, the exchange buffer) is zeroed per call from the allocation's start (the fault word is NOT in here: it is the
 // device-global g_rnn_fault, which launches never touch)
 size_t sync_region_bytes(int ngrp) { return (size_t)ngrp * (NSH * CSTRIDE + NFLAG + NXCC) * sizeof(unsigned); }
-PersistWs carve_ws(void* ws, int ngrp, int K) {
+PersistWs carve_ws(void* ws, int ngrp, int K, int mb) {
   PersistWs p;
   p.sync_bytes = sync_region_bytes(ngrp);
   p.cnt = (unsigned*)ws;
   // two fp32 parities, then the granule area of the XCD-local split kernels (two parities of 8-byte granules)
-  p.xb_bytes = (size_t)3 * 2 * ngrp * (K / 4) * MB * 4 * sizeof(float);
+  p.xb_bytes = (size_t)3 * 2 * ngrp * (K / 4) * mb * 4 * sizeof(float);
   p.xb = (float*)((char*)ws + p.sync_bytes);
   p.total_bytes = p.sync_bytes + p.xb_bytes;
   return p;
 }
 
-// reduce-scatter backward: xb[parity][group][consumer][producer][256]
-PersistWs carve_ws_rs(void* ws, int ngrp, int nchunks) {
+// reduce-scatter backward: xb[parity][group][consumer][producer][16 * mb]
+PersistWs carve_ws_rs(void* ws, int ngrp, int nchunks, int mb) {
   PersistWs p;
   p.sync_bytes = sync_region_bytes(ngrp);
   p.cnt = (unsigned*)ws;
-  p.xb_bytes = (size_t)2 * ngrp * nchunks * nchunks * 256 * sizeof(float);
+  p.xb_bytes = (size_t)2 * ngrp * nchunks * nchunks * 16 * mb * sizeof(float);
   p.xb = (float*)((char*)ws + p.sync_bytes);
   p.total_bytes = p.sync_bytes + p.xb_bytes;
   return p;
+}
+
+// Batch rows per workgroup of the forms that come in an 8-row variant (the 512-wide LSTM's forward and reduce-scatter
+// BPTT), for nd * ceil(B / 16) (direction, batch group) groups.  Every group runs on one XCD slot of its own, so with
+// fewer than 8 groups the 16-row form leaves slots idle (B = 32: 4 of 8); 8 rows give the same batch twice the groups,
+// each CU half the rows to load, multiply and update per step, with the same results bit for bit.  Only where the
+// 8-row groups still fit one per slot and are more of them.  FT_RNN_MB=16 (read per launch): always 16 rows.
+int rows_per_wg(int nd, int B) {
+  if (env_int("FT_RNN_MB", 8) == 16) return 16;
+  const int g16 = nd * ft_cdiv(B, 16), g8 = nd * ft_cdiv(B, 8);
+  return g16 < 8 && g8 <= 8 && g8 > g16 ? 8 : 16;
 }
 
 constexpr int MAX_DEV = 16;
@@ -1497,19 +1527,19 @@ double plan_launch(KernelT kernel, int block, Geom& geo, int& grid, hipStream_t 
 // fill_probe (ft_rnn_fwd_xcd_fill): no launch -- report the share of an XCD's CUs the aligned layout of this kernel holds
 double* g_fill_probe = nullptr;
 
-template <int G, int NW, bool B3, int UB, int BC>
+template <int G, int NW, bool B3, int UB, int BC, int MB = MB16>
 int launch_fwd_persist(const RnnFwdArgs& a, Geom geo, const PersistWs& p, hipStream_t stream) {
   if (g_fill_probe) {
     const int ngroups = geo.total / geo.nchunks;
-    *g_fill_probe = xcd_demand(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC>, NW * 64, geo.nchunks * ft_cdiv(ngroups, 8));
+    *g_fill_probe = xcd_demand(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>, NW * 64, geo.nchunks * ft_cdiv(ngroups, 8));
     return FT_OK;
   }
   int grid = 0;
-  const double cus = plan_launch(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC>, NW * 64, geo, grid, stream);
+  const double cus = plan_launch(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>, NW * 64, geo, grid, stream);
   if (cus < 0.0) return -1;
   if (BC > 2 && !env_int("FT_RNN_GRAN4", 1)) geo.gran = 0;
   (void)hipMemsetAsync(p.cnt, 0, p.total_bytes, stream);
-  hipLaunchKernelGGL((ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb,
+  hipLaunchKernelGGL((ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb,
                      p.cnt, ft_rnn_fault_word(), (unsigned)p.xb_bytes);
   admitted_launch_done(cus, stream);
   return ft_check_launch("rnn_fwd_persistent");
@@ -1540,20 +1570,24 @@ int fwd_persistent(RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
   // us per step at T = 841 (lab/gru256_ab.py): 4 waves x 2 blocks x 8 units 2.03 | 8 x 1 x 8: 2.03-2.07 | 4 x 2 x 16:
   // 2.04 | 8 x 1 x 16: 1.78-1.81 | 8 x 1 x 32: 2.30.  FT_RNN_GRU_WIDE=0: the 4-wave 8-unit form.
   const bool gru_wide = G == 3 && H == 256 && b3 && NW == 4 && env_int("FT_RNN_GRU_WIDE", 1);
+  const int mb = wide && G == 4 ? rows_per_wg(a.ND, B) : MB16;
   Geom geo;
   geo.nchunks = H / ((wide || gru_wide) ? 16 : 8);
-  geo.nbg = ft_cdiv(B, MB);
+  geo.nbg = ft_cdiv(B, mb);
   geo.total = a.ND * geo.nbg * geo.nchunks;      // ND = 1: the forward direction's groups only (the workspace keeps two)
   geo.xcd_aware = env_int("FT_RNN_XCDMAP", 1);
   geo.sig_per_wave = env_int("FT_RNN_SIG", 1);
   geo.max_spins = g_max_spins;
-  PersistWs p = carve_ws(ws, 2 * geo.nbg, H);
+  PersistWs p = carve_ws(ws, 2 * geo.nbg, H, mb);
   if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
   geo.xcd_off = 0;
   geo.local_ok = 0;
   geo.gran = 0;
   geo.fast = 0;
   a.s = 0;
+  if constexpr (G == 4) {
+    if (wide && mb == 8) return launch_fwd_persist<G, 8, true, 16, 2, 8>(a, geo, p, stream);
+  }
   if (wide) return launch_fwd_persist<G, 8, true, 16, 2>(a, geo, p, stream);
   if constexpr (G == 3) {
     if (gru_wide) return launch_fwd_persist<G, 8, true, 16, 1>(a, geo, p, stream);
@@ -1586,29 +1620,34 @@ int launch_bwd_persist(const RnnBwdArgs& a, Geom geo, const PersistWs& p, hipStr
   return ft_check_launch("rnn_bwd_persistent");
 }
 
-template <int G, int NW, int NT>
+template <int G, int NW, int NT, int MB = MB16>
 int launch_bwd_rs(const RnnBwdArgs& a, Geom geo, const PersistWs& p, hipStream_t stream) {
   if (g_fill_probe) {
-    *g_fill_probe = xcd_demand(ft_rnn_bwd_rs_kernel<G, NW, NT>, NW * 64, geo.nchunks * ft_cdiv(geo.total / geo.nchunks, 8));
+    *g_fill_probe =
+        xcd_demand(ft_rnn_bwd_rs_kernel<G, NW, NT, MB>, NW * 64, geo.nchunks * ft_cdiv(geo.total / geo.nchunks, 8));
     return FT_OK;
   }
   int grid = 0;
-  const double cus = plan_launch(ft_rnn_bwd_rs_kernel<G, NW, NT>, NW * 64, geo, grid, stream);
+  const double cus = plan_launch(ft_rnn_bwd_rs_kernel<G, NW, NT, MB>, NW * 64, geo, grid, stream);
   if (cus < 0.0) return -1;
   // only the sync region (counters, flags, XCC ids) needs zeroing: every exchange block is written before it is read
   (void)hipMemsetAsync(p.cnt, 0, p.sync_bytes, stream);
-  hipLaunchKernelGGL((ft_rnn_bwd_rs_kernel<G, NW, NT>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb, p.cnt,
+  hipLaunchKernelGGL((ft_rnn_bwd_rs_kernel<G, NW, NT, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb, p.cnt,
                      ft_rnn_fault_word(), (unsigned)p.xb_bytes);
   admitted_launch_done(cus, stream);
   return ft_check_launch("rnn_bwd_persistent_rs");
 }
 
-// reduce-scatter form: H/16 output tiles over NW waves, NT tiles each; -1 if it does not apply
+// reduce-scatter form: H/16 output tiles over NW waves, NT tiles each; -1 if it does not apply.  The LSTM-512 form
+// (G = 4, 32 tiles) comes in 8 rows per workgroup too (rows_per_wg), which regroups geo's batch.
 template <int G>
-int bwd_persistent_rs(RnnBwdArgs a, const Geom& geo, void* ws, size_t ws_bytes, hipStream_t stream) {
+int bwd_persistent_rs(RnnBwdArgs a, Geom geo, void* ws, size_t ws_bytes, hipStream_t stream) {
   const int tiles = a.H / 16;
   if (!env_int("FT_RNN_BWD_RS", 1) || !env_int("FT_RNN_B3", 1) || !geo.sig_per_wave) return -1;
-  PersistWs p = carve_ws_rs(ws, 2 * geo.nbg, geo.nchunks);
+  const int mb = G == 4 && tiles == 32 ? rows_per_wg(2, a.B) : MB16;
+  geo.nbg = ft_cdiv(a.B, mb);
+  geo.total = 2 * geo.nbg * geo.nchunks;
+  PersistWs p = carve_ws_rs(ws, 2 * geo.nbg, geo.nchunks, mb);
   if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
   // measured (lab/rnn_step_us.py, B = 32, us/step, all-gather -> reduce-scatter): LSTM H=512 5.26 -> 4.67;
   // GRU H=256 3.15 -> 3.60, H=128 2.87 -> 2.95, H=64 2.70 -> 2.73: the form pays once the gathered operand is large
@@ -1619,7 +1658,11 @@ int bwd_persistent_rs(RnnBwdArgs a, const Geom& geo, void* ws, size_t ws_bytes, 
     case 4: return launch_bwd_rs<G, 4, 1>(a, geo, p, stream);
     case 8: return launch_bwd_rs<G, 8, 1>(a, geo, p, stream);
     case 16: return launch_bwd_rs<G, 8, 2>(a, geo, p, stream);
-    case 32: return launch_bwd_rs<G, 8, 4>(a, geo, p, stream);
+    case 32:
+      if constexpr (G == 4) {
+        if (mb == 8) return launch_bwd_rs<G, 8, 4, 8>(a, geo, p, stream);
+      }
+      return launch_bwd_rs<G, 8, 4>(a, geo, p, stream);
     default: return -1;
   }
 }
@@ -1637,7 +1680,7 @@ int bwd_persistent(RnnBwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
   if (ft_cdiv(ngroups, NW) > GW) return -1;
   Geom geo;
   geo.nchunks = H / 16;
-  geo.nbg = ft_cdiv(B, MB);
+  geo.nbg = ft_cdiv(B, MB16);
   geo.total = 2 * geo.nbg * geo.nchunks;
   geo.xcd_aware = env_int("FT_RNN_XCDMAP", 1);
   geo.sig_per_wave = env_int("FT_RNN_SIG", 1);
@@ -1651,7 +1694,7 @@ int bwd_persistent(RnnBwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
     const int rc = bwd_persistent_rs<G>(a, geo, ws, ws_bytes, stream);
     if (rc != -1) return rc;
   }
-  PersistWs p = carve_ws(ws, 2 * geo.nbg, K);
+  PersistWs p = carve_ws(ws, 2 * geo.nbg, K, MB16);
   if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
   // (GRU H = 256, K = 768 on 16 waves with 2 of the 24 k-blocks each instead of 8 x 3: 11.9 us per step against 2.45 --
   //  a 1024-thread workgroup caps a lane at 128 registers; 12 waves x 2 blocks: 5.1 us; lab/gru256_ab.py)
@@ -1723,12 +1766,19 @@ extern "C" {
 
 size_t ft_rnn_workspace(int gates, int B, int H) {
   if (gates < 3 || gates > 4 || B <= 0 || H <= 0 || H % 16 != 0) return 0;
-  const int ngrp = 2 * ft_cdiv(B, MB);
-  const PersistWs f = carve_ws(nullptr, ngrp, H);
-  const PersistWs b = carve_ws(nullptr, ngrp, gates * H);
-  const PersistWs r = carve_ws_rs(nullptr, ngrp, H / 16);
-  size_t m = f.total_bytes > b.total_bytes ? f.total_bytes : b.total_bytes;
-  return r.total_bytes > m ? r.total_bytes : m;
+  // the largest of every form's workspace, in 16 and 8 rows per workgroup (8 rows: as many or fewer padded rows, but
+  // up to twice the groups' sync words)
+  size_t m = 0;
+  for (int mb : {MB16, 8}) {
+    const int ngrp = 2 * ft_cdiv(B, mb);
+    const size_t f = carve_ws(nullptr, ngrp, H, mb).total_bytes;
+    const size_t b = carve_ws(nullptr, ngrp, gates * H, mb).total_bytes;
+    const size_t r = carve_ws_rs(nullptr, ngrp, H / 16, mb).total_bytes;
+    m = f > m ? f : m;
+    m = b > m ? b : m;
+    m = r > m ? r : m;
+  }
+  return m;
 }
 
 /* share of ONE XCD's CUs the persistent recurrence of this shape holds while it runs (gates 3 | 4; backward != 0: the
