@@ -275,3 +275,280 @@ extern "C" int ft_dur_extract(const float* attn, int Tm, int Tx, const float* me
                      durations, Tx_out, fstats, istats, rowinfo, bpg);
   return ft_check_launch("dur_extract");
 }
+
+// ==================================================================================================================
+// Per-token pitch and energy (train_tacotron.py:39-93 extract_pitch_energy, :24-35 normalize_values).
+//
+// ft_token_values_kernel, one workgroup per item:
+//   1. frame energies, lanes over frames (loads coalesced along Tmel): sqrt(sum_c exp(mel[c,t])^2), the channels
+//      added in ascending order in fp32 with each square rounded before its add (np.linalg.norm(axis=0, ord=2) is an
+//      axis-0 add.reduce of the squared array); each frame's raw pitch is fetched with it, 0 past pitch_len (zeros are
+//      dropped by the pitch filter, which is exactly the reference's slice truncation).  The (energy, pitch) pairs
+//      live in LDS for up to TV_LDS_FRAMES frames, beyond that in the global workspace.
+//   2. inclusive prefix sum of the durations in LDS (contiguous chunks per lane, a Hillis-Steele scan of the chunk
+//      sums): frames [cum[j], cum[j+1]) belong to token j.
+//   3. one lane per token: the segment means, accumulated in fp64 and rounded to fp32 once.
+// ==================================================================================================================
+namespace {
+
+constexpr int TV_THREADS = 256;
+constexpr int TV_TPL = 8;                                  // tokens per lane: Tx <= 2048
+constexpr int TV_TX_MAX = TV_THREADS * TV_TPL;
+constexpr int TV_LDS_FRAMES = 8192;                        // 64 KiB of (energy, pitch) pairs
+
+constexpr int TV_ST_OK = 0, TV_ST_SUM = 1, TV_ST_XLEN = 2, TV_ST_MELLEN = 3, TV_ST_PLEN = 4, TV_ST_NEGDUR = 5,
+              TV_ST_NOWS = 6;
+
+__device__ __forceinline__ float tv_energy_term(float acc, float m) {
+#pragma clang fp contract(off)
+  const float e = expf(m);
+  return acc + e * e;                                      // the square rounded, then the add: no FMA
+}
+
+__global__ void __launch_bounds__(TV_THREADS) ft_token_values_kernel(
+    const float* __restrict__ mel, int n_mels, int Tmel, const long* __restrict__ mel_len,
+    const float* __restrict__ pitch, int Tp, const long* __restrict__ pitch_len, const long* __restrict__ dur, int Tx,
+    const long* __restrict__ x_len, float fmin, float fmax, float* __restrict__ pitch_tok,
+    float* __restrict__ energy_tok, int* __restrict__ status, float2* __restrict__ frames_ws) {
+  __shared__ float2 s_fr[TV_LDS_FRAMES];
+  __shared__ long s_cum[TV_TX_MAX + 1];                    // s_cum[j + 1] = d_0 + ... + d_j, s_cum[0] = 0
+  __shared__ long s_part[TV_THREADS];
+  __shared__ int s_neg;
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long xl_l = x_len[b], ml_l = mel_len[b], pl_l = pitch_len[b];
+  long d[TV_TPL];                                          // durations requested with the lengths
+#pragma unroll
+  for (int k = 0; k < TV_TPL; ++k) {
+    const int j = tid + k * TV_THREADS;
+    d[k] = j < Tx ? dur[(long)b * Tx + j] : 0;
+  }
+  float* pt = pitch_tok + (long)b * Tx;
+  float* et = energy_tok + (long)b * Tx;
+
+  int st = TV_ST_OK;
+  if (xl_l < 1 || xl_l > Tx) st = TV_ST_XLEN;
+  else if (ml_l < 1 || ml_l > Tmel) st = TV_ST_MELLEN;
+  else if (pl_l < 0 || pl_l > Tp) st = TV_ST_PLEN;
+  else if (ml_l > TV_LDS_FRAMES && frames_ws == nullptr) st = TV_ST_NOWS;
+  if (st != TV_ST_OK) {                                    // uniform over the block
+    for (int j = tid; j < Tx; j += TV_THREADS) { pt[j] = 0.f; et[j] = 0.f; }
+    if (tid == 0) status[b] = st;
+    return;
+  }
+  const int xl = (int)xl_l, ml = (int)ml_l, pl = (int)pl_l;
+  float2* fr = ml <= TV_LDS_FRAMES ? s_fr : frames_ws + (long)b * Tmel;
+  if (tid == 0) s_neg = 0;
+
+  // ---- 1. frame energies and pitches --------------------------------------------------------------------------------
+  const float* M = mel + (long)b * n_mels * Tmel;          // M[c * Tmel + t]
+  const float* P = pitch + (long)b * Tp;
+  for (int t = tid; t < ml; t += TV_THREADS) {
+    const float p = t < pl ? P[t] : 0.f;
+    float acc = 0.f;
+    int c = 0;
+    for (; c + 16 <= n_mels; c += 16) {
+      float v[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) v[k] = M[(long)(c + k) * Tmel + t];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) acc = tv_energy_term(acc, v[k]);
+    }
+    for (; c < n_mels; ++c) acc = tv_energy_term(acc, M[(long)c * Tmel + t]);
+    fr[t] = make_float2(sqrtf(acc), p);
+  }
+  __syncthreads();                                         // s_neg initialised
+
+  // ---- 2. duration prefix sum ---------------------------------------------------------------------------------------
+  bool neg = false;
+#pragma unroll
+  for (int k = 0; k < TV_TPL; ++k) {
+    const int j = tid + k * TV_THREADS;
+    const long v = j < xl ? d[k] : 0;
+    neg |= v < 0;
+    s_cum[j + 1] = v;
+  }
+  if (neg) s_neg = 1;
+  if (tid == 0) s_cum[0] = 0;
+  __syncthreads();
+  long part = 0;
+#pragma unroll
+  for (int k = 0; k < TV_TPL; ++k) part += s_cum[1 + tid * TV_TPL + k];
+  s_part[tid] = part;
+  __syncthreads();
+  for (int o = 1; o < TV_THREADS; o <<= 1) {
+    const long v = tid >= o ? s_part[tid - o] : 0;
+    __syncthreads();
+    s_part[tid] += v;
+    __syncthreads();
+  }
+  long run = tid ? s_part[tid - 1] : 0;
+#pragma unroll
+  for (int k = 0; k < TV_TPL; ++k) {
+    run += s_cum[1 + tid * TV_TPL + k];
+    s_cum[1 + tid * TV_TPL + k] = run;
+  }
+  __syncthreads();
+
+  // train_tacotron.py:63 asserts sum(dur) == mel_len (the item is skipped); a negative duration is an input error
+  st = s_neg ? TV_ST_NEGDUR : (s_cum[xl] != ml_l ? TV_ST_SUM : TV_ST_OK);
+  if (tid == 0) status[b] = st;
+  if (st != TV_ST_OK) {
+    for (int j = tid; j < Tx; j += TV_THREADS) { pt[j] = 0.f; et[j] = 0.f; }
+    return;
+  }
+
+  // ---- 3. segment means; zip(range(mel_len), cum[:-1], cum[1:]) stops after min(mel_len, x_len) tokens --------------
+  const int ntok = xl < ml ? xl : ml;
+  for (int j = tid; j < Tx; j += TV_THREADS) {
+    float pv = 0.f, ev = 0.f;
+    if (j < ntok) {
+      const int a = (int)s_cum[j], e = (int)s_cum[j + 1];  // 0 <= a <= e <= mel_len
+      double ps = 0.0, es = 0.0;
+      int pn = 0;
+      for (int t = a; t < e; ++t) {
+        const float2 f = fr[t];
+        es += (double)f.x;
+        if (f.y != 0.f && f.y >= fmin && f.y <= fmax) { ps += (double)f.y; ++pn; }   // NaN fails every test
+      }
+      if (pn) pv = (float)(ps / (double)pn);
+      if (e > a) ev = (float)(es / (double)(e - a));
+    }
+    pt[j] = pv;
+    et[j] = ev;
+  }
+}
+
+// ---- per-speaker pitch statistics and normalisation (normalize_values) --------------------------------------------
+// Three launches over one speaker's token pitches v[n] in the caller's (fixed) order.  Slab p covers the contiguous
+// range [p * chunk, min(n, (p + 1) * chunk)), chunk = ceil(n / P), P = ps_slabs(n): a function of n only.  Every
+// block that needs a total sums the P slabs itself in ascending order, so there is no atomic and no cross-workgroup
+// wait, and one input gives one result bit pattern.
+//   ft_pstat_sum_kernel:  slab[p] = (sum of the nonzero v, their count), fp64;
+//   ft_pstat_sq_kernel:   mean = sum / count; slab[P + p].x = sum of (v - mean)^2 over the nonzero v, fp64;
+//   ft_pstat_norm_kernel: std = sqrt(sq / count) (population, as np.std); mean32 = (float)mean, std32 = (float)std,
+//                         std32 = 1e10 unless std32 > 0; v = (v - mean32) / std32 in fp32 where v != 0.
+constexpr int PS_THREADS = 256;
+constexpr int PS_MAX_SLABS = 256;
+constexpr long PS_MIN_CHUNK = 4096;
+
+int ps_slabs(long n) {
+  const long p = (n + PS_MIN_CHUNK - 1) / PS_MIN_CHUNK;
+  return p < 1 ? 1 : (p > PS_MAX_SLABS ? PS_MAX_SLABS : (int)p);
+}
+
+__device__ __forceinline__ double ps_block_sum(double v, double* red) {
+  v = ft_wave_sum_d(v);                                    // fixed butterfly, then the four waves in order
+  __syncthreads();                                         // red is free from a previous call
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < PS_THREADS / 64; ++w) s += red[w];
+  return s;
+}
+
+__device__ __forceinline__ void ps_totals(const double2* __restrict__ slab, int P, double* sum, double* cnt,
+                                          double* sq) {
+  double s = 0.0, c = 0.0, q = 0.0;
+  for (int p = 0; p < P; ++p) {
+    const double2 a = slab[p];
+    s += a.x;
+    c += a.y;
+    if (sq) q += slab[P + p].x;
+  }
+  *sum = s;
+  *cnt = c;
+  if (sq) *sq = q;
+}
+
+__global__ void __launch_bounds__(PS_THREADS) ft_pstat_sum_kernel(const float* __restrict__ v, long n, long chunk,
+                                                                  double2* __restrict__ slab) {
+  __shared__ double red[PS_THREADS / 64];
+  const long lo = (long)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+  double s = 0.0, c = 0.0;
+  for (long i = lo + threadIdx.x; i < hi; i += PS_THREADS) {
+    const float x = v[i];
+    if (x != 0.f) { s += (double)x; c += 1.0; }
+  }
+  s = ps_block_sum(s, red);
+  c = ps_block_sum(c, red);
+  if (threadIdx.x == 0) slab[blockIdx.x] = make_double2(s, c);
+}
+
+__global__ void __launch_bounds__(PS_THREADS) ft_pstat_sq_kernel(const float* __restrict__ v, long n, long chunk,
+                                                                 double2* __restrict__ slab) {
+  __shared__ double red[PS_THREADS / 64];
+  const int P = gridDim.x;
+  double sum, cnt;
+  ps_totals(slab, P, &sum, &cnt, nullptr);
+  const double mean = sum / cnt;
+  const long lo = (long)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+  double q = 0.0;
+  for (long i = lo + threadIdx.x; i < hi; i += PS_THREADS) {
+    const float x = v[i];
+    if (x != 0.f) { const double dx = (double)x - mean; q += dx * dx; }
+  }
+  q = ps_block_sum(q, red);
+  if (threadIdx.x == 0) slab[P + blockIdx.x] = make_double2(q, 0.0);
+}
+
+__global__ void __launch_bounds__(PS_THREADS) ft_pstat_norm_kernel(float* __restrict__ v, long n, int P,
+                                                                   const double2* __restrict__ slab,
+                                                                   double* __restrict__ stats) {
+  double sum, cnt, sq;
+  ps_totals(slab, P, &sum, &cnt, &sq);
+  const double mean = sum / cnt, sd = sqrt(sq / cnt);     // no nonzero value: NaN, NaN (np.mean / np.std of [])
+  const float m32 = (float)mean;
+  float s32 = (float)sd;
+  if (!(s32 > 0.f)) s32 = 1e10f;                           // train_tacotron.py:28-29
+  for (long i = (long)blockIdx.x * PS_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * PS_THREADS) {
+    const float x = v[i];
+    if (x != 0.f) v[i] = (x - m32) / s32;                  // zeros stay 0 (:31-34)
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    stats[0] = cnt; stats[1] = mean; stats[2] = sd; stats[3] = (double)m32; stats[4] = (double)s32;
+  }
+}
+
+}  // namespace
+
+extern "C" size_t ft_token_values_workspace(int B, int Tmel) {
+  if (B <= 0 || Tmel <= 0) return 0;
+  return Tmel > TV_LDS_FRAMES ? (size_t)B * Tmel * sizeof(float2) : 0;
+}
+
+extern "C" int ft_token_values(const float* mel, int n_mels, int Tmel, const long* mel_len, const float* pitch, int Tp,
+                               const long* pitch_len, const long* dur, int Tx, const long* x_len, float pitch_min_freq,
+                               float pitch_max_freq, int B, float* pitch_tok, float* energy_tok, int* status, void* ws,
+                               void* stream) {
+  FT_REQUIRE(B >= 0 && n_mels > 0 && Tmel > 0 && Tp > 0 && Tx > 0, "token_values: bad dims");
+  FT_REQUIRE(Tx <= TV_TX_MAX, "token_values: at most %d tokens per item (got %d)", TV_TX_MAX, Tx);
+  if (B == 0) return FT_OK;
+  FT_REQUIRE(Tmel <= TV_LDS_FRAMES || ws != nullptr, "token_values: a workspace is required for Tmel > %d",
+             TV_LDS_FRAMES);
+  hipLaunchKernelGGL(ft_token_values_kernel, dim3(B), dim3(TV_THREADS), 0, (hipStream_t)stream, mel, n_mels, Tmel,
+                     mel_len, pitch, Tp, pitch_len, dur, Tx, x_len, pitch_min_freq, pitch_max_freq, pitch_tok,
+                     energy_tok, status, Tmel > TV_LDS_FRAMES ? (float2*)ws : nullptr);
+  return ft_check_launch("token_values");
+}
+
+extern "C" size_t ft_pitch_norm_workspace(long n) {
+  if (n <= 0) return 0;
+  return (size_t)2 * ps_slabs(n) * sizeof(double2);
+}
+
+extern "C" int ft_pitch_norm(float* values, long n, double* stats, void* ws, void* stream) {
+  FT_REQUIRE(n >= 0 && stats != nullptr, "pitch_norm: bad arguments");
+  if (n == 0) return FT_OK;
+  FT_REQUIRE(ws != nullptr, "pitch_norm: a workspace is required");
+  const int P = ps_slabs(n);
+  const long chunk = (n + P - 1) / P;
+  const long blocks = (n + PS_THREADS - 1) / PS_THREADS;
+  double2* slab = (double2*)ws;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ft_pstat_sum_kernel, dim3(P), dim3(PS_THREADS), 0, s, values, n, chunk, slab);
+  hipLaunchKernelGGL(ft_pstat_sq_kernel, dim3(P), dim3(PS_THREADS), 0, s, values, n, chunk, slab);
+  hipLaunchKernelGGL(ft_pstat_norm_kernel, dim3(blocks < 1024 ? (int)blocks : 1024), dim3(PS_THREADS), 0, s, values,
+                     n, P, (const double2*)slab, stats);
+  return ft_check_launch("pitch_norm");
+}

@@ -156,21 +156,28 @@ def extract_durations(model, batches: Iterable[Dict], out_dir: Union[str, os.Pat
             mel = batch['mel'].to(attn.device, non_blocking=True)
             x = batch['x'].to(attn.device, non_blocking=True)
             res = extractor.extract_batch(attn.contiguous(), x, batch['x_len'], mel.contiguous(), batch['mel_len'])
-            dur = res.durations.cpu().numpy()
-            att_score = res.att_score.cpu().numpy()
-            align_score = res.align_score.cpu().numpy()
-            max_dur = res.max_duration.cpu().numpy()
-            max_ones = res.max_consecutive_ones.cpu().numpy()
-            x_len = batch['x_len'].cpu().numpy()
-            mel_len = batch['mel_len'].cpu().numpy()
-            for b, item_id in enumerate(batch['item_id']):
-                d = dur[b, :x_len[b]].astype(np.int64)
-                np.save(os.path.join(out_dir, f'{item_id}.npy'), d, allow_pickle=False)
-                if save_attention:
-                    np.save(os.path.join(save_attention, f'{item_id}.npy'),
-                            attn[b, :mel_len[b], :x_len[b]].cpu().numpy(), allow_pickle=False)
-                stats[item_id] = DurationStats(att_sharpness_score=float(att_score[b]),
-                                               att_align_score=float(align_score[b]),
-                                               max_consecutive_ones=int(max_ones[b]),
-                                               max_duration=int(max_dur[b]))
+            write_durations(res, batch, attn, out_dir, save_attention, stats)
     return stats
+
+
+def write_durations(res: DurationBatch, batch: Dict, attn: torch.Tensor, out_dir: Union[str, os.PathLike],
+                    save_attention: Optional[Union[str, os.PathLike]], stats: Dict[str, DurationStats]) -> None:
+    """extract_durations' output for one batch: <out_dir>/<item_id>.npy int64 durations [x_len], the attention
+    [mel_len, x_len] under `save_attention` if given, and stats[item_id]"""
+    dur = res.durations.cpu().numpy()
+    att_score = res.att_score.cpu().numpy()
+    align_score = res.align_score.cpu().numpy()
+    max_dur = res.max_duration.cpu().numpy()
+    max_ones = res.max_consecutive_ones.cpu().numpy()
+    x_len = batch['x_len'].cpu().numpy()
+    mel_len = batch['mel_len'].cpu().numpy()
+    for b, item_id in enumerate(batch['item_id']):
+        d = dur[b, :x_len[b]].astype(np.int64)
+        np.save(os.path.join(out_dir, f'{item_id}.npy'), d, allow_pickle=False)
+        if save_attention:
+            np.save(os.path.join(save_attention, f'{item_id}.npy'),
+                    attn[b, :mel_len[b], :x_len[b]].cpu().numpy(), allow_pickle=False)
+        stats[item_id] = DurationStats(att_sharpness_score=float(att_score[b]),
+                                       att_align_score=float(align_score[b]),
+                                       max_consecutive_ones=int(max_ones[b]),
+                                       max_duration=int(max_dur[b]))

@@ -21,7 +21,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#define FWDTACO_ABI_VERSION 6
+#define FWDTACO_ABI_VERSION 7
 
 #ifdef __cplusplus
 extern "C" {
@@ -575,6 +575,30 @@ int ft_dur_extract(const float* attn, int Tm, int Tx, const float* mel, int n_me
                    const long* x_len, const long* mel_len, const long* sil_ids, int n_sil, float silence_threshold,
                    float silence_prob_shift, int B, long* durations, int Tx_out, double* fstats, long* istats,
                    void* ws, void* stream);
+
+/* ---- per-token pitch and energy (train_tacotron.py:39-93 extract_pitch_energy ; :24-35 normalize_values) ---------- */
+/* One workgroup per item b; every length is read on the device.  Inputs: log mel [B,n_mels,Tmel] fp32, mel_len [B]
+ * int64; raw pitch [B,Tp] fp32 and pitch_len [B] int64 (item b's track is pitch[b, :pitch_len]); dur [B,Tx] int64,
+ * x_len [B] int64.  energy[t] = ||exp(mel[:, t])||_2 (:62; fp32, channels added in ascending order, each square
+ * rounded before its add).  Token j < min(mel_len, x_len) covers frames [cum_j, cum_j + dur_j) (:65-73): pitch_tok =
+ * mean of the raw pitch there without zeros and values outside [pitch_min_freq, pitch_max_freq] (inclusive; frames
+ * past pitch_len count as dropped), energy_tok = mean of the frame energies; both summed in fp64 and rounded once, 0
+ * for an empty segment and for every j >= min(mel_len, x_len).  status [B] int32: 0 ok, 1 durations do not sum to
+ * mel_len (:63: the item is skipped), 2 bad x_len (1..Tx), 3 bad mel_len (1..Tmel), 4 bad pitch_len (0..Tp),
+ * 5 negative duration, 6 no workspace; an item with status != 0 gets zeros.  Tx <= 2048; ws:
+ * ft_token_values_workspace(B, Tmel) bytes (0 for Tmel <= 8192: the frame values then sit in LDS; NULL allowed). */
+size_t ft_token_values_workspace(int B, int Tmel);
+int ft_token_values(const float* mel, int n_mels, int Tmel, const long* mel_len, const float* pitch, int Tp,
+                    const long* pitch_len, const long* dur, int Tx, const long* x_len, float pitch_min_freq,
+                    float pitch_max_freq, int B, float* pitch_tok, float* energy_tok, int* status, void* ws,
+                    void* stream);
+/* normalize_values over one speaker's token pitches values[n] (the caller keeps them in a fixed item order), in place:
+ * count, mean and population std of the nonzero values in fp64 (two passes, fixed-order slabs, no atomics), then
+ * mean32 = (float)mean, std32 = (float)std, std32 = 1e10 unless std32 > 0 (:28-29; no nonzero value: mean NaN), and
+ * v = (v - mean32) / std32 in fp32 where v != 0 (zeros stay 0).  stats [5] fp64 = (count, mean, std, mean32, std32),
+ * not written for n == 0.  Three launches; ws: ft_pitch_norm_workspace(n) bytes. */
+size_t ft_pitch_norm_workspace(long n);
+int ft_pitch_norm(float* values, long n, double* stats, void* ws, void* stream);
 
 /* ---- Tacotron teacher-forced attention recurrence (models/tacotron.py:124-146 Decoder.forward, :65-99 LSA) -------- */
 /* All S decoder steps of attn_rnn (GRUCell 384 -> 256, gates r, z, n) + LSA (location conv 2 -> 32, k = 31, pad 15, no
