@@ -38,7 +38,9 @@
 //     a group fills one XCD, so at B = 32 the 16-row form runs 4 groups on 4 of the 8 XCDs; 8 rows run 8 groups, one
 //     per XCD, each CU with half the operand bytes, partials and exchange stores per step (MFMA tiles stay 16 rows
 //     tall, rows 8..15 repeat 0..7 and are discarded) -- bit-identical results, 3.10 -> 2.68 / 3.22 -> 2.86 us per step
-//     inside the train step (profiles/r04_rows_ab.txt);
+//     inside the train step (profiles/r04_rows_ab.txt).  The GRU-256 forward and all-gather BPTT (the postnet and
+//     prenet GRUs: 16 workgroups per group) have the same 8-row variant: 1.80 -> 1.57 / 2.40 -> 2.05 us per step
+//     inside the train step (profiles/r05_rows_gru_ab.txt);
 //   * the x-projection / saved-activation operands of step s+1 are requested during step s (loads return in order, so
 //     a same-step request would sit in front of the exchange loads with its HBM latency);
 //   * 1-D grid with an XCD-aware decode: the 8 XCDs take contiguous ranges of (group, chunk), so a group's exchange
@@ -57,7 +59,7 @@ namespace {
 constexpr int NSH = 16;                // arrival-counter shards per group
 constexpr int CSTRIDE = 32;            // one counter per 128-B line
 constexpr unsigned MAX_SPINS_DEFAULT = 1u << 18;
-constexpr int MB16 = 16;               // batch rows per workgroup (the forward and the reduce-scatter BPTT also have 8)
+constexpr int MB16 = 16;               // batch rows per workgroup (some forms also have 8: rows_per_wg)
 constexpr int NFLAG = 256;             // XCD-local mode: flag words per group (one per signalling wave)
 constexpr int NXCC = 64;               // published XCC ids per group (one per workgroup)
 
@@ -638,19 +640,20 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
 }
 
 // ---------------------------------------------------------------------------------------------------
-// backward: workgroup = 16 batch rows x 16 hidden units, K = G*H over NW waves
+// backward: workgroup = MB batch rows x 16 hidden units, K = G*H over NW waves
 // ---------------------------------------------------------------------------------------------------
-template <int G, int NW, int GW, bool B3>
+template <int G, int NW, int GW, bool B3, int MB>
 __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs a, Geom geo, float* xb, unsigned* cnt,
                                                                      unsigned* fault, unsigned xb_bytes) {
+  static_assert(MB == 16 || MB == 8, "rows per workgroup");
   __shared__ float red2[2 * NW * 16 * RLD];            // double-buffered by step parity (see the forward kernel)
   __shared__ int s_ok;
-  constexpr int MB = MB16;
   int d, bgp, chunk, grp;
   if (!decode(geo, d, bgp, chunk, grp)) return;
   const int u0 = chunk * 16, b0 = bgp * MB;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int q = lane >> 4, l15 = lane & 15;
+  const int ar = l15 & (MB - 1);                       // A-operand row (MB = 8: rows 8..15 repeat 0..7, see the forward)
   const int H = a.H, T = a.T, K = G * H, nq = K / 4;
   const long ldg = (long)a.ND * K;
   const long ldo = (long)a.ND * H;
@@ -703,11 +706,13 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs 
   const int pq0 = B3 ? 8 * kb0 : 4 * g0, pnq = B3 ? 8 * max(kb1 - kb0, 0) : 4 * max(g1 - g0, 0);
   const unsigned* pollf = lane < pnq ? myflags + ((4 * (pq0 + lane)) % H) / 4 : nullptr;
 
-  // ---- cell threads (first 256): wave j4 owns units 4*j4..4*j4+3 -> whole [16][4] exchange blocks, one per gate
+  // ---- cell threads (first 256): wave j4 owns units 4*j4..4*j4+3 -> whole [MB][4] exchange blocks, one per gate
+  //      (MB = 8: lanes of rows 8..15 have no row)
   const int j4 = tid >> 6, ci = (tid >> 2) & 15, jj = tid & 3;
   const int cj = 4 * j4 + jj;
   const int cb = b0 + ci, cun = u0 + cj;
-  const bool sthr = tid < 256;
+  const bool cwave = tid < 256;
+  const bool sthr = cwave && ci < MB;
   const bool cthr = sthr && cb < a.B;
   const int L = cthr ? clamp_len(a.lens, cb, T) : 0;
   float carry = 0.f;
@@ -758,8 +763,8 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs 
         const unsigned gbase = (unsigned)(((long)2 * par_floats * 4) + ((long)((s - 1) & 1) * par_floats + base_floats) * 8);
         auto offs = [&](int c, unsigned& oa, unsigned& ob) {
           const long quad = 8 * (kb0 + c) + 2 * q;
-          oa = gbase + (unsigned)((quad * MB + l15) * 4 * 8);
-          ob = gbase + (unsigned)(((quad + 1) * MB + l15) * 4 * 8);
+          oa = gbase + (unsigned)((quad * MB + ar) * 4 * 8);
+          ob = gbase + (unsigned)(((quad + 1) * MB + ar) * 4 * 8);
         };
         Gran gr[2];
         unsigned oa, ob;
@@ -814,15 +819,15 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs 
           for (int c = 0; c < GW; ++c)
             if (g0 + c < g1) {
               const long quad = 4 * (g0 + c) + q;
-              av[c] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + l15) * 4) * 4));
+              av[c] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + ar) * 4) * 4));
             }
         } else {
 #pragma unroll
           for (int c = 0; c < BW; ++c)
             if (kb0 + c < kb1) {
               const long quad = 8 * (kb0 + c) + 2 * q;
-              aw[c][0] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + l15) * 4) * 4));
-              aw[c][1] = ld_sc1_b128(rs, (unsigned)((rbase + ((quad + 1) * MB + l15) * 4) * 4));
+              aw[c][0] = ld_sc1_b128(rs, (unsigned)((rbase + (quad * MB + ar) * 4) * 4));
+              aw[c][1] = ld_sc1_b128(rs, (unsigned)((rbase + ((quad + 1) * MB + ar) * 4) * 4));
             }
         }
       }
@@ -907,7 +912,7 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs 
         }
       }
     } else if (geo.sig_per_wave) {
-      if (sthr) {                                          // waves 0..3, wave-uniform
+      if (cwave) {                                         // waves 0..3, wave-uniform
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) {
           if (local)
@@ -1351,10 +1356,11 @@ PersistWs carve_ws_rs(void* ws, int ngrp, int nchunks, int mb) {
 }
 
 // Batch rows per workgroup of the forms that come in an 8-row variant (the 512-wide LSTM's forward and reduce-scatter
-// BPTT), for nd * ceil(B / 16) (direction, batch group) groups.  Every group runs on one XCD slot of its own, so with
+// BPTT, the 256-wide GRU's forward and all-gather BPTT), for nd * ceil(B / 16) (direction, batch group) groups.  Every group runs on one XCD slot of its own, so with
 // fewer than 8 groups the 16-row form leaves slots idle (B = 32: 4 of 8); 8 rows give the same batch twice the groups,
 // each CU half the rows to load, multiply and update per step, with the same results bit for bit.  Only where the
-// 8-row groups still fit one per slot and are more of them.  FT_RNN_MB=16 (read per launch): always 16 rows.
+// 8-row groups still fit one per slot and are more of them.  The narrower GRUs (the predictors, H <= 128) stay on 16
+// rows: not measured.  FT_RNN_MB=16 (read per launch): always 16 rows.
 int rows_per_wg(int nd, int B) {
   if (env_int("FT_RNN_MB", 8) == 16) return 16;
   const int g16 = nd * ft_cdiv(B, 16), g8 = nd * ft_cdiv(B, 8);
@@ -1570,7 +1576,7 @@ int fwd_persistent(RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
   // us per step at T = 841 (lab/gru256_ab.py): 4 waves x 2 blocks x 8 units 2.03 | 8 x 1 x 8: 2.03-2.07 | 4 x 2 x 16:
   // 2.04 | 8 x 1 x 16: 1.78-1.81 | 8 x 1 x 32: 2.30.  FT_RNN_GRU_WIDE=0: the 4-wave 8-unit form.
   const bool gru_wide = G == 3 && H == 256 && b3 && NW == 4 && env_int("FT_RNN_GRU_WIDE", 1);
-  const int mb = wide && G == 4 ? rows_per_wg(a.ND, B) : MB16;
+  const int mb = (wide && G == 4) || gru_wide ? rows_per_wg(a.ND, B) : MB16;
   Geom geo;
   geo.nchunks = H / ((wide || gru_wide) ? 16 : 8);
   geo.nbg = ft_cdiv(B, mb);
@@ -1590,6 +1596,7 @@ int fwd_persistent(RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
   }
   if (wide) return launch_fwd_persist<G, 8, true, 16, 2>(a, geo, p, stream);
   if constexpr (G == 3) {
+    if (gru_wide && mb == 8) return launch_fwd_persist<G, 8, true, 16, 1, 8>(a, geo, p, stream);
     if (gru_wide) return launch_fwd_persist<G, 8, true, 16, 1>(a, geo, p, stream);
   }
   if (b3) {
@@ -1603,19 +1610,19 @@ int fwd_persistent(RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
                  : launch_fwd_persist<G, 4, false, 8, 1>(a, geo, p, stream);
 }
 
-template <int G, int NW, int GW, bool B3>
+template <int G, int NW, int GW, bool B3, int MB = MB16>
 int launch_bwd_persist(const RnnBwdArgs& a, Geom geo, const PersistWs& p, hipStream_t stream) {
   if (g_fill_probe) {
-    *g_fill_probe = xcd_demand(ft_rnn_bwd_persist_kernel<G, NW, GW, B3>, NW * 64,
+    *g_fill_probe = xcd_demand(ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>, NW * 64,
                                geo.nchunks * ft_cdiv(geo.total / geo.nchunks, 8));
     return FT_OK;
   }
   int grid = 0;
-  const double cus = plan_launch(ft_rnn_bwd_persist_kernel<G, NW, GW, B3>, NW * 64, geo, grid, stream);
+  const double cus = plan_launch(ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>, NW * 64, geo, grid, stream);
   if (cus < 0.0) return -1;
   (void)hipMemsetAsync(p.cnt, 0, p.total_bytes, stream);
-  hipLaunchKernelGGL((ft_rnn_bwd_persist_kernel<G, NW, GW, B3>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb, p.cnt,
-                     ft_rnn_fault_word(), (unsigned)p.xb_bytes);
+  hipLaunchKernelGGL((ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb,
+                     p.cnt, ft_rnn_fault_word(), (unsigned)p.xb_bytes);
   admitted_launch_done(cus, stream);
   return ft_check_launch("rnn_bwd_persistent");
 }
@@ -1694,11 +1701,19 @@ int bwd_persistent(RnnBwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
     const int rc = bwd_persistent_rs<G>(a, geo, ws, ws_bytes, stream);
     if (rc != -1) return rc;
   }
-  PersistWs p = carve_ws(ws, 2 * geo.nbg, K, MB16);
-  if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
   // (GRU H = 256, K = 768 on 16 waves with 2 of the 24 k-blocks each instead of 8 x 3: 11.9 us per step against 2.45 --
   //  a 1024-thread workgroup caps a lane at 128 registers; 12 waves x 2 blocks: 5.1 us; lab/gru256_ab.py)
-  if (K % 32 == 0 && ft_cdiv(K / 32, NW) <= GW / 2 && env_int("FT_RNN_B3", 1)) {
+  const bool b3 = K % 32 == 0 && ft_cdiv(K / 32, NW) <= GW / 2 && env_int("FT_RNN_B3", 1);
+  // the GRU-256 form (8 waves x 3 resident k-blocks) comes in 8 rows per workgroup too (rows_per_wg): regroup the batch
+  const int mb = G == 3 && H == 256 && b3 && NW == 8 && GW == 8 ? rows_per_wg(2, B) : MB16;
+  geo.nbg = ft_cdiv(B, mb);
+  geo.total = 2 * geo.nbg * geo.nchunks;
+  PersistWs p = carve_ws(ws, 2 * geo.nbg, K, mb);
+  if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
+  if (b3) {
+    if constexpr (G == 3) {
+      if (mb == 8) return launch_bwd_persist<G, 8, 8, true, 8>(a, geo, p, stream);
+    }
     if (NW == 16) return launch_bwd_persist<G, 16, 16, true>(a, geo, p, stream);
     if (NW == 8) return GW == 16 ? launch_bwd_persist<G, 8, 16, true>(a, geo, p, stream)
                                  : launch_bwd_persist<G, 8, 8, true>(a, geo, p, stream);
