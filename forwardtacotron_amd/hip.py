@@ -1125,3 +1125,44 @@ def mask_rows(src: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
     dst = torch.empty_like(src)
     _lib.call('ft_mask_rows', _p(src), _p(lens), _p(dst), B, T, C, _stream())
     return dst
+
+
+# ---------------------------------------------------------------------------------------------------
+# audio front end (csrc/ft_audio.hip; the public interface is forwardtacotron_amd/audio.py)
+# ---------------------------------------------------------------------------------------------------
+def wav_trim_peak(wav: torch.Tensor, lens: torch.Tensor, Lmax: int, do_trim: bool, top_db: float, peak_mode: int,
+                  hop: int, alloc=torch.empty):
+    """wav [B, ld] fp32, lens [B] int64 (device) -> dict of per-item device tensors: trim_start, trim_end, wav_len,
+    mel_len (int64), peak (fp32), scaled (int32).  peak_mode: 1 always scale, 0 only if peak > 1, -1 never."""
+    _chk(wav, 'wav'); _chk(lens, 'lens', torch.int64)
+    B, ld = wav.shape
+    dev = wav.device
+    out = {k: alloc(B, dtype=torch.int64, device=dev) for k in ('trim_start', 'trim_end', 'wav_len', 'mel_len')}
+    out['peak'] = alloc(B, dtype=torch.float32, device=dev)
+    out['scaled'] = alloc(B, dtype=torch.int32, device=dev)
+    ws = workspace(_lib.query('ft_wav_trim_peak_workspace', B, Lmax), dev)
+    _lib.call('ft_wav_trim_peak', _p(wav), ld, _p(lens), B, Lmax, int(do_trim), float(top_db), int(peak_mode), hop,
+              _p(out['trim_start']), _p(out['trim_end']), _p(out['wav_len']), _p(out['mel_len']), _p(out['peak']),
+              _p(out['scaled']), _p(ws), _stream())
+    return out
+
+
+def wav_pack(wav: torch.Tensor, tp, stride: int, n_fft: int, reflect: bool, alloc=torch.empty):
+    """-> (packed [B * stride + n_fft], wav_out [B, ld]); tp = the dict wav_trim_peak returned"""
+    B, ld = wav.shape
+    packed = alloc(B * stride + n_fft, dtype=torch.float32, device=wav.device)
+    wav_out = alloc(B, ld, dtype=torch.float32, device=wav.device)
+    _lib.call('ft_wav_pack', _p(wav), ld, _p(tp['trim_start']), _p(tp['trim_end']), _p(tp['peak']), _p(tp['scaled']), B,
+              _p(packed), stride, n_fft, int(reflect), _p(wav_out), ld, _stream())
+    return packed, wav_out
+
+
+def mel_project(spec: torch.Tensor, Fp: int, rows_per_item: int, mel_len: torch.Tensor, w: torch.Tensor,
+                meta: torch.Tensor, n_mels: int, B: int, Tmax: int, log_clip: bool, pad_value: float,
+                alloc=torch.empty) -> torch.Tensor:
+    """split spectra [B * rows_per_item, 2 Fp] -> (log-)mel [B, n_mels, Tmax], pad_value at t >= mel_len[b]"""
+    _chk(spec, 'spec'); _chk(mel_len, 'mel_len', torch.int64); _chk(w, 'w'); _chk(meta, 'meta', torch.int32)
+    mel = alloc(B, n_mels, Tmax, dtype=torch.float32, device=spec.device)
+    _lib.call('ft_mel_project', _p(spec), spec.shape[1], Fp, rows_per_item, _p(mel_len), _p(w), _p(meta), w.numel(),
+              n_mels, B, Tmax, int(log_clip), float(pad_value), _p(mel), _stream())
+    return mel

@@ -556,6 +556,39 @@ int ft_gl_phase(const float* rebuilt, float* tprev, const float* S, float* proj,
                 int has_prev, void* stream);
 int ft_overlap_add(const float* frames, const float* inv_wss, float* ypad, int N, int n_fft, int hop, void* stream);
 
+/* ---- audio front end: trim, peak-normalise, wav -> mel (utils/dsp.py:62-78,96-104 DSP.wav_to_mel / normalize /
+ *      trim_silence ; preprocess.py:78-89, the audio half of Preprocessor._convert_file) ------------------------- */
+/* A ragged batch is wav [B, ld] fp32 (16-byte aligned rows, ld % 4 == 0) with len [B] int64 on the device (item b is
+ * wav[b, :len[b]], len <= Lmax <= ld; Lmax is the host's bound on the lengths and sizes every launch).
+ * wav_trim_peak (two launches): frame mean squares of 2048-sample frames every 512 samples, centred, zero padding,
+ * 1 + len / 512 frames; db = 10 log10(max(1e-10, ms)) - 10 log10(max(1e-10, max ms)); with do_trim, trim_start = 512 *
+ * (first frame with db > -top_db), trim_end = min(len, 512 * (last such frame + 1)), (0, 0) if there is none (an all-zero
+ * item is kept whole); without, (0, len).  wav_len = end - start, mel_len = 1 + wav_len / hop (0 for an empty item),
+ * peak = max |y| over [start, end), scaled = peak_norm > 0 || (peak_norm == 0 && peak > 1) (peak_norm < 0: never).
+ * An item's results depend on that item alone.
+ * ws: ft_wav_trim_peak_workspace(B, Lmax) bytes.
+ * wav_pack: packed [B * stride + n_fft] (stride % 4 == 0, stride >= ldw + n_fft; a multiple of hop makes the frames of
+ * all items rows of ONE GEMM with ldx = hop): packed[b * stride + n_fft / 2 + j] = z[j] for j < wav_len[b], where z =
+ * the trimmed item, (y / peak) * 0.95f in fp32 with an IEEE division if scaled[b] (an all-zero item with scaled[b] set
+ * gives 0 / 0 = NaN samples, as numpy does; the padding stays zero); around it zeros, or with reflect the
+ * signal mirrored about its first / last sample for n_fft / 2 samples on both sides (zeros where the item is too short
+ * to supply them); zeros up to the next item and in the n_fft tail.  wav_out [B, ldw] (ldw % 4 == 0, ldw >= every
+ * wav_len) = z, zero beyond wav_len[b].  n_fft % 8 == 0.
+ * mel_project: spec [rows, ld_spec] split spectra (Re at 0.., Im at Fp.., Fp % 4 == 0, ld_spec >= 2 Fp), item b's frame
+ * t at row b * rows_per_item + t -> mel [B, n_mels, Tmax]: mel[b, m, t] = sum over the bins of filter m, ascending, of
+ * w * |X| (fp32 fma chain), then log(max(., 1e-5)) if log_clip; pad_value for t >= mel_len[b].  The basis is sparse:
+ * meta [n_mels, 3] int32 = (first bin, number of bins, offset into w) per filter, w [nnz] fp32. */
+size_t ft_wav_trim_peak_workspace(int B, long Lmax);
+int ft_wav_trim_peak(const float* wav, long ld, const long* len, int B, long Lmax, int do_trim, float top_db,
+                     int peak_norm, int hop, long* trim_start, long* trim_end, long* wav_len, long* mel_len, float* peak,
+                     int* scaled, void* ws, void* stream);
+int ft_wav_pack(const float* wav, long ld, const long* trim_start, const long* trim_end, const float* peak,
+                const int* scaled, int B, float* packed, long stride, int n_fft, int reflect, float* wav_out, long ldw,
+                void* stream);
+int ft_mel_project(const float* spec, long ld_spec, int Fp, long rows_per_item, const long* mel_len, const float* w,
+                   const int* meta, int nnz, int n_mels, int B, int Tmax, int log_clip, float pad_value, float* mel,
+                   void* stream);
+
 /* ---- durations from a Tacotron attention (duration_extraction/duration_extractor.py:23-84 DurationExtractor ;
  *      duration_extraction_pipe.py:56-62,173-183 ; utils/metrics.py:4-31 attention_score, r = 1) ---------------- */
 /* One workgroup per item b; every length is read on the device.  Inputs: attn [B,Tm,Tx] fp32 (rows = mel frames),
