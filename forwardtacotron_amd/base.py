@@ -1,0 +1,220 @@
+"""What the four acoustic models (ForwardTacotron, MultiForwardTacotron, FastPitch, MultiFastPitch) share: the
+dependency-free helpers, the predictors' common front and tail, and AcousticModel -- the base class that carries the
+host-side plumbing (device check, predictor side stream and its fork / join, step counters, config / checkpoint
+constructors) and documents what trainer.TrainStep and parallel.FlatBuffers expect of a model.
+"""
+import os
+from pathlib import Path
+from typing import Any, Callable, Dict, Optional, Tuple, Union
+
+import torch
+import torch.nn as nn
+
+from . import hip as H
+from . import ops
+
+PAD_VALUE = -11.5129
+NUM_CHARS_DEFAULT = 135      # len(utils.text.symbols.phonemes), utils/text/symbols.py:21-23
+
+
+_seed_state = {'torch_seed': None, 'base': 0, 'n': 0}
+
+
+def _seed() -> int:
+    """Seed of one dropout site: host arithmetic only (no device sync, no tensor op -- a step draws ~170 of them).
+    The stream is re-based from torch's host RNG whenever torch.manual_seed() installs a different seed."""
+    st = _seed_state
+    s = torch.initial_seed()
+    if st['torch_seed'] != s:
+        st['torch_seed'] = s
+        st['base'] = int(torch.randint(0, 2 ** 62, (1,)).item())
+        st['n'] = 0
+    st['n'] += 1
+    return (st['base'] + 0x9E3779B97F4A7C15 * st['n']) & ((1 << 62) - 1)
+
+
+def _side_priority() -> int:
+    return -1 if os.environ.get('FT_PRED_PRIORITY', '1') == '1' else 0
+
+
+def _dropout(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
+    if not training or p <= 0.0:
+        return x
+    return ops.DropoutFn.apply(x, p, _seed())
+
+
+class LengthRegulator(nn.Module):
+    """common_layers.py:12-24"""
+
+    def forward(self, x: torch.Tensor, dur: torch.Tensor, pack_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """pack_lens: lengths the result will be packed with (see ops.LengthRegulateFn); None = reference signature"""
+        if not dur.is_contiguous() or dur.dtype != torch.float32:
+            raise H._lib.FtError('LengthRegulator: dur must be contiguous fp32 (it is clamped in place)')
+        return ops.LengthRegulateFn.apply(x, dur, pack_lens)
+
+
+def predictor_front(x: torch.Tensor, embedding: nn.Embedding, x_cond: Optional[torch.Tensor] = None,
+                    cond_embedding: Optional[nn.Embedding] = None,
+                    speaker_emb: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """What every series predictor starts with: token embedding ++ conditional embedding ++ speaker embedding repeated
+    over time (the last two optional) -> [B,T,C]"""
+    B, T = x.shape
+    e = ops.EmbeddingFn.apply(x, embedding.weight)
+    if x_cond is None and speaker_emb is None:
+        return e
+    c = ops.EmbeddingFn.apply(x_cond, cond_embedding.weight) if x_cond is not None else None
+    return ops.ConcatColsFn.apply(e, c, speaker_emb, B, T, False)
+
+
+def predictor_tail(x: torch.Tensor, lin: nn.Linear, alpha: float, x_tm_B: int = 0) -> torch.Tensor:
+    """What every series predictor ends with: Linear, then / alpha -> [B,T,out]; x_tm_B > 0: x is a time-major
+    [T,B,C] recurrence output (ops.LinearFn)"""
+    x = ops.LinearFn.apply(x, lin.weight, lin.bias, x_tm_B)
+    if alpha != 1.0:
+        x = ops.ScaleFn.apply(x, 1.0 / alpha)
+    return x
+
+
+class AcousticModel(nn.Module):
+    """Base of the four acoustic models.  It registers no parameter, buffer or submodule: every subclass builds its
+    modules and its `step` buffer itself, in the reference's order (which fixes the state_dict key order and the
+    constructor's RNG draws).  A subclass sets `config_key` and `recurrent`, has an `embedding`, a `padding_value` and
+    a `step` buffer, and runs its predictors through _fork_predictors / _join_predictors.
+
+    The attributes below are the contract with trainer.TrainStep (which reads and sets them directly) and
+    parallel.FlatBuffers; the values here are the defaults of a model that does not care."""
+
+    config_key: str = ''            # the model's section of a config: config[config_key]['model']
+    recurrent: bool = False         # the trunk has recurrences and BatchNorms (the two Tacotron variants)
+
+    # 'fp32' (the reference's arithmetic; parity bars) or 'bf16' (BASELINE configs[2]; the FastPitch variants): matmul
+    # operands rounded to bf16, fp32 accumulation; LayerNorm / softmax statistics / losses / optimizer stay fp32.
+    # forward() / generate() of the FastPitch variants run under it; TrainStep extends it over backward.
+    matmul_dtype: str = 'fp32'
+    # predictor branches share no graph node with the trunk in training: TrainStep may run their backward as a stage of
+    # its own (or, through predictor_hook, inside the forward)
+    independent_predictors: bool = True
+    # token-side row count (incl. the conv bank's extra row), set per forward by the recurrent models: TrainStep keeps
+    # weight gradients of operands this short on the main stream (ops.GradSink.inline_rows)
+    wgrad_inline_rows: int = 0
+    wgrad_defer: bool = False       # recurrences ahead (ops.GradSink.defer); set per forward by the recurrent models
+    # set by TrainStep around one forward: cut the graph below the decoder LSTM (model.regulate_and_decode), which
+    # leaves (tensor below the cut, its detached twin above it) in _cut for the trainer's three-stage backward
+    stage_backward: bool = False
+    _cut: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+    # set by TrainStep around one forward: called with the predictors' outputs on their stream, right behind their
+    # forward (the predictors' losses + backward)
+    predictor_hook: Optional[Callable[[Dict[str, torch.Tensor]], None]] = None
+    # flat int64 storage of every BatchNorm's num_batches_tracked (_bump_batchnorm_counters); parallel.FlatBuffers
+    # points it at its own flat buffer
+    _nbt_flat: Optional[torch.Tensor] = None
+
+    def __repr__(self):
+        return f'{type(self).__name__}, num params: {sum(p.numel() for p in self.parameters())}'
+
+    def _require_device(self, t: torch.Tensor) -> None:
+        if not t.is_cuda or not self.embedding.weight.is_cuda:
+            raise H._lib.FtError(f'forwardtacotron_amd.{type(self).__name__} runs on an MI355X (HIP) device only: '
+                                 'move the model and the batch with .cuda(); there is no CPU fallback')
+
+    def _bump_batchnorm_counters(self) -> None:
+        """num_batches_tracked += 1 for every BatchNorm1d, as one op on shared int64 storage."""
+        bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm1d)]
+        f = self._nbt_flat
+        ok = f is not None and f.device == bns[0].num_batches_tracked.device
+        if ok:
+            for i in (0, len(bns) - 1):
+                ok = ok and bns[i].num_batches_tracked.data_ptr() == f.data_ptr() + 8 * i
+        if not ok:
+            f = torch.stack([b.num_batches_tracked.detach().reshape(()) for b in bns]).contiguous()
+            for i, b in enumerate(bns):
+                b._buffers['num_batches_tracked'] = f[i]
+            self._nbt_flat = f
+        f += 1
+
+    def _begin_forward(self, x: torch.Tensor) -> None:
+        """head of every forward(): device check, the trainer's weight-gradient hints, the training counters"""
+        self._require_device(x)
+        if self.recurrent:
+            self.wgrad_inline_rows = x.shape[0] * (x.shape[1] + 1)
+            self.wgrad_defer = True
+        if self.training:
+            self.step += 1
+            if self.recurrent:          # the models with BatchNorms
+                self._bump_batchnorm_counters()
+
+    # -- the predictors' side stream ------------------------------------------------------------------------------
+    def _side_stream(self, device) -> 'torch.cuda.Stream':
+        key = torch.device(device).index or 0
+        if not hasattr(self, '_streams'):
+            self._streams = {}
+        if key not in self._streams:
+            # high priority like the trainer's main stream: the predictors' kernels are small and many, behind the trunk's
+            # 1000-workgroup GEMMs in a default-priority queue each of them waits for a free CU (0.25 ms of the step)
+            self._streams[key] = torch.cuda.Stream(device=device, priority=_side_priority())
+        return self._streams[key]
+
+    def _fork_predictors(self, device, run: Callable[[], Dict[str, torch.Tensor]], overlap: bool = True):
+        """Runs the predictors (`run` -> their output dict) on the side stream, behind everything the current stream has
+        been given so far, then predictor_hook on the same stream.  overlap=False: on the current stream itself.
+        -> (main, side, outputs) for _join_predictors"""
+        main = torch.cuda.current_stream()
+        side = self._side_stream(device) if overlap else main
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            pred = run()
+            if self.predictor_hook is not None:
+                self.predictor_hook(pred)
+        return main, side, pred
+
+    def _join_predictors(self, fork) -> Dict[str, torch.Tensor]:
+        """the fork's main stream waits for the predictors and takes their outputs over"""
+        main, side, pred = fork
+        main.wait_stream(side)
+        if self.recurrent:
+            H.rnn_note_join(main, side)
+        for t in pred.values():
+            t.record_stream(main)
+        return pred
+
+    def _generate_fork(self, x: torch.Tensor, run: Callable[[], Dict[str, torch.Tensor]]):
+        """generate() of the recurrent models: the predictors only meet the trunk behind the prenet, so they run on the
+        side stream while the main stream does embedding + prenet CBHG (its 128-step GRU is latency-bound: a single
+        utterance spends 84 % of its time in recurrences), joined where their outputs are needed.  FT_GEN_OVERLAP=0: no
+        overlap.  -> (outputs, late_inputs for _trunk); after the trunk outputs['dur'] is the tensor the trunk consumed"""
+        fork = self._fork_predictors(x.device, run, overlap=os.environ.get('FT_GEN_OVERLAP', '1') == '1')
+        pred, B = fork[2], x.shape[0]
+
+        def late_inputs():
+            self._join_predictors(fork)
+            if torch.sum(pred['dur'].long()) <= 0:
+                torch.fill_(pred['dur'], value=2.)
+            pred['dur'] = pred['dur'].contiguous()
+            return pred['dur'], pred['pitch'].reshape(B, -1).contiguous(), pred['energy'].reshape(B, -1).contiguous()
+
+        return pred, late_inputs
+
+    # -------------------------------------------------------------------------------------------------------------
+    def get_step(self) -> int:
+        return self.step.data.item()
+
+    def pad(self, x: torch.Tensor, max_len: int) -> torch.Tensor:
+        """forward_tacotron.py:236-239 on a [B,C,T] tensor (kept for API parity; forward() fuses it)."""
+        x = x[:, :, :max_len]
+        return torch.nn.functional.pad(x, [0, max_len - x.size(2), 0, 0], 'constant', self.padding_value)
+
+    _pad = pad      # the name in forward_tacotron.py
+
+    @classmethod
+    def from_config(cls, config: Dict[str, Any]):
+        model_config = config[cls.config_key]['model']
+        model_config['num_chars'] = config.get('num_chars', NUM_CHARS_DEFAULT)   # reference: len(phonemes)
+        model_config['n_mels'] = config['dsp']['num_mels']
+        return cls(**model_config)
+
+    @classmethod
+    def from_checkpoint(cls, path: Union[Path, str]):
+        checkpoint = torch.load(path, map_location=torch.device('cpu'), weights_only=True)
+        model = cls.from_config(checkpoint['config'])
+        model.load_state_dict(checkpoint['model'])
+        return model

@@ -10,8 +10,7 @@ import copy
 import functools
 import math
 import os
-from pathlib import Path
-from typing import Any, Callable, Dict, Optional, Union
+from typing import Callable, Dict, Optional
 
 import torch
 import torch.nn as nn
@@ -20,7 +19,7 @@ from torch.autograd import Function
 from . import _lib
 from . import hip as H
 from . import ops
-from .model import LengthRegulator, NUM_CHARS_DEFAULT, PAD_VALUE, _dropout, _seed
+from .base import AcousticModel, LengthRegulator, PAD_VALUE, _dropout, _seed, predictor_front, predictor_tail
 from .ops import _c, _emit, _emit_multi
 
 _F4 = 4
@@ -50,7 +49,7 @@ def precision_scoped(fn):
     """runs a model method under the model's `matmul_dtype` ('fp32' default, 'bf16' = BASELINE configs[2])"""
     @functools.wraps(fn)
     def wrapped(self, *a, **k):
-        with H.gemm_precision(getattr(self, 'matmul_dtype', 'fp32')):
+        with H.gemm_precision(self.matmul_dtype):
             return fn(self, *a, **k)
     return wrapped
 
@@ -639,16 +638,18 @@ class SeriesPredictor(nn.Module):
         self.lin = nn.Linear(d_model, 1)
 
     def forward(self, x: torch.Tensor, src_pad_mask: Optional[torch.Tensor] = None, alpha: float = 1.0):
-        x = ops.EmbeddingFn.apply(x, self.embedding.weight)
-        x = self.transformer(x, src_pad_mask=src_pad_mask)
-        x = ops.LinearFn.apply(x, self.lin.weight, self.lin.bias)
-        if alpha != 1.0:
-            x = ops.ScaleFn.apply(x, 1.0 / alpha)
-        return x
+        return transformer_predict(self, predictor_front(x, self.embedding), src_pad_mask, alpha)
 
 
-class FastPitch(nn.Module):
-    """Drop-in for models/fast_pitch.py:44-235."""
+def transformer_predict(pred: nn.Module, x: torch.Tensor, src_pad_mask: Optional[torch.Tensor], alpha: float):
+    """ForwardTransformer -> Linear (/ alpha) of the transformer series predictors, on the output of
+    base.predictor_front"""
+    return predictor_tail(pred.transformer(x, src_pad_mask=src_pad_mask), pred.lin, alpha)
+
+
+class FastPitch(AcousticModel):
+    """Drop-in for models/fast_pitch.py:44-235.  `matmul_dtype` (base.AcousticModel) selects fp32 or bf16 matmuls."""
+    config_key = 'fast_pitch'
 
     def __init__(self, num_chars: int,
                  durpred_dropout: float, durpred_d_model: int, durpred_n_heads: int, durpred_layers: int,
@@ -662,14 +663,7 @@ class FastPitch(nn.Module):
                  n_mels: int, padding_value=PAD_VALUE):
         super().__init__()
         self.padding_value = padding_value
-        # 'fp32' (the reference's arithmetic; parity bars) or 'bf16' (BASELINE configs[2]): matmul operands rounded to
-        # bf16, fp32 accumulation; LayerNorm / softmax statistics / losses / optimizer stay fp32.  forward() / generate()
-        # run under it; trainer.TrainStep extends it over backward (hip.gemm_precision for a hand-rolled backward).
-        self.matmul_dtype = 'fp32'
         self.lr = LengthRegulator()
-        # predictor branches share no graph node with the trunk in training (trainer.TrainStep may run their backward as a
-        # stage of its own)
-        self.independent_predictors = True
         self.dur_pred = SeriesPredictor(num_chars=num_chars, d_model=durpred_d_model, n_heads=durpred_n_heads,
                                         layers=durpred_layers, d_fft=durpred_d_fft, conv1_kernel=conv1_kernel,
                                         conv2_kernel=conv2_kernel, dropout=durpred_dropout)
@@ -693,13 +687,6 @@ class FastPitch(nn.Module):
         self.pitch_proj = nn.Conv1d(1, d_model, kernel_size=3, padding=1)
         self.energy_proj = nn.Conv1d(1, d_model, kernel_size=3, padding=1)
 
-    def __repr__(self):
-        return f'FastPitch, num params: {sum(p.numel() for p in self.parameters())}'
-
-    def _require_device(self, t: torch.Tensor) -> None:
-        if not t.is_cuda or not self.embedding.weight.is_cuda:
-            raise _lib.FtError('FastPitch runs on an MI355X (HIP) device only; there is no CPU fallback')
-
     def _mel(self, x_idx, tok_mask, dur, pitch, energy, frame_lens: Optional[torch.Tensor]):
         x = ops.EmbeddingFn.apply(x_idx, self.embedding.weight)
         x = self.prenet(x, src_pad_mask=tok_mask)
@@ -720,29 +707,22 @@ class FastPitch(nn.Module):
         mel = batch['mel']
         dur = batch['dur']
         mel_lens = batch['mel_len']
-        self._require_device(x)
-        if self.training:
-            self.step += 1
+        self._begin_forward(x)
         len_mask = x == 0                                                       # make_token_len_mask
-        # the three token-side predictors only feed the losses in training (fast_pitch.py:129-131 vs :133-150): side HIP
-        # stream, concurrently with the frame-side trunk (autograd replays their backward on the same stream)
-        main = torch.cuda.current_stream()
-        side = self._side_stream(x.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
+
+        def predict():      # in the order that fixes the dropout seed sequence: dur, pitch, energy
             dur_hat = self.dur_pred(x, src_pad_mask=len_mask).squeeze(-1)
             pitch_hat = self.pitch_pred(x, src_pad_mask=len_mask).transpose(1, 2)
             energy_hat = self.energy_pred(x, src_pad_mask=len_mask).transpose(1, 2)
-            hook = getattr(self, 'predictor_hook', None)   # trainer.TrainStep: the predictors' losses + backward, right here
-            if hook is not None:
-                hook({'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat})
+            return {'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat}
+
+        # the three token-side predictors only feed the losses in training (fast_pitch.py:129-131 vs :133-150): side HIP
+        # stream, concurrently with the frame-side trunk (autograd replays their backward on the same stream)
+        fork = self._fork_predictors(x.device, predict)
         mel_cl = self._mel(x, len_mask, dur, batch['pitch'], batch['energy'],
                            mel_lens.to(device=x.device, dtype=torch.long))
         x_mel = ops.TransposePadFn.apply(mel_cl, mel.size(2), self.padding_value)
-        main.wait_stream(side)
-        for t in (dur_hat, pitch_hat, energy_hat):
-            t.record_stream(main)
-        return {'mel': x_mel, 'mel_post': x_mel, 'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat}
+        return {'mel': x_mel, 'mel_post': x_mel, **self._join_predictors(fork)}
 
     @precision_scoped
     def generate(self, x: torch.Tensor, alpha=1.0,
@@ -763,33 +743,3 @@ class FastPitch(nn.Module):
                                energy_hat.reshape(B, -1).contiguous(), None)
             m = H.transpose_pad_fwd(mel_cl, mel_cl.shape[1], 0.0)
             return {'mel': m, 'mel_post': m, 'dur': dur_in, 'pitch': pitch_hat, 'energy': energy_hat}
-
-    def pad(self, x: torch.Tensor, max_len: int) -> torch.Tensor:
-        x = x[:, :, :max_len]
-        return torch.nn.functional.pad(x, [0, max_len - x.size(2), 0, 0], 'constant', self.padding_value)
-
-    def _side_stream(self, device) -> 'torch.cuda.Stream':
-        key = torch.device(device).index or 0
-        if not hasattr(self, '_streams'):
-            self._streams = {}
-        if key not in self._streams:
-            from .model import _side_priority
-            self._streams[key] = torch.cuda.Stream(device=device, priority=_side_priority())
-        return self._streams[key]
-
-    def get_step(self) -> int:
-        return self.step.data.item()
-
-    @classmethod
-    def from_config(cls, config: Dict[str, Any]) -> 'FastPitch':
-        model_config = config['fast_pitch']['model']
-        model_config['num_chars'] = config.get('num_chars', NUM_CHARS_DEFAULT)
-        model_config['n_mels'] = config['dsp']['num_mels']
-        return FastPitch(**model_config)
-
-    @classmethod
-    def from_checkpoint(cls, path: Union[Path, str]) -> 'FastPitch':
-        checkpoint = torch.load(path, map_location=torch.device('cpu'), weights_only=True)
-        model = FastPitch.from_config(checkpoint['config'])
-        model.load_state_dict(checkpoint['model'])
-        return model

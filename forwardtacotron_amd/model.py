@@ -9,44 +9,15 @@ CPU / eager fallback: the model refuses to run if its tensors are not on a HIP d
 """
 import math
 import os
-from pathlib import Path
-from typing import Any, Callable, Dict, List, Optional, Union
+from typing import Callable, Dict, List, Optional
 
 import torch
 import torch.nn as nn
 
 from . import hip as H
 from . import ops
-
-PAD_VALUE = -11.5129
-NUM_CHARS_DEFAULT = 135      # len(utils.text.symbols.phonemes), utils/text/symbols.py:21-23
-
-
-_seed_state = {'torch_seed': None, 'base': 0, 'n': 0}
-
-
-def _seed() -> int:
-    """Seed of one dropout site: host arithmetic only (no device sync, no tensor op -- a step draws ~170 of them).
-    The stream is re-based from torch's host RNG whenever torch.manual_seed() installs a different seed."""
-    st = _seed_state
-    s = torch.initial_seed()
-    if st['torch_seed'] != s:
-        st['torch_seed'] = s
-        st['base'] = int(torch.randint(0, 2 ** 62, (1,)).item())
-        st['n'] = 0
-    st['n'] += 1
-    return (st['base'] + 0x9E3779B97F4A7C15 * st['n']) & ((1 << 62) - 1)
-
-
-def _side_priority() -> int:
-    import os
-    return -1 if os.environ.get('FT_PRED_PRIORITY', '1') == '1' else 0
-
-
-def _dropout(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
-    if not training or p <= 0.0:
-        return x
-    return ops.DropoutFn.apply(x, p, _seed())
+from .base import (AcousticModel, LengthRegulator, NUM_CHARS_DEFAULT, PAD_VALUE, _dropout, _seed,  # noqa: F401
+                   _side_priority, predictor_front, predictor_tail)                                # (re-exported)
 
 
 class _RNNParams(nn.Module):
@@ -106,7 +77,7 @@ class LSTM(_RNNParams):
 def regulate_and_decode(model, x: torch.Tensor, dur: torch.Tensor, mel_lens: Optional[torch.Tensor]) -> torch.Tensor:
     """LengthRegulator + decoder LSTM of the ForwardTacotron variants (forward_tacotron.py:145-152), and the place where
     trainer.TrainStep's staged backward cuts the graph.  FT_LR_LSTM_FUSED=0 keeps the two as separate nodes."""
-    staged = model.training and torch.is_grad_enabled() and getattr(model, 'stage_backward', False)
+    staged = model.training and torch.is_grad_enabled() and model.stage_backward
     fused = os.environ.get('FT_LR_LSTM_FUSED', '1') != '0'
     if not fused:
         x = model.lr(x, dur, mel_lens)      # at max(mel_lens) frames, the length pad_packed_sequence returns (:147-152)
@@ -119,16 +90,6 @@ def regulate_and_decode(model, x: torch.Tensor, dur: torch.Tensor, mel_lens: Opt
     if fused:
         return model.lstm.forward_regulated(x, dur, mel_lens, model.padding_value)
     return model.lstm(x, mel_lens, model.padding_value)
-
-
-class LengthRegulator(nn.Module):
-    """common_layers.py:12-24"""
-
-    def forward(self, x: torch.Tensor, dur: torch.Tensor, pack_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """pack_lens: lengths the result will be packed with (see ops.LengthRegulateFn); None = reference signature"""
-        if not dur.is_contiguous() or dur.dtype != torch.float32:
-            raise H._lib.FtError('LengthRegulator: dur must be contiguous fp32 (it is clamped in place)')
-        return ops.LengthRegulateFn.apply(x, dur, pack_lens)
 
 
 class HighwayNetwork(nn.Module):
@@ -267,20 +228,24 @@ class SeriesPredictor(nn.Module):
         self.dropout = dropout
 
     def forward(self, x: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
-        x = ops.EmbeddingFn.apply(x, self.embedding.weight)
-        for conv in self.convs:
-            x = conv(x)
-            x = _dropout(x, self.dropout, self.training)
-        B = x.shape[0]
-        x = self.rnn(x, time_major_out=True)
-        x = ops.LinearFn.apply(x, self.lin.weight, self.lin.bias, B)       # [T,B,2H] -> [B,T,1]
-        if alpha != 1.0:
-            x = ops.ScaleFn.apply(x, 1.0 / alpha)
-        return x
+        return conv_gru_predict(self, predictor_front(x, self.embedding), alpha)
 
 
-class ForwardTacotron(nn.Module):
+def conv_gru_predict(pred: nn.Module, x: torch.Tensor, alpha: float) -> torch.Tensor:
+    """3 x (BatchNormConv, dropout) -> biGRU -> Linear (/ alpha) of the conv-GRU series predictors, on the output of
+    base.predictor_front"""
+    for conv in pred.convs:
+        x = conv(x)
+        x = _dropout(x, pred.dropout, pred.training)
+    B = x.shape[0]
+    x = pred.rnn(x, time_major_out=True)
+    return predictor_tail(x, pred.lin, alpha, B)                           # [T,B,2H] -> [B,T,out]
+
+
+class ForwardTacotron(AcousticModel):
     """Drop-in for models/forward_tacotron.py:42-254."""
+    config_key = 'forward_tacotron'
+    recurrent = True
 
     def __init__(self,
                  embed_dims: int, series_embed_dims: int, num_chars: int,
@@ -296,9 +261,6 @@ class ForwardTacotron(nn.Module):
         self.padding_value = padding_value
         self.embedding = nn.Embedding(num_chars, embed_dims)
         self.lr = LengthRegulator()
-        # predictor branches share no graph node with the trunk in training (trainer.TrainStep may run their backward as a
-        # stage of its own)
-        self.independent_predictors = True
         self.dur_pred = SeriesPredictor(num_chars=num_chars, emb_dim=series_embed_dims,
                                         conv_dims=durpred_conv_dims, rnn_dims=durpred_rnn_dims,
                                         dropout=durpred_dropout)
@@ -322,32 +284,6 @@ class ForwardTacotron(nn.Module):
         self.energy_strength = energy_strength
         self.pitch_proj = nn.Conv1d(1, 2 * prenet_dims, kernel_size=3, padding=1)
         self.energy_proj = nn.Conv1d(1, 2 * prenet_dims, kernel_size=3, padding=1)
-        self._nbt_flat = None
-
-    def __repr__(self):
-        num_params = sum(p.numel() for p in self.parameters())
-        return f'ForwardTacotron, num params: {num_params}'
-
-    # ------------------------------------------------------------------------------------------------
-    def _require_device(self, t: torch.Tensor) -> None:
-        if not t.is_cuda or not self.embedding.weight.is_cuda:
-            raise H._lib.FtError('forwardtacotron_amd.ForwardTacotron runs on an MI355X (HIP) device only: '
-                                 'move the model and the batch with .cuda(); there is no CPU fallback')
-
-    def _bump_batchnorm_counters(self) -> None:
-        """num_batches_tracked += 1 for every BatchNorm1d, as one op on shared int64 storage."""
-        bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm1d)]
-        f = self._nbt_flat
-        ok = f is not None and f.device == bns[0].num_batches_tracked.device
-        if ok:
-            for i in (0, len(bns) - 1):
-                ok = ok and bns[i].num_batches_tracked.data_ptr() == f.data_ptr() + 8 * i
-        if not ok:
-            f = torch.stack([b.num_batches_tracked.detach().reshape(()) for b in bns]).contiguous()
-            for i, b in enumerate(bns):
-                b._buffers['num_batches_tracked'] = f[i]
-            self._nbt_flat = f
-        f += 1
 
     def _trunk(self, x: torch.Tensor, dur, pitch, energy, mel_lens: Optional[torch.Tensor], late_inputs=None):
         """late_inputs (inference): a callable that delivers (dur, pitch, energy) once the prenet has been enqueued -- the
@@ -366,57 +302,32 @@ class ForwardTacotron(nn.Module):
         post = ops.LinearFn.apply(post, self.post_proj.weight, None, B)     # -> [B,T,n_mels]
         return mel, post
 
+    def _predict(self, x: torch.Tensor, alpha: float = 1.0, pitch_function=lambda p: p, energy_function=lambda e: e):
+        """the three predictors, in the order that fixes the dropout seed sequence: dur, pitch, energy"""
+        dur_hat = self.dur_pred(x, alpha=alpha).squeeze(-1)
+        pitch_hat = pitch_function(self.pitch_pred(x).transpose(1, 2))
+        energy_hat = energy_function(self.energy_pred(x).transpose(1, 2))
+        return {'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat}
+
     def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         x = batch['x']
         mel = batch['mel']
         dur = batch['dur']
         mel_lens = batch['mel_len']
-        self._require_device(x)
         pitch = batch['pitch']               # [B,Tx]  (the reference unsqueezes to [B,1,Tx] for its Conv1d)
         energy = batch['energy']
-
-        # token-side row count (incl. the conv bank's extra row): trainer.TrainStep keeps weight gradients of
-        # operands this short on the main stream (ops.GradSink.inline_rows)
-        self.wgrad_inline_rows = x.shape[0] * (x.shape[1] + 1)
-        self.wgrad_defer = True          # recurrences ahead: ops.GradSink.defer
-        if self.training:
-            self.step += 1
-            self._bump_batchnorm_counters()
+        self._begin_forward(x)
 
         # The three predictors are independent of the trunk (forward_tacotron.py:129-131 vs :133-159) and
         # their 128-step recurrences are latency-bound, so they run on a side HIP stream concurrently with the
         # trunk; autograd replays each backward node on the stream of its forward, so the overlap also holds
         # in backward.
-        main = torch.cuda.current_stream()
-        side = self._side_stream(x.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            dur_hat = self.dur_pred(x).squeeze(-1)
-            pitch_hat = self.pitch_pred(x).transpose(1, 2)
-            energy_hat = self.energy_pred(x).transpose(1, 2)
-            hook = getattr(self, 'predictor_hook', None)   # trainer.TrainStep: the predictors' losses + backward, right here
-            if hook is not None:
-                hook({'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat})
-
+        fork = self._fork_predictors(x.device, lambda: self._predict(x))
         mel_cl, post_cl = self._trunk(x, dur, pitch, energy, mel_lens.to(device=x.device, dtype=torch.long))
         Tout = mel.size(2)
         x_post = ops.TransposePadFn.apply(post_cl, Tout, self.padding_value)
         x_mel = ops.TransposePadFn.apply(mel_cl, Tout, self.padding_value)
-        main.wait_stream(side)
-        H.rnn_note_join(main, side)
-        for t in (dur_hat, pitch_hat, energy_hat):
-            t.record_stream(main)
-        return {'mel': x_mel, 'mel_post': x_post, 'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat}
-
-    def _side_stream(self, device) -> 'torch.cuda.Stream':
-        key = torch.device(device).index or 0
-        if not hasattr(self, '_streams'):
-            self._streams = {}
-        if key not in self._streams:
-            # high priority like the trainer's main stream: the predictors' kernels are small and many, behind the trunk's
-            # 1000-workgroup GEMMs in a default-priority queue each of them waits for a free CU (0.25 ms of the step)
-            self._streams[key] = torch.cuda.Stream(device=device, priority=_side_priority())
-        return self._streams[key]
+        return {'mel': x_mel, 'mel_post': x_post, **self._join_predictors(fork)}
 
     def generate(self, x: torch.Tensor, alpha=1.0,
                  pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda x: x,
@@ -439,34 +350,11 @@ class ForwardTacotron(nn.Module):
 
     def _generate(self, x, alpha, pitch_function, energy_function):
         self._require_device(x)
-        # The predictors only meet the trunk behind the prenet (forward_tacotron.py:168-189 runs them first, then the
-        # prenet): they run on the side stream while the main stream does embedding + prenet CBHG (its 128-step GRU is
-        # latency-bound: a single utterance spends 84 % of its time in recurrences), joined where their outputs are needed.
-        import os
-        main = torch.cuda.current_stream()
-        side = self._side_stream(x.device) if os.environ.get('FT_GEN_OVERLAP', '1') == '1' else main
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            dur_hat = self.dur_pred(x, alpha=alpha).squeeze(2)
-            pitch_hat = pitch_function(self.pitch_pred(x).transpose(1, 2))
-            energy_hat = energy_function(self.energy_pred(x).transpose(1, 2))
-        got = {}
-
-        def late_inputs():
-            main.wait_stream(side)
-            H.rnn_note_join(main, side)
-            for t in (dur_hat, pitch_hat, energy_hat):
-                t.record_stream(main)
-            if torch.sum(dur_hat.long()) <= 0:
-                torch.fill_(dur_hat, value=2.)
-            got['dur'] = dur_hat.contiguous()
-            return (got['dur'], pitch_hat.reshape(x.shape[0], -1).contiguous(),
-                    energy_hat.reshape(x.shape[0], -1).contiguous())
-
+        # forward_tacotron.py:168-189 runs the predictors first, then the prenet; here they run beside it
+        pred, late_inputs = self._generate_fork(x, lambda: self._predict(x, alpha, pitch_function, energy_function))
         mel_cl, post_cl = self._trunk(x, None, None, None, None, late_inputs=late_inputs)
         T = mel_cl.shape[1]
-        return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0),
-                'dur': got['dur'], 'pitch': pitch_hat, 'energy': energy_hat}
+        return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0), **pred}
 
     def _generate_mel(self, x: torch.Tensor, dur_hat: torch.Tensor, pitch_hat: torch.Tensor,
                       energy_hat: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -479,28 +367,6 @@ class ForwardTacotron(nn.Module):
         T = mel_cl.shape[1]
         return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0),
                 'dur': dur_in, 'pitch': pitch_hat, 'energy': energy_hat}
-
-    def get_step(self) -> int:
-        return self.step.data.item()
-
-    def _pad(self, x: torch.Tensor, max_len: int) -> torch.Tensor:
-        """forward_tacotron.py:236-239 on a [B,C,T] tensor (kept for API parity; forward() fuses it)."""
-        x = x[:, :, :max_len]
-        return torch.nn.functional.pad(x, [0, max_len - x.size(2), 0, 0], 'constant', self.padding_value)
-
-    @classmethod
-    def from_config(cls, config: Dict[str, Any]) -> 'ForwardTacotron':
-        model_config = config['forward_tacotron']['model']
-        model_config['num_chars'] = config.get('num_chars', NUM_CHARS_DEFAULT)   # reference: len(phonemes)
-        model_config['n_mels'] = config['dsp']['num_mels']
-        return ForwardTacotron(**model_config)
-
-    @classmethod
-    def from_checkpoint(cls, path: Union[Path, str]) -> 'ForwardTacotron':
-        checkpoint = torch.load(path, map_location=torch.device('cpu'), weights_only=True)
-        model = ForwardTacotron.from_config(checkpoint['config'])
-        model.load_state_dict(checkpoint['model'])
-        return model
 
 
 from . import export as _export  # noqa: E402,F401  (registers torch.ops.fwdtaco.generate_jit for torch.jit.load)

@@ -2,71 +2,64 @@
 constructor kwargs, batch-dict forward()/generate() and state_dict.  Composition of the FastPitch transformer blocks
 (forwardtacotron_amd.fastpitch) with the speaker / pitch_cond column concat of the multispeaker ForwardTacotron.
 """
-from pathlib import Path
-from typing import Any, Callable, Dict, Optional, Union
+from typing import Callable, Dict, Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib
 from . import hip as H
 from . import ops
-from .fastpitch import ForwardTransformer, precision_scoped
-from .model import LengthRegulator, NUM_CHARS_DEFAULT, PAD_VALUE
+from .base import AcousticModel, LengthRegulator, PAD_VALUE, predictor_front
+from .fastpitch import ForwardTransformer, precision_scoped, transformer_predict
 
 
-class SeriesPredictor(nn.Module):
+class _SpeakerSeriesPredictor(nn.Module):
+    """embedding ++ [conditional embedding ++] speaker embedding -> ForwardTransformer -> Linear(out_dim): the two
+    predictors below, which differ in the conditional embedding only"""
+
+    def __init__(self, num_chars: int, d_model: int, n_heads: int, d_fft: int, layers: int, conv1_kernel: int,
+                 conv2_kernel: int, speaker_emb_dims: int, dropout, out_dim: int = 1, cond_emb_size: int = 0,
+                 cond_emb_dims: int = 0):
+        super().__init__()
+        self.embedding = nn.Embedding(num_chars, d_model)
+        if cond_emb_size:
+            self.conditional_embedding = nn.Embedding(cond_emb_size, cond_emb_dims)
+        wide = d_model + speaker_emb_dims + cond_emb_dims
+        self.transformer = ForwardTransformer(heads=n_heads, dropout=dropout, d_model=wide, d_fft=d_fft,
+                                              conv1_kernel=conv1_kernel, conv2_kernel=conv2_kernel, layers=layers)
+        self.lin = nn.Linear(wide, out_dim)
+
+
+class SeriesPredictor(_SpeakerSeriesPredictor):
     """multi_fast_pitch.py:14-49: embedding ++ speaker embedding -> ForwardTransformer -> Linear(out_dim)."""
 
     def __init__(self, num_chars: int, d_model: int, n_heads: int, d_fft: int, layers: int, conv1_kernel: int,
                  conv2_kernel: int, speaker_emb_dims: int, dropout=0.1, out_dim: int = 1):
-        super().__init__()
-        self.embedding = nn.Embedding(num_chars, d_model)
-        self.transformer = ForwardTransformer(heads=n_heads, dropout=dropout, d_model=d_model + speaker_emb_dims,
-                                              d_fft=d_fft, conv1_kernel=conv1_kernel, conv2_kernel=conv2_kernel,
-                                              layers=layers)
-        self.lin = nn.Linear(d_model + speaker_emb_dims, out_dim)
+        super().__init__(num_chars, d_model, n_heads, d_fft, layers, conv1_kernel, conv2_kernel, speaker_emb_dims,
+                         dropout, out_dim)
 
     def forward(self, x: torch.Tensor, speaker_emb: torch.Tensor, src_pad_mask: Optional[torch.Tensor] = None,
                 alpha: float = 1.0) -> torch.Tensor:
-        B, T = x.shape
-        x = ops.EmbeddingFn.apply(x, self.embedding.weight)
-        x = ops.ConcatColsFn.apply(x, None, speaker_emb, B, T, False)
-        x = self.transformer(x, src_pad_mask=src_pad_mask)
-        x = ops.LinearFn.apply(x, self.lin.weight, self.lin.bias)
-        if alpha != 1.0:
-            x = ops.ScaleFn.apply(x, 1.0 / alpha)
-        return x
+        return transformer_predict(self, predictor_front(x, self.embedding, speaker_emb=speaker_emb), src_pad_mask, alpha)
 
 
-class ConditionalSeriesPredictor(nn.Module):
+class ConditionalSeriesPredictor(_SpeakerSeriesPredictor):
     """multi_fast_pitch.py:52-90: embedding ++ conditional embedding ++ speaker embedding -> ..."""
 
     def __init__(self, num_chars: int, d_model: int, n_heads: int, d_fft: int, layers: int, conv1_kernel: int,
                  conv2_kernel: int, speaker_emb_dims: int, cond_emb_size: int = 4, cond_emb_dims: int = 8, dropout=0.1):
-        super().__init__()
-        self.embedding = nn.Embedding(num_chars, d_model)
-        self.conditional_embedding = nn.Embedding(cond_emb_size, cond_emb_dims)
-        self.transformer = ForwardTransformer(heads=n_heads, dropout=dropout,
-                                              d_model=d_model + speaker_emb_dims + cond_emb_dims, d_fft=d_fft,
-                                              conv1_kernel=conv1_kernel, conv2_kernel=conv2_kernel, layers=layers)
-        self.lin = nn.Linear(d_model + speaker_emb_dims + cond_emb_dims, 1)
+        super().__init__(num_chars, d_model, n_heads, d_fft, layers, conv1_kernel, conv2_kernel, speaker_emb_dims,
+                         dropout, cond_emb_size=cond_emb_size, cond_emb_dims=cond_emb_dims)
 
     def forward(self, x: torch.Tensor, x_cond: torch.Tensor, speaker_emb: torch.Tensor,
                 src_pad_mask: Optional[torch.Tensor] = None, alpha: float = 1.0) -> torch.Tensor:
-        B, T = x.shape
-        e = ops.EmbeddingFn.apply(x, self.embedding.weight)
-        c = ops.EmbeddingFn.apply(x_cond, self.conditional_embedding.weight)
-        x = ops.ConcatColsFn.apply(e, c, speaker_emb, B, T, False)
-        x = self.transformer(x, src_pad_mask=src_pad_mask)
-        x = ops.LinearFn.apply(x, self.lin.weight, self.lin.bias)
-        if alpha != 1.0:
-            x = ops.ScaleFn.apply(x, 1.0 / alpha)
-        return x
+        x = predictor_front(x, self.embedding, x_cond, self.conditional_embedding, speaker_emb)
+        return transformer_predict(self, x, src_pad_mask, alpha)
 
 
-class MultiFastPitch(nn.Module):
-    """Drop-in for models/multi_fast_pitch.py:93-328."""
+class MultiFastPitch(AcousticModel):
+    """Drop-in for models/multi_fast_pitch.py:93-328.  `matmul_dtype`: see fastpitch.FastPitch."""
+    config_key = 'multi_fast_pitch'
 
     # Constructor keywords = the keys of config['multi_fast_pitch']['model'] (+ num_chars, n_mels), exactly the
     # reference's (multi_fast_pitch.py:95-133).  Four predictors share one hyper-parameter pattern
@@ -91,11 +84,7 @@ class MultiFastPitch(nn.Module):
         if missing or extra:
             raise TypeError(f'MultiFastPitch(): missing {missing}, unexpected {extra}')
         self.padding_value = padding_value
-        self.matmul_dtype = 'fp32'          # or 'bf16': see fastpitch.FastPitch
         self.lr = LengthRegulator()
-        # predictor branches share no graph node with the trunk in training (trainer.TrainStep may run their backward as a
-        # stage of its own)
-        self.independent_predictors = True
         shared = {k: hp[k] for k in ('num_chars', 'conv1_kernel', 'conv2_kernel', 'speaker_emb_dims')}
 
         def predictor(kind, prefix, **more):
@@ -124,13 +113,6 @@ class MultiFastPitch(nn.Module):
         self.pitch_proj = nn.Conv1d(1, wide, kernel_size=3, padding=1)
         self.energy_proj = nn.Conv1d(1, wide, kernel_size=3, padding=1)
 
-    def __repr__(self):
-        return f'MultiFastPitch, num params: {sum(p.numel() for p in self.parameters())}'
-
-    def _require_device(self, t: torch.Tensor) -> None:
-        if not t.is_cuda or not self.embedding.weight.is_cuda:
-            raise _lib.FtError('MultiFastPitch runs on an MI355X (HIP) device only; there is no CPU fallback')
-
     def _mel(self, x_idx, semb, tok_mask, dur, pitch, energy, frame_lens: Optional[torch.Tensor]):
         B, Tx = x_idx.shape
         x = ops.EmbeddingFn.apply(x_idx, self.embedding.weight)
@@ -154,36 +136,22 @@ class MultiFastPitch(nn.Module):
         semb = batch['speaker_emb'].contiguous()
         mel_lens = batch['mel_len']
         pitch_cond = batch['pitch_cond']
-        self._require_device(x)
-        if self.training:
-            self.step += 1
+        self._begin_forward(x)
         len_mask = x == 0
-        # predictors on a side HIP stream, concurrently with the frame-side trunk (see FastPitch.forward)
-        main = torch.cuda.current_stream()
-        key = x.device.index or 0
-        if not hasattr(self, '_streams'):
-            self._streams = {}
-        if key not in self._streams:
-            from .model import _side_priority
-            self._streams[key] = torch.cuda.Stream(device=x.device, priority=_side_priority())
-        side = self._streams[key]
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
+
+        def predict():      # in the order that fixes the dropout seed sequence: dur, pitch, pitch_cond, energy
             dur_hat = self.dur_pred(x, pitch_cond, semb, src_pad_mask=len_mask).squeeze(-1)
             pitch_hat = self.pitch_pred(x, pitch_cond, semb, src_pad_mask=len_mask).transpose(1, 2)
             pitch_cond_hat = self.pitch_cond_pred(x, semb, src_pad_mask=len_mask)
             energy_hat = self.energy_pred(x, semb, src_pad_mask=len_mask).transpose(1, 2)
-            hook = getattr(self, 'predictor_hook', None)   # trainer.TrainStep: the predictors' losses + backward, right here
-            if hook is not None:
-                hook({'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat, 'pitch_cond': pitch_cond_hat})
+            return {'pitch_cond': pitch_cond_hat, 'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat}
+
+        # predictors on a side HIP stream, concurrently with the frame-side trunk (see FastPitch.forward)
+        fork = self._fork_predictors(x.device, predict)
         mel_cl = self._mel(x, semb, len_mask, dur, batch['pitch'], batch['energy'],
                            mel_lens.to(device=x.device, dtype=torch.long))
         x_mel = ops.TransposePadFn.apply(mel_cl, mel.size(2), self.padding_value)
-        main.wait_stream(side)
-        for t in (dur_hat, pitch_hat, pitch_cond_hat, energy_hat):
-            t.record_stream(main)
-        return {'mel': x_mel, 'mel_post': x_mel, 'pitch_cond': pitch_cond_hat, 'dur': dur_hat, 'pitch': pitch_hat,
-                'energy': energy_hat}
+        return {'mel': x_mel, 'mel_post': x_mel, **self._join_predictors(fork)}
 
     @precision_scoped
     def generate(self, x: torch.Tensor, speaker_emb: torch.Tensor, alpha=1.0,
@@ -209,24 +177,3 @@ class MultiFastPitch(nn.Module):
             m = H.transpose_pad_fwd(mel_cl, mel_cl.shape[1], 0.0)
             return {'mel': m, 'mel_post': m, 'dur': dur_in, 'pitch_cond': pitch_cond_hat, 'pitch': pitch_hat,
                     'energy': energy_hat}
-
-    def pad(self, x: torch.Tensor, max_len: int) -> torch.Tensor:
-        x = x[:, :, :max_len]
-        return torch.nn.functional.pad(x, [0, max_len - x.size(2), 0, 0], 'constant', self.padding_value)
-
-    def get_step(self) -> int:
-        return self.step.data.item()
-
-    @classmethod
-    def from_config(cls, config: Dict[str, Any]) -> 'MultiFastPitch':
-        model_config = config['multi_fast_pitch']['model']
-        model_config['num_chars'] = config.get('num_chars', NUM_CHARS_DEFAULT)
-        model_config['n_mels'] = config['dsp']['num_mels']
-        return MultiFastPitch(**model_config)
-
-    @classmethod
-    def from_checkpoint(cls, path: Union[Path, str]) -> 'MultiFastPitch':
-        checkpoint = torch.load(path, map_location=torch.device('cpu'), weights_only=True)
-        model = MultiFastPitch.from_config(checkpoint['config'])
-        model.load_state_dict(checkpoint['model'])
-        return model

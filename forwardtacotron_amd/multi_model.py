@@ -3,27 +3,29 @@ models/multi_forward_tacotron.py:14-323 -- same constructor kwargs, batch-dict f
 353-entry state_dict.  Built from the same HIP ops as forwardtacotron_amd.model plus the speaker concat,
 the conditional predictors and the 3-class pitch_cond head.
 """
-from pathlib import Path
-from typing import Any, Callable, Dict, Optional, Union
+from typing import Callable, Dict, Optional
 
 import torch
 import torch.nn as nn
 
 from . import hip as H
 from . import ops
-from .model import (BatchNormConv, CBHG, GRU, LSTM, LengthRegulator, NUM_CHARS_DEFAULT, PAD_VALUE, _dropout,
-                    _side_priority, regulate_and_decode)
+from .base import AcousticModel, LengthRegulator, PAD_VALUE, predictor_front
+from .model import BatchNormConv, CBHG, GRU, LSTM, conv_gru_predict, regulate_and_decode
 
 
-class SeriesPredictor(nn.Module):
-    """multi_forward_tacotron.py:14-50: embedding ++ speaker embedding -> 3 BatchNormConv -> biGRU -> Linear."""
+class _SpeakerSeriesPredictor(nn.Module):
+    """embedding ++ [pitch_cond embedding ++] speaker embedding -> 3 BatchNormConv -> biGRU -> Linear(out_dim): the two
+    predictors below, which differ in the conditional embedding only"""
 
-    def __init__(self, num_chars: int, emb_dim: int = 64, conv_dims: int = 256, rnn_dims: int = 64,
-                 dropout: float = 0.5, speaker_emb_dims: int = 256, out_dim: int = 1):
+    def __init__(self, num_chars: int, emb_dim: int, conv_dims: int, rnn_dims: int, dropout: float,
+                 speaker_emb_dims: int, out_dim: int = 1, cond_emb_size: int = 0, cond_emb_dims: int = 0):
         super().__init__()
         self.embedding = nn.Embedding(num_chars, emb_dim)
+        if cond_emb_size:
+            self.pitch_cond_embedding = nn.Embedding(cond_emb_size, cond_emb_dims)
         self.convs = nn.ModuleList([
-            BatchNormConv(emb_dim + speaker_emb_dims, conv_dims, 5, relu=True),
+            BatchNormConv(emb_dim + cond_emb_dims + speaker_emb_dims, conv_dims, 5, relu=True),
             BatchNormConv(conv_dims, conv_dims, 5, relu=True),
             BatchNormConv(conv_dims, conv_dims, 5, relu=True),
         ])
@@ -31,55 +33,36 @@ class SeriesPredictor(nn.Module):
         self.lin = nn.Linear(2 * rnn_dims, out_dim)
         self.dropout = dropout
 
+
+class SeriesPredictor(_SpeakerSeriesPredictor):
+    """multi_forward_tacotron.py:14-50: embedding ++ speaker embedding -> 3 BatchNormConv -> biGRU -> Linear."""
+
+    def __init__(self, num_chars: int, emb_dim: int = 64, conv_dims: int = 256, rnn_dims: int = 64,
+                 dropout: float = 0.5, speaker_emb_dims: int = 256, out_dim: int = 1):
+        super().__init__(num_chars, emb_dim, conv_dims, rnn_dims, dropout, speaker_emb_dims, out_dim)
+
     def forward(self, x: torch.Tensor, semb: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
-        B, T = x.shape
-        x = ops.EmbeddingFn.apply(x, self.embedding.weight)
-        x = ops.ConcatColsFn.apply(x, None, semb, B, T, False)
-        for conv in self.convs:
-            x = conv(x)
-            x = _dropout(x, self.dropout, self.training)
-        x = self.rnn(x, time_major_out=True)
-        x = ops.LinearFn.apply(x, self.lin.weight, self.lin.bias, B)
-        if alpha != 1.0:
-            x = ops.ScaleFn.apply(x, 1.0 / alpha)
-        return x
+        return conv_gru_predict(self, predictor_front(x, self.embedding, speaker_emb=semb), alpha)
 
 
-class ConditionalSeriesPredictor(nn.Module):
+class ConditionalSeriesPredictor(_SpeakerSeriesPredictor):
     """multi_forward_tacotron.py:53-93: embedding ++ pitch_cond embedding ++ speaker embedding -> ..."""
 
     def __init__(self, num_chars: int, emb_dim: int = 64, cond_emb_size: int = 4, cond_emb_dims: int = 8,
                  conv_dims: int = 256, rnn_dims: int = 64, dropout: float = 0.5, speaker_emb_dims: int = 256):
-        super().__init__()
-        self.embedding = nn.Embedding(num_chars, emb_dim)
-        self.pitch_cond_embedding = nn.Embedding(cond_emb_size, cond_emb_dims)
-        self.convs = nn.ModuleList([
-            BatchNormConv(emb_dim + cond_emb_dims + speaker_emb_dims, conv_dims, 5, relu=True),
-            BatchNormConv(conv_dims, conv_dims, 5, relu=True),
-            BatchNormConv(conv_dims, conv_dims, 5, relu=True),
-        ])
-        self.rnn = GRU(conv_dims, rnn_dims)
-        self.lin = nn.Linear(2 * rnn_dims, 1)
-        self.dropout = dropout
+        super().__init__(num_chars, emb_dim, conv_dims, rnn_dims, dropout, speaker_emb_dims,
+                         cond_emb_size=cond_emb_size, cond_emb_dims=cond_emb_dims)
 
     def forward(self, x: torch.Tensor, x_cond: torch.Tensor, speaker_emb: torch.Tensor,
                 alpha: float = 1.0) -> torch.Tensor:
-        B, T = x.shape
-        e = ops.EmbeddingFn.apply(x, self.embedding.weight)
-        c = ops.EmbeddingFn.apply(x_cond, self.pitch_cond_embedding.weight)
-        x = ops.ConcatColsFn.apply(e, c, speaker_emb, B, T, False)
-        for conv in self.convs:
-            x = conv(x)
-            x = _dropout(x, self.dropout, self.training)
-        x = self.rnn(x, time_major_out=True)
-        x = ops.LinearFn.apply(x, self.lin.weight, self.lin.bias, B)
-        if alpha != 1.0:
-            x = ops.ScaleFn.apply(x, 1.0 / alpha)
-        return x
+        return conv_gru_predict(self, predictor_front(x, self.embedding, x_cond, self.pitch_cond_embedding, speaker_emb),
+                                alpha)
 
 
-class MultiForwardTacotron(nn.Module):
+class MultiForwardTacotron(AcousticModel):
     """Drop-in for models/multi_forward_tacotron.py:96-323."""
+    config_key = 'multi_forward_tacotron'
+    recurrent = True
 
     # Constructor keywords = the keys of config['multi_forward_tacotron']['model'] (+ num_chars, n_mels), exactly the
     # reference's (multi_forward_tacotron.py:98-129).
@@ -100,9 +83,6 @@ class MultiForwardTacotron(nn.Module):
         E, P, Q, S = hp['embed_dims'], hp['prenet_dims'], hp['postnet_dims'], hp['speaker_emb_dims']
         self.embedding = nn.Embedding(hp['num_chars'], E)
         self.lr = LengthRegulator()
-        # predictor branches share no graph node with the trunk in training (trainer.TrainStep may run their backward as a
-        # stage of its own)
-        self.independent_predictors = True
 
         def predictor(kind, prefix, **more):
             # NB (reference quirk, multi_forward_tacotron.py:135-157): speaker_emb_dims is NOT forwarded to the
@@ -127,28 +107,6 @@ class MultiForwardTacotron(nn.Module):
         self.energy_strength = hp['energy_strength']
         self.pitch_proj = nn.Conv1d(1, 2 * P + S, kernel_size=3, padding=1)
         self.energy_proj = nn.Conv1d(1, 2 * P + S, kernel_size=3, padding=1)
-        self._nbt_flat = None
-
-    def __repr__(self):
-        return f'MultiForwardTacotron, num params: {sum(p.numel() for p in self.parameters())}'
-
-    def _require_device(self, t: torch.Tensor) -> None:
-        if not t.is_cuda or not self.embedding.weight.is_cuda:
-            raise H._lib.FtError('MultiForwardTacotron runs on an MI355X (HIP) device only; there is no CPU fallback')
-
-    def _bump_batchnorm_counters(self) -> None:
-        bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm1d)]
-        f = self._nbt_flat
-        ok = f is not None and f.device == bns[0].num_batches_tracked.device
-        if ok:
-            for i in (0, len(bns) - 1):
-                ok = ok and bns[i].num_batches_tracked.data_ptr() == f.data_ptr() + 8 * i
-        if not ok:
-            f = torch.stack([b.num_batches_tracked.detach().reshape(()) for b in bns]).contiguous()
-            for i, b in enumerate(bns):
-                b._buffers['num_batches_tracked'] = f[i]
-            self._nbt_flat = f
-        f += 1
 
     def _trunk(self, x, semb, dur, pitch, energy, mel_lens: Optional[torch.Tensor], late_inputs=None):
         """late_inputs (inference): delivers (dur, pitch, energy) once the prenet has been enqueued (see
@@ -168,6 +126,19 @@ class MultiForwardTacotron(nn.Module):
         post = ops.LinearFn.apply(post, self.post_proj.weight, None, B)
         return mel, post
 
+    def _predict(self, x, semb, pitch_cond=None, alpha: float = 1.0, pitch_function=lambda p: p,
+                 energy_function=lambda e: e):
+        """the four predictors, in the order that fixes the dropout seed sequence: pitch_cond, dur, pitch, energy.
+        pitch_cond None (generate): the argmax of the pitch_cond predictor conditions the other two -- a chain that
+        only works for B = 1, like the reference's (multi_forward_tacotron.py:258-262)"""
+        pitch_cond_hat = self.pitch_cond_pred(x, semb).squeeze(-1)               # [B,Tx,3]
+        if pitch_cond is None:
+            pitch_cond = pitch_cond_hat = torch.argmax(pitch_cond_hat.squeeze(), dim=1).long().unsqueeze(0)
+        dur_hat = self.dur_pred(x, pitch_cond, semb, alpha=alpha).squeeze(-1)
+        pitch_hat = pitch_function(self.pitch_pred(x, pitch_cond, semb).transpose(1, 2))
+        energy_hat = energy_function(self.energy_pred(x, semb).transpose(1, 2))
+        return {'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat, 'pitch_cond': pitch_cond_hat}
+
     def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         x = batch['x']
         mel = batch['mel']
@@ -177,41 +148,18 @@ class MultiForwardTacotron(nn.Module):
         pitch = batch['pitch']
         pitch_cond = batch['pitch_cond']
         energy = batch['energy']
-        self._require_device(x)
-        # token-side row count (incl. the conv bank's extra row): trainer.TrainStep keeps weight gradients of
-        # operands this short on the main stream (ops.GradSink.inline_rows)
-        self.wgrad_inline_rows = x.shape[0] * (x.shape[1] + 1)
-        self.wgrad_defer = True          # recurrences ahead: ops.GradSink.defer
-        if self.training:
-            self.step += 1
-            self._bump_batchnorm_counters()
+        self._begin_forward(x)
 
         # the four predictors are independent of the trunk in training (it consumes the batch's targets,
         # multi_forward_tacotron.py:183-213) and their 128-step recurrences are latency-bound: side HIP stream,
         # concurrently with the trunk, as in the single-speaker model (autograd replays each backward node on the
         # stream of its forward)
-        main = torch.cuda.current_stream()
-        side = self._side_stream(x.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            pitch_cond_hat = self.pitch_cond_pred(x, semb).squeeze(-1)           # [B,Tx,3]
-            dur_hat = self.dur_pred(x, pitch_cond, semb).squeeze(-1)
-            pitch_hat = self.pitch_pred(x, pitch_cond, semb).transpose(1, 2)
-            energy_hat = self.energy_pred(x, semb).transpose(1, 2)
-            hook = getattr(self, 'predictor_hook', None)   # trainer.TrainStep: the predictors' losses + backward, right here
-            if hook is not None:
-                hook({'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat, 'pitch_cond': pitch_cond_hat})
-
+        fork = self._fork_predictors(x.device, lambda: self._predict(x, semb, pitch_cond))
         mel_cl, post_cl = self._trunk(x, semb, dur, pitch, energy, mel_lens.to(device=x.device, dtype=torch.long))
         Tout = mel.size(2)
         x_post = ops.TransposePadFn.apply(post_cl, Tout, self.padding_value)
         x_mel = ops.TransposePadFn.apply(mel_cl, Tout, self.padding_value)
-        main.wait_stream(side)
-        H.rnn_note_join(main, side)
-        for t in (pitch_cond_hat, dur_hat, pitch_hat, energy_hat):
-            t.record_stream(main)
-        return {'mel': x_mel, 'mel_post': x_post, 'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat,
-                'pitch_cond': pitch_cond_hat}
+        return {'mel': x_mel, 'mel_post': x_post, **self._join_predictors(fork)}
 
     def generate(self, x: torch.Tensor, speaker_emb: torch.Tensor, alpha=1.0,
                  pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda x: x,
@@ -221,56 +169,9 @@ class MultiForwardTacotron(nn.Module):
             self._require_device(x)
             speaker_emb = speaker_emb.contiguous()
             # the four predictors beside embedding + prenet CBHG (side stream), joined where the trunk needs them
-            import os
-            main = torch.cuda.current_stream()
-            side = self._side_stream(x.device) if os.environ.get('FT_GEN_OVERLAP', '1') == '1' else main
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                pitch_cond_hat = self.pitch_cond_pred(x, speaker_emb).squeeze(-1)
-                pitch_cond_hat = torch.argmax(pitch_cond_hat.squeeze(), dim=1).long().unsqueeze(0)
-                dur_hat = self.dur_pred(x, pitch_cond_hat, speaker_emb, alpha=alpha).squeeze(-1)
-                pitch_hat = pitch_function(self.pitch_pred(x, pitch_cond_hat, speaker_emb).transpose(1, 2))
-                energy_hat = energy_function(self.energy_pred(x, speaker_emb).transpose(1, 2))
-            B = x.shape[0]
-            got = {}
-
-            def late_inputs():
-                main.wait_stream(side)
-                H.rnn_note_join(main, side)
-                for t in (pitch_cond_hat, dur_hat, pitch_hat, energy_hat):
-                    t.record_stream(main)
-                if torch.sum(dur_hat.long()) <= 0:
-                    torch.fill_(dur_hat, value=2.)
-                got['dur'] = dur_hat.contiguous()
-                return got['dur'], pitch_hat.reshape(B, -1).contiguous(), energy_hat.reshape(B, -1).contiguous()
-
+            pred, late_inputs = self._generate_fork(
+                x, lambda: self._predict(x, speaker_emb, None, alpha, pitch_function, energy_function))
             mel_cl, post_cl = self._trunk(x, speaker_emb, None, None, None, None, late_inputs=late_inputs)
             T = mel_cl.shape[1]
             return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0),
-                    'dur': got['dur'], 'pitch': pitch_hat, 'energy': energy_hat,
-                    'pitch_cond': pitch_cond_hat.unsqueeze(1)}
-
-    def _side_stream(self, device) -> 'torch.cuda.Stream':
-        key = torch.device(device).index or 0
-        if not hasattr(self, '_streams'):
-            self._streams = {}
-        if key not in self._streams:
-            self._streams[key] = torch.cuda.Stream(device=device, priority=_side_priority())
-        return self._streams[key]
-
-    def get_step(self) -> int:
-        return self.step.data.item()
-
-    @classmethod
-    def from_config(cls, config: Dict[str, Any]) -> 'MultiForwardTacotron':
-        model_config = config['multi_forward_tacotron']['model']
-        model_config['num_chars'] = config.get('num_chars', NUM_CHARS_DEFAULT)
-        model_config['n_mels'] = config['dsp']['num_mels']
-        return MultiForwardTacotron(**model_config)
-
-    @classmethod
-    def from_checkpoint(cls, path: Union[Path, str]) -> 'MultiForwardTacotron':
-        checkpoint = torch.load(path, map_location=torch.device('cpu'), weights_only=True)
-        model = MultiForwardTacotron.from_config(checkpoint['config'])
-        model.load_state_dict(checkpoint['model'])
-        return model
+                    **pred, 'pitch_cond': pred['pitch_cond'].unsqueeze(1)}

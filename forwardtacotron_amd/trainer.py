@@ -34,6 +34,7 @@ import torch.distributed as dist
 from . import _lib
 from . import hip as H
 from . import ops
+from .base import AcousticModel
 from .parallel import BucketedAllReduce, FlatBuffers, FlatParams
 
 _CU_LIMITED_STREAMS: Dict[tuple, 'torch.cuda.Stream'] = {}
@@ -44,7 +45,7 @@ DEFAULT_TRAIN_CFG = dict(dur_loss_factor=0.1, pitch_loss_factor=0.1, energy_loss
 
 
 class TrainStep:
-    def __init__(self, model: torch.nn.Module, lr: float, train_cfg: Optional[dict] = None,
+    def __init__(self, model: AcousticModel, lr: float, train_cfg: Optional[dict] = None,
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, bucket_bytes: int = 24 << 20,
                  on_rnn_fault: str = 'raise', gc_freeze: Optional[bool] = None):
         """gc_freeze: after the third step, move every object alive in the process out of Python's cyclic GC
@@ -52,6 +53,8 @@ class TrainStep:
         steps with the GPU running dry (profiles/r02_per_step_ms.txt) -- but the freeze is PROCESS-WIDE, so it is the
         application's decision: off unless asked for here or with FT_GC_FREEZE=1 (bench.py and tools/ ask for it);
         close() undoes it."""
+        if not isinstance(model, AcousticModel):
+            raise TypeError('TrainStep drives a base.AcousticModel (see its class attributes for what is read and set)')
         self.model = model
         self.lr = float(lr)
         self.cfg = dict(DEFAULT_TRAIN_CFG)
@@ -80,7 +83,7 @@ class TrainStep:
         # weight gradients are written straight into the flat buffer, the GEMM-shaped ones on a side stream
         # models with a recurrent trunk: 28 CUs per XCD by default (see _make_wgrad_stream); FT_WGRAD_CUS overrides
         self.wgrad_stream = self._make_wgrad_stream(dev, None if 'FT_WGRAD_CUS' in os.environ
-                                                    else (28 if hasattr(model, 'lstm') else 0))
+                                                    else (28 if model.recurrent else 0))
         self.reducer.streams.add(self.wgrad_stream)
         self.sink = ops.GradSink({p.data_ptr(): (i, p.grad) for i, p in enumerate(self.flat.params)},
                                  stream=self.wgrad_stream, on_write=self.reducer.notify)
@@ -261,8 +264,8 @@ class TrainStep:
         packs = self._weight_packs()
         packs.refresh()                     # every conv pack / weight transpose of this step, one launch
         H.pack_cache = packs
-        old_precision = H.set_gemm_precision(getattr(model, 'matmul_dtype', 'fp32'))    # forward AND backward
-        independent = bool(getattr(model, 'independent_predictors', False))
+        old_precision = H.set_gemm_precision(model.matmul_dtype)    # forward AND backward
+        independent = bool(model.independent_predictors)
         # EARLY predictor backward (FT_PRED_BWD_EARLY=1, off by default): the predictors' loss terms depend on nothing but
         # the predictors' own outputs and the batch's targets (forward_trainer.py:86-93), so their whole backward can be
         # issued on the predictors' stream right behind their forward, INSIDE the model's forward (model.predictor_hook),
@@ -272,16 +275,16 @@ class TrainStep:
         # predictors' BPTT kernels: 24.6 -> 25.8 ms.  Same gradients bit for bit either way (tests run both).
         early = independent and os.environ.get('FT_PRED_BWD_EARLY', '0') == '1'
         # staged backward (see below): only this trainer asks the model to cut its graph below the LSTM
-        staged = (not early and independent and hasattr(model, 'lstm')
+        staged = (not early and independent and model.recurrent
                   and os.environ.get('FT_STAGED_BACKWARD', '1') == '1')
         model.stage_backward = staged
         model._cut = None
         side_terms: Dict[str, torch.Tensor] = {}
 
         def arm_sink():
-            self.sink.inline_rows = int(getattr(model, 'wgrad_inline_rows', 0))
+            self.sink.inline_rows = int(model.wgrad_inline_rows)
             # models with recurrences queue their side-stream weight gradients and issue them beside the next BPTT kernel
-            self.sink.defer = bool(getattr(model, 'wgrad_defer', False)) and os.environ.get('FT_WGRAD_DEFER', '1') == '1'
+            self.sink.defer = bool(model.wgrad_defer) and os.environ.get('FT_WGRAD_DEFER', '1') == '1'
 
         def predictor_hook(p: Dict[str, torch.Tensor]) -> None:
             # called by the model on the predictors' stream, right behind their forward
@@ -329,28 +332,11 @@ class TrainStep:
                 # predictors -- their BPTT kernels queue behind the LSTM's and run beside the prenet's GEMMs -- then
                 # LR .. prenet, whose GRU fits next to a predictor's.
                 side_root, main_root = L.pop('_roots')
-                cut = getattr(model, '_cut', None)
+                cut = model._cut
                 model._cut = None
                 first = staged and cut is not None and self._predictors_first(model, int(batch['x'].shape[0]))
-                self.sink.late_ok = first and os.environ.get('FT_WGRAD_LATE', '1') == '1'
-                if first:
-                    # The predictors' stage issued FIRST: it then runs beside the postnet GRU's BPTT and the postnet's conv
-                    # backward -- the first 4 ms of the backward, of which 2 ms are a recurrence that leaves most of the chip
-                    # idle -- instead of in the tail of the step, where it was the last stream to finish (the LSTM's BPTT,
-                    # which fills its XCD slots, waits on the device for the predictors' BPTT kernels: they are long done).
-                    # Only where the predictors' BPTT grids fit BESIDE the postnet GRU's (_predictors_first): otherwise they
-                    # queue behind it and the stage delays the trunk (multispeaker: 38.0 -> 38.9 ms).
-                    here = torch.cuda.current_stream()
-                    pstream = model._side_stream(side_root.device)
-                    pstream.wait_stream(here)
-                    with torch.cuda.stream(pstream):
-                        side_root.backward()
-                    side_root.record_stream(pstream)
-                    self.sink.used.add(pstream)
-                    main_root.backward()
-                    cut[0].backward(cut[1].grad)
-                elif staged and cut is not None:
-                    main_root.backward()
+
+                def predictors_backward():
                     # backward() ends by making the CALLING stream wait for every stream it ran nodes on: called from
                     # the main stream the predictors' stage would simply be inserted into the critical path.  It is
                     # issued from the predictors' own stream; the step's final join picks that stream up.
@@ -361,6 +347,21 @@ class TrainStep:
                         side_root.backward()
                     side_root.record_stream(pstream)
                     self.sink.used.add(pstream)
+
+                self.sink.late_ok = first and os.environ.get('FT_WGRAD_LATE', '1') == '1'
+                if first:
+                    # The predictors' stage issued FIRST: it then runs beside the postnet GRU's BPTT and the postnet's conv
+                    # backward -- the first 4 ms of the backward, of which 2 ms are a recurrence that leaves most of the chip
+                    # idle -- instead of in the tail of the step, where it was the last stream to finish (the LSTM's BPTT,
+                    # which fills its XCD slots, waits on the device for the predictors' BPTT kernels: they are long done).
+                    # Only where the predictors' BPTT grids fit BESIDE the postnet GRU's (_predictors_first): otherwise they
+                    # queue behind it and the stage delays the trunk (multispeaker: 38.0 -> 38.9 ms).
+                    predictors_backward()
+                    main_root.backward()
+                    cut[0].backward(cut[1].grad)
+                elif staged and cut is not None:
+                    main_root.backward()
+                    predictors_backward()
                     cut[0].backward(cut[1].grad)
                 else:
                     L['loss'].backward()

@@ -50,7 +50,7 @@ def main():
     torch.manual_seed(0)
     model, cfg = build(args.model, device)
     if args.dtype == 'bf16':
-        if not hasattr(model, 'matmul_dtype'):
+        if model.recurrent:
             raise SystemExit('--dtype bf16 applies to the FastPitch variants (recurrent models stay fp32)')
         model.matmul_dtype = 'bf16'
     if args.no_dropout:
