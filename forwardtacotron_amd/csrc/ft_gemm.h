@@ -243,6 +243,21 @@ __device__ __forceinline__ FtTnWho ft_tn_who(const FtGemmTNTask& T, int S, int B
   return w;
 }
 
+// Which kernel each GEMM launch took, counted on the host at the dispatch sites since the library loaded
+// (ft_gemm_variant_counts; the order is the ABI's, include/fwdtaco_hip.h).  Plain integers: no device work, no
+// synchronisation.  Tests assert the delta of the one variant they mean to exercise, so a planner threshold that moves
+// a test's shape onto another kernel fails that test instead of quietly testing less.
+enum FtGemmVariant {
+  FT_GV_ROWS_F32_64_NT_FAST = 0, FT_GV_ROWS_F32_64_NT_SLOW, FT_GV_ROWS_F32_64_NN_FAST, FT_GV_ROWS_F32_64_NN_SLOW,
+  FT_GV_ROWS_F32_128_NT_FAST, FT_GV_ROWS_F32_128_NT_SLOW, FT_GV_ROWS_F32_128_NN_FAST, FT_GV_ROWS_F32_128_NN_SLOW,
+  FT_GV_ROWS_B3_64, FT_GV_ROWS_B3_128, FT_GV_ROWS_B3P, FT_GV_ROWS_B3P_KSPLIT,
+  FT_GV_TN_F32_64_FAST, FT_GV_TN_F32_64_SLOW, FT_GV_TN_F32_128_FAST, FT_GV_TN_F32_128_SLOW,
+  FT_GV_TN_B3_64, FT_GV_TN_B3_128, FT_GV_TN_B3P,
+  FT_GV_COUNT
+};
+extern long g_ft_gemm_variant[FT_GV_COUNT];
+static inline void ft_count_variant(int v) { ++g_ft_gemm_variant[v]; }
+
 // the launcher's tile choice for a launch whose tasks have `tiles128` 128x128 output tiles in total
 static inline bool ft_rows_tile_is_big(long tiles128, int maxM, int maxN) { return tiles128 >= 192 && maxN > 64 && maxM > 64; }
 static_assert(sizeof(FtGemmBatch) <= 4080, "FtGemmBatch travels as a kernel argument (4 KB limit)");

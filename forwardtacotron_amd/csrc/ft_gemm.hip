@@ -16,6 +16,7 @@
 // routed to the bf16-split kernel of ft_gemm_b3.hip instead (136-148 TFLOP/s fp32-equivalent); this file keeps the
 // 64x64 tiles, the [K][N] operand form, unaligned / odd shapes and the TN (weight-gradient) kernel.
 #include "ft_gemm.h"
+#include "fwdtaco_hip.h"
 
 namespace {
 
@@ -657,6 +658,13 @@ extern "C" int ft_set_gemm_precision(int bf16) {
   return old;
 }
 
+static_assert(FT_GV_COUNT == FT_GEMM_VARIANTS, "FtGemmVariant and the ABI's variant table differ");
+long g_ft_gemm_variant[FT_GV_COUNT] = {};
+extern "C" int ft_gemm_variant_counts(long* counts, int n) {
+  for (int i = 0; i < n && i < FT_GV_COUNT; ++i) counts[i] = g_ft_gemm_variant[i];
+  return FT_GV_COUNT;
+}
+
 size_t ft_gemm_tn_workspace_floats(const FtGemmTNTask& t) {
   // the query does not know the operands' alignment yet: cover both plans the launcher may pick
   const TNPlan p0 = plan_tn(t, false), p1 = plan_tn(t, true);
@@ -768,12 +776,15 @@ int ft_launch_gemm_rows(FtGemmBatch* batch, int ntasks, bool b_ncontig, hipStrea
   batch->stat_fused = b3 && big && !chained;      // only the 128x128 split kernel computes BatchNorm statistics
   if (b3) {
     (void)ft_launch_gemm_rows_b3(*batch, big, grid, stream);
-  } else if (big) {
-    if (b_ncontig) FT_ROWS_LAUNCH(2, true);
-    else FT_ROWS_LAUNCH(2, false);
   } else {
-    if (b_ncontig) FT_ROWS_LAUNCH(1, true);
-    else FT_ROWS_LAUNCH(1, false);
+    ft_count_variant((big ? FT_GV_ROWS_F32_128_NT_FAST : FT_GV_ROWS_F32_64_NT_FAST) + (b_ncontig ? 2 : 0) + (fast ? 0 : 1));
+    if (big) {
+      if (b_ncontig) FT_ROWS_LAUNCH(2, true);
+      else FT_ROWS_LAUNCH(2, false);
+    } else {
+      if (b_ncontig) FT_ROWS_LAUNCH(1, true);
+      else FT_ROWS_LAUNCH(1, false);
+    }
   }
 #undef FT_ROWS_LAUNCH
   if (GemmLog::on()) {
@@ -837,9 +848,11 @@ int ft_launch_gemm_tn(const FtGemmTNTask& task_in, float* workspace, size_t work
   if (b3) {
     (void)ft_launch_gemm_tn_b3(t, workspace, p.S, p.rows_per_split, p.tm, grid, stream);
   } else if (p.tm == 2) {
+    ft_count_variant(fast ? FT_GV_TN_F32_128_FAST : FT_GV_TN_F32_128_SLOW);
     if (fast) hipLaunchKernelGGL((ft_gemm_tn_kernel<2, 2, true>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
     else hipLaunchKernelGGL((ft_gemm_tn_kernel<2, 2, false>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
   } else {
+    ft_count_variant(fast ? FT_GV_TN_F32_64_FAST : FT_GV_TN_F32_64_SLOW);
     if (fast) hipLaunchKernelGGL((ft_gemm_tn_kernel<1, 1, true>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
     else hipLaunchKernelGGL((ft_gemm_tn_kernel<1, 1, false>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
   }

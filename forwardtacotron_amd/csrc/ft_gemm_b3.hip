@@ -1200,9 +1200,11 @@ int ft_launch_gemm_tn_b3(const FtGemmTNTask& t, float* slab, int S, int rows_per
       if (bf16) hipLaunchKernelGGL((ft_gemm_tn_b3p_kernel<1>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
       else hipLaunchKernelGGL((ft_gemm_tn_b3p_kernel<3>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
       ++g_tn_pipelined;
+      ft_count_variant(FT_GV_TN_B3P);
       return FT_OK;
     }
   }
+  ft_count_variant(tm == 2 ? FT_GV_TN_B3_128 : FT_GV_TN_B3_64);
   if (tm == 2) {
     if (bf16) hipLaunchKernelGGL((ft_gemm_tn_b3_kernel<2, 2, 1>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
     else hipLaunchKernelGGL((ft_gemm_tn_b3_kernel<2, 2, 3>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
@@ -1242,6 +1244,7 @@ int ft_launch_gemm_rows_b3(const FtGemmBatch& batch, bool big, dim3 grid, hipStr
   const int ntask = batch.chain > 1 ? batch.chain : (batch.ksplit > 1 ? 1 : (int)grid.z);
   const bool p_ok = ft_rows_b3p_ok(batch, ntask);
   FT_REQUIRE(batch.ksplit <= 1 || (big && p_ok), "gemm_rows: split-K planned for a launch the pipelined kernel cannot take");
+  ft_count_variant(big && p_ok ? (batch.ksplit > 1 ? FT_GV_ROWS_B3P_KSPLIT : FT_GV_ROWS_B3P) : (big ? FT_GV_ROWS_B3_128 : FT_GV_ROWS_B3_64));
   if (big && p_ok) {
     if (bf16) hipLaunchKernelGGL((ft_gemm_rows_b3p_kernel<1>), grid, dim3(256), 0, stream, batch);
     else hipLaunchKernelGGL((ft_gemm_rows_b3p_kernel<3>), grid, dim3(256), 0, stream, batch);

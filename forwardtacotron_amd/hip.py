@@ -94,6 +94,24 @@ def gemm_precision(mode: str):
         set_gemm_precision(old)
 
 
+# names of ft_gemm_variant_counts' entries, in the ABI's order (include/fwdtaco_hip.h)
+GEMM_VARIANTS = (
+    'rows_f32_64_nt_fast', 'rows_f32_64_nt_slow', 'rows_f32_64_nn_fast', 'rows_f32_64_nn_slow',
+    'rows_f32_128_nt_fast', 'rows_f32_128_nt_slow', 'rows_f32_128_nn_fast', 'rows_f32_128_nn_slow',
+    'rows_b3_64', 'rows_b3_128', 'rows_b3p', 'rows_b3p_ksplit',
+    'tn_f32_64_fast', 'tn_f32_64_slow', 'tn_f32_128_fast', 'tn_f32_128_slow',
+    'tn_b3_64', 'tn_b3_128', 'tn_b3p')
+
+
+def gemm_variant_counts() -> dict:
+    """{variant name: launches since the library loaded} -- which kernel the GEMM launchers dispatched (host counters)"""
+    n = len(GEMM_VARIANTS)
+    arr = (ctypes.c_long * n)()
+    if _lib.query('ft_gemm_variant_counts', ctypes.cast(arr, c_void_p), n) != n:
+        raise _lib.FtError('ft_gemm_variant_counts: the library knows another variant list than hip.GEMM_VARIANTS')
+    return dict(zip(GEMM_VARIANTS, (int(v) for v in arr)))
+
+
 # ---------------------------------------------------------------------------------------------------
 # fused attention (bf16 mode)
 # ---------------------------------------------------------------------------------------------------

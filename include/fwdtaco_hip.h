@@ -42,6 +42,17 @@ int ft_set_gemm_precision(int bf16);
 /* weight-gradient launches that took the software-pipelined 128x128 kernel since the library loaded (tests use it to
  * prove which kernel they exercised; the choice never changes results: both kernels give the same bits) */
 int ft_gemm_tn_pipelined_launches(void);
+/* Launches per GEMM kernel variant since the library loaded, counted on the host where the launchers dispatch (plain
+ * integers: no device work, no synchronisation).  Fills counts[0 .. min(n, FT_GEMM_VARIANTS) - 1] and returns
+ * FT_GEMM_VARIANTS.  Order (forwardtacotron_amd/hip.py: GEMM_VARIANTS names them):
+ *   row kernels, f32 MFMA:  0-3 the 64x64 tile as NT fast, NT not fast, NN fast, NN not fast ("fast" = 16-B loads: aligned
+ *                           operands, K % 4 == 0 or padded rows); 4-7 the 128x128 tile in the same order;
+ *   row kernels, bf16 split (or bf16 mode): 8 64x64, 9 128x128 two-barrier, 10 128x128 pipelined, 11 pipelined with split-K;
+ *   weight gradients (TN), f32 MFMA: 12 64 fast, 13 64 not fast, 14 128 fast, 15 128 not fast;
+ *   weight gradients, bf16 split (or bf16 mode): 16 64, 17 128 two-barrier, 18 128 pipelined.
+ * Tests assert the delta of the one variant they mean to exercise (tests/test_gpu_gemm_edges.py). */
+#define FT_GEMM_VARIANTS 19
+int ft_gemm_variant_counts(long* counts, int n);
 
 /* ---- nn.Linear (models/forward_tacotron.py:25,100,108 ; common_layers.py:31-32,83) ------------------ */
 /* Row layouts: the rows of an activation matrix are the (b,t) positions in batch-major order (row = b*T+t,
