@@ -57,6 +57,13 @@ def maxdiff(a, b):
         return 0.0
     return float((a - b).abs().max())
 
+
+def rel_err(a, b):
+    """worst absolute difference over the largest reference magnitude"""
+    a = torch.as_tensor(a).double().cpu(); b = torch.as_tensor(b).double().cpu()
+    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
+
+
 TINY_MULTI = dict(embed_dims=16, series_embed_dims=8, num_chars=135,
                   durpred_conv_dims=16, durpred_rnn_dims=8, durpred_dropout=0.0,
                   pitch_conv_dims=16, pitch_rnn_dims=12, pitch_dropout=0.0, pitch_strength=1.0,

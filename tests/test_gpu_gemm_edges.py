@@ -21,6 +21,8 @@ import ctypes
 import pytest
 import torch
 
+from helpers import rel_err
+
 pytestmark = pytest.mark.gpu
 
 NAN = float('nan')
@@ -36,11 +38,6 @@ def H():
 def _call(name, *args):
     from forwardtacotron_amd import _lib
     _lib.call(name, *args)
-
-
-def rel_err(a, b):
-    a = torch.as_tensor(a).double().cpu(); b = torch.as_tensor(b).double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 def elem_err(got, ref, scale):

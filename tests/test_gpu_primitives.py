@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_npz, maxdiff
+from helpers import load_npz, maxdiff, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -17,11 +17,6 @@ def H():
 
 def dev(t):
     return t.cuda().contiguous()
-
-
-def rel_err(a, b):
-    a = torch.as_tensor(a).double().cpu(); b = torch.as_tensor(b).double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 @pytest.mark.parametrize('rows,in_f,out_f', [(7, 5, 3), (64, 32, 64), (130, 257, 66), (4096, 256, 512),
