@@ -30,6 +30,7 @@ int ft_check_launch(const char* what) {
 }
 
 int ft_lr_scan_impl(float*, int, int, int*, int*, hipStream_t);
+int ft_gen_durations_impl(float*, const long*, int, int, long*, int*, hipStream_t);
 int ft_lr_expand_impl(const float*, const int*, float*, int*, int, int, int, int, hipStream_t, int = 0, const float* = nullptr);
 int ft_lr_bwd_impl(const float*, const int*, float*, int, int, int, int, hipStream_t, int = 0, float* = nullptr);
 
@@ -344,6 +345,20 @@ int ft_conv1d_fwd(const float* x, long ldx, const float* wp, const float* scale,
   b.t[0].scale = scale;
   b.t[0].shift = shift;
   b.t[0].accumulate = accumulate;
+  return ft_launch_gemm_rows(&b, 1, false, (hipStream_t)stream);
+}
+
+int ft_conv1d_fwd_lens(const float* x, long ldx, const float* wp, const float* scale, const float* shift, float* y,
+                       long ldy, const long* lens, int B, int T, int Cin, int Cout, int k, int relu, int accumulate,
+                       void* stream) {
+  FT_REQUIRE(k >= 1 && lens != nullptr, "conv1d_fwd_lens: bad k / null lens");
+  FtGemmBatch b;
+  memset(&b, 0, sizeof(b));
+  conv_fwd_task(b.t[0], x, ldx, wp, y, ldy, B, T, Cin, Cout, k, T, relu);
+  b.t[0].scale = scale;
+  b.t[0].shift = shift;
+  b.t[0].accumulate = accumulate;
+  b.out_lens = lens;               // the epilogue stores zeros at t >= lens[b] (FtGemmBatch.out_lens)
   return ft_launch_gemm_rows(&b, 1, false, (hipStream_t)stream);
 }
 
@@ -725,6 +740,11 @@ int ft_bgemm_tn(const float* A, long lda, long sA0, long sA1, const float* Bm, l
 }
 
 // ------------------------------------------------------------------------------------------------
+int ft_gen_durations(float* dur, const long* x_len, int B, int Tx, long* mel_len, int* bad, void* stream) {
+  FT_REQUIRE(dur && x_len && mel_len && bad && Tx >= 1, "gen_durations: bad arguments");
+  return ft_gen_durations_impl(dur, x_len, B, Tx, mel_len, bad, (hipStream_t)stream);
+}
+
 int ft_lr_scan(float* dur, int B, int Tx, int* cum, int* total, void* stream) {
   return ft_lr_scan_impl(dur, B, Tx, cum, total, (hipStream_t)stream);
 }

@@ -113,6 +113,27 @@ __global__ void ft_embedding_fwd_kernel(const long* __restrict__ idx, const floa
   }
   out[i] = w[v * C + c];
 }
+// the embedding of a ragged batch: rows t >= lens[b] are zero and their ids are never read (they may hold anything)
+__global__ void ft_embedding_fwd_lens_kernel(const long* __restrict__ idx, const long* __restrict__ lens,
+                                             const float* __restrict__ w, float* __restrict__ out, int B, int T, int C,
+                                             int V, int* __restrict__ err) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * T * C) return;
+  long r = i / C;
+  int c = (int)(i - r * C);
+  int b = (int)(r / T), t = (int)(r - (long)b * T);
+  if (t >= lens[b]) {
+    out[i] = 0.f;
+    return;
+  }
+  long v = idx[r];
+  if (v < 0 || v >= V) {
+    if (c == 0) atomicExch(err, 1);
+    out[i] = 0.f;
+    return;
+  }
+  out[i] = w[v * C + c];
+}
 
 // onehot[row][v] = (idx[row] == v): the embedding weight gradient is then onehot^T * dout, one TN MFMA GEMM
 // (ordered split reduction -> reproducible), shared by every embedding table fed by the same ids
@@ -192,6 +213,46 @@ __global__ __launch_bounds__(256) void ft_maxpool_fwd4_kernel(const float4* __re
     v.y = v.y > p.y ? v.y : p.y;
     v.z = v.z > p.z ? v.z : p.z;
     v.w = v.w > p.w ? v.w : p.w;
+  }
+  out[i] = v;
+}
+// The same with per-item lengths (ForwardTacotron.generate_batch): out[b,t] = 0 at t >= lens[b] -- the window of row
+// lens[b] would otherwise carry x[lens[b]-1] into the padding, where the next convolution reads it.  Rows beyond the
+// length load nothing.
+__global__ void ft_maxpool_fwd_lens_kernel(const float* __restrict__ x, const long* __restrict__ lens,
+                                           float* __restrict__ out, int B, int T, int C) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long total = (long)B * T * C;
+  if (i >= total) return;
+  long row = i / C;
+  int b = (int)(row / T), t = (int)(row - (long)b * T);
+  float v = 0.f;
+  if (t < lens[b]) {
+    v = x[i];
+    if (t > 0) {
+      float p = x[i - C];
+      v = v > p ? v : p;
+    }
+  }
+  out[i] = v;
+}
+__global__ __launch_bounds__(256) void ft_maxpool_fwd4_lens_kernel(const float4* __restrict__ x,
+                                                                   const long* __restrict__ lens,
+                                                                   float4* __restrict__ out, long total4, int T, int C4) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const long row = i / C4;
+  const int b = (int)(row / T), t = (int)(row - (long)b * T);
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (t < lens[b]) {
+    v = x[i];
+    if (t > 0) {
+      const float4 p = x[i - C4];
+      v.x = v.x > p.x ? v.x : p.x;
+      v.y = v.y > p.y ? v.y : p.y;
+      v.z = v.z > p.z ? v.z : p.z;
+      v.w = v.w > p.w ? v.w : p.w;
+    }
   }
   out[i] = v;
 }
@@ -388,6 +449,27 @@ __global__ __launch_bounds__(256) void ft_transpose_pad_kernel(const float* __re
     if (c < C && t < Tout) out[((long)b * C + c) * Tout + t] = tile[tx][i];
   }
 }
+// out[b,c,t] = t < min(lens[b], T) ? x[b,t,c] : pad   for t < Tout   (per-item lengths: ForwardTacotron.generate_batch)
+__global__ __launch_bounds__(256) void ft_transpose_pad_lens_kernel(const float* __restrict__ x,
+                                                                    const long* __restrict__ lens,
+                                                                    float* __restrict__ out, int T, int C, int Tout,
+                                                                    float pad) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z;
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+  const long Lb = lens[b];
+  const int L = Lb < 0 ? 0 : (Lb > T ? T : (int)Lb);
+  for (int i = ty; i < 32; i += 8) {
+    int t = t0 + i, c = c0 + tx;
+    tile[i][tx] = (t < L && c < C) ? x[((long)b * T + t) * C + c] : pad;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    int c = c0 + i, t = t0 + tx;
+    if (c < C && t < Tout) out[((long)b * C + c) * Tout + t] = tile[tx][i];
+  }
+}
 // dx[b,t,c] = t < Tout ? dout[b,c,t] : 0   for t < T
 __global__ __launch_bounds__(256) void ft_transpose_pad_bwd_kernel(const float* __restrict__ dout, float* __restrict__ dx,
                                                                    int T, int C, int Tout) {
@@ -538,6 +620,16 @@ int ft_embedding_fwd(const long* idx, const float* w, float* out, long rows, int
   return ft_check_launch("embedding_fwd");
 }
 
+int ft_embedding_fwd_lens(const long* idx, const long* lens, const float* w, float* out, int B, int T, int C, int V,
+                          int* err_flag, void* stream) {
+  FT_REQUIRE(B >= 0 && T >= 0 && C >= 0 && V > 0 && lens != nullptr, "embedding_fwd_lens: bad dims / null lens");
+  const long total = (long)B * T * C;
+  if (total == 0) return FT_OK;
+  hipLaunchKernelGGL(ft_embedding_fwd_lens_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, idx,
+                     lens, w, out, B, T, C, V, err_flag);
+  return ft_check_launch("embedding_fwd_lens");
+}
+
 int ft_onehot(const long* idx, float* out, long rows, int V, void* stream) {
   FT_REQUIRE(rows >= 0 && V > 0, "onehot: bad dims");
   if (rows == 0) return FT_OK;
@@ -580,6 +672,19 @@ int ft_maxpool2_fwd(const float* x, float* out, int B, int T, int C, void* strea
   return ft_check_launch("maxpool2_fwd");
 }
 
+int ft_maxpool2_fwd_lens(const float* x, const long* lens, float* out, int B, int T, int C, void* stream) {
+  FT_REQUIRE(lens != nullptr, "maxpool2_fwd_lens: null lens");
+  long total = (long)B * T * C;
+  if (total <= 0) return FT_OK;
+  if (C % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0)
+    hipLaunchKernelGGL(ft_maxpool_fwd4_lens_kernel, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float4*)x, lens, (float4*)out, total / 4, T, C / 4);
+  else
+    hipLaunchKernelGGL(ft_maxpool_fwd_lens_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, lens,
+                       out, B, T, C);
+  return ft_check_launch("maxpool2_fwd_lens");
+}
+
 int ft_maxpool2_bwd(const float* dout, const float* x, float* dx, int B, int T, int C, void* stream) {
   long total = (long)B * T * C;
   if (total <= 0) return FT_OK;
@@ -617,6 +722,16 @@ int ft_transpose_pad_fwd(const float* x, float* out, int B, int T, int C, int To
   hipLaunchKernelGGL(ft_transpose_pad_kernel, dim3(ft_cdiv(Tout, 32), ft_cdiv(C, 32), B), dim3(256), 0,
                      (hipStream_t)stream, x, out, T, C, Tout, pad);
   return ft_check_launch("transpose_pad_fwd");
+}
+
+int ft_transpose_pad_lens_fwd(const float* x, const long* lens, float* out, int B, int T, int C, int Tout, float pad,
+                              void* stream) {
+  FT_REQUIRE(lens != nullptr, "transpose_pad_lens_fwd: null lens");
+  if (B <= 0 || C <= 0 || Tout <= 0) return FT_OK;
+  FT_REQUIRE(B <= 65535 && ft_cdiv(C, 32) <= 65535, "transpose_pad_lens_fwd: grid too large");
+  hipLaunchKernelGGL(ft_transpose_pad_lens_kernel, dim3(ft_cdiv(Tout, 32), ft_cdiv(C, 32), B), dim3(256), 0,
+                     (hipStream_t)stream, x, lens, out, T, C, Tout, pad);
+  return ft_check_launch("transpose_pad_lens_fwd");
 }
 
 int ft_transpose_pad_bwd(const float* dout, float* dx, int B, int T, int C, int Tout, void* stream) {

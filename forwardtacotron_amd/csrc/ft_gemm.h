@@ -90,6 +90,10 @@ struct FtGemmBatch {
   const float* hw_b2;
   float* hw_x12;
   float* hw_d12;
+  // Row mask in the epilogue (the length-aware eval convolutions, ft_conv1d_fwd_lens): int64 [items] or null.  A stored
+  // row (item, t) = (row / amap.Tlog, row % amap.Tlog) of any task with t >= out_lens[item] is written as exactly 0,
+  // whatever bias / ReLU / scale-shift / accumulate would have made of it.  Not combined with split-K or the highway modes.
+  const long* out_lens;
 };
 
 // The highway epilogues (see FtGemmBatch) for an accumulator tile in the 32x32 MFMA layout shared by the row kernels:

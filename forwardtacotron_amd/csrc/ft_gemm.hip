@@ -292,6 +292,8 @@ __global__ __launch_bounds__(256) void ft_gemm_rows_kernel(FtGemmBatch batch) {
   const bool erelu = T.relu != 0, eacc = T.accumulate != 0;
   const long ldc = T.ldc, cbst = T.cmap.bstride, ctst = T.cmap.tstride;
   const int cTlog = T.cmap.Tlog;
+  const long* olens = batch.out_lens;
+  const int oTlog = T.amap.Tlog;
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -316,6 +318,10 @@ __global__ __launch_bounds__(256) void ft_gemm_rows_kernel(FtGemmBatch batch) {
         if (escale) v = v * sc + sh;
         if (batch.relu_mask && !(batch.relu_mask[crow * ldc + col] > 0.f)) v = 0.f;
         if (eacc) v += *cp;              // residual / gradient accumulation happens last
+        if (olens) {                     // (length-aware convolutions: rows beyond the item's length are zeros)
+          const int ob = row / oTlog;
+          if (row - ob * oTlog >= olens[ob]) v = 0.f;
+        }
         *cp = v;
       }
     }
@@ -682,7 +688,7 @@ static int rows_ksplit_plan(const FtGemmBatch& b, int ntasks, hipStream_t stream
   const bool chained = b.chain > 1;
   if (!enabled || !(chained ? b.chain == ntasks : ntasks == 1) || !ft_gemm_b3_enabled()) return 1;
   const FtGemmTask& t0 = b.t[0];
-  if (t0.nz > 1 || t0.relu || t0.scale || t0.stat || b.hw_mode || b.relu_mask || t0.N % 4 != 0 || t0.M <= 64 || t0.N <= 64) return 1;
+  if (t0.nz > 1 || t0.relu || t0.scale || t0.stat || b.hw_mode || b.relu_mask || b.out_lens || t0.N % 4 != 0 || t0.M <= 64 || t0.N <= 64) return 1;
   if (!ft_rows_b3p_ok(b, ntasks)) return 1;
   long stages = 0;
   for (int i = 0; i < ntasks; ++i) stages += (long)b.t[i].taps * ft_cdiv(b.t[i].K, 16);

@@ -76,7 +76,7 @@ __device__ __forceinline__ void store_rn(unsigned short* row, const float4& v) {
 template <int TM, int TN>
 __device__ __forceinline__ void rows_b3_epilogue(const FtGemmTask& T, float* TC, f32x16 (&acc)[TM][TN], unsigned short* smem,
                                                  int m0, int n0, int tM, int tN, int tid, int mtile,
-                                                 const float* relu_mask = nullptr) {
+                                                 const float* relu_mask = nullptr, const long* olens = nullptr) {
   const int wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
   const int half = lane >> 5, l31 = lane & 31;
@@ -92,6 +92,22 @@ __device__ __forceinline__ void rows_b3_epilogue(const FtGemmTask& T, float* TC,
   const int stb = stat ? srow0 % sTlog : 0;
   const bool ssmall = sTlog < 32 * TM;
   double* sred = reinterpret_cast<double*>(smem);          // [wm 2][128 columns][2] doubles = 4 KB of the (now idle) tiles
+  // FtGemmBatch.out_lens: bit 16 * i + e = row (i, e) of this lane lies inside its item's length (else it is stored as 0);
+  // worked out once, ahead of the column loop, so that the lengths stay out of it
+  unsigned keep = 0xFFFFFFFFu;
+  if (olens) {
+    static_assert(TM <= 2, "one keep bit per accumulator row of the lane");
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * 32 * TM + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * half;
+        if (row < tM) {
+          const int ob = row / sTlog;
+          if (row - ob * sTlog >= olens[ob]) keep &= ~(1u << (16 * i + e));
+        }
+      }
+  }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int col = n0 + wn * 32 * TN + 32 * j + l31;
@@ -126,6 +142,7 @@ __device__ __forceinline__ void rows_b3_epilogue(const FtGemmTask& T, float* TC,
         if (escale) v = v * sc + sh;
         if (relu_mask && !(relu_mask[crow * ldc + col] > 0.f)) v = 0.f;
         if (eacc) v += *cp;
+        if (!((keep >> (16 * i + e)) & 1u)) v = 0.f;
         *cp = v;
       }
     }
@@ -315,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void ft_gemm_rows_b3_kernel(FtGemmBatch bat
     ft_highway_epilogue<TM, TN>(batch, T, TC, acc, reinterpret_cast<float*>(smem), m0, n0, tid);
     return;
   }
-  rows_b3_epilogue<TM, TN>(T, TC, acc, smem, m0, n0, tM, tN, tid, blockIdx.x, batch.relu_mask);
+  rows_b3_epilogue<TM, TN>(T, TC, acc, smem, m0, n0, tM, tN, tid, blockIdx.x, batch.relu_mask, batch.out_lens);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -661,7 +678,7 @@ __global__ __launch_bounds__(256, 2) void ft_gemm_rows_b3p_kernel(FtGemmBatch ba
     ft_highway_epilogue<TM, TN>(batch, T, TC, acc, reinterpret_cast<float*>(smem), m0, n0, tid);
     return;
   }
-  rows_b3_epilogue<TM, TN>(T, TC, acc, smem, m0, n0, tM, tN, tid, bx, batch.relu_mask);
+  rows_b3_epilogue<TM, TN>(T, TC, acc, smem, m0, n0, tM, tN, tid, bx, batch.relu_mask, batch.out_lens);
 }
 
 // second launch of a split-K NT product: C[cmap(row)][col] (+)= sum_z slab[z][row][col] + bias, in range order

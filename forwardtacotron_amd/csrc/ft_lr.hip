@@ -40,6 +40,42 @@ __global__ __launch_bounds__(64) void ft_lr_scan_kernel(float* dur, int Tx, int*
   }
 }
 
+// Durations of a ragged inference batch (ForwardTacotron.generate_batch; forward_tacotron.py:174-177 and
+// common_layers.py:17-24 per ITEM): one wave per item, L = x_len[b].
+//   fallback : sum_{j < L} trunc(dur[j]) <= 0  ->  every token j < L gets 2.0
+//   dur      : 0 at j >= L, negatives clamped to 0 (the form the LengthRegulator leaves behind)
+//   mel_len  : sum_j (long)(dur[j] + 0.5f)  -- ft_lr_scan's rounding, so it equals that kernel's total
+// An x_len outside [1, Tx] raises *bad and is clamped into the range (the caller reports it).
+__global__ __launch_bounds__(64) void ft_gen_durations_kernel(float* dur, const long* __restrict__ x_len, int Tx,
+                                                              long* __restrict__ mel_len, int* bad) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float* d = dur + (long)b * Tx;
+  long Lb = x_len[b];
+  if (Lb < 1 || Lb > Tx) {
+    if (lane == 0) atomicOr(bad, 1);
+    Lb = Lb < 1 ? 1 : Tx;
+  }
+  const int L = (int)Lb;
+  long tr = 0;
+  for (int j = lane; j < L; j += 64) tr += (long)d[j];        // dur_hat.long(): truncation toward zero
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
+  const bool fallback = tr <= 0;
+  long total = 0;
+  for (int j = lane; j < Tx; j += 64) {
+    float v = 0.f;
+    if (j < L) {
+      v = fallback ? 2.f : d[j];
+      if (v < 0.f) v = 0.f;
+    }
+    d[j] = v;
+    total += (long)(v + 0.5f);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
+  if (lane == 0) mel_len[b] = total;
+}
+
 // one block = FR frames of one item; each wave copies FR/4 rows
 // output row of (b, t) = b * y_bs + t * y_ts (batch-major: Tm, 1; time-major: 1, B); pad_row (optional, C floats) is
 // what rows beyond an item's frames hold instead of zeros
@@ -150,6 +186,12 @@ __global__ __launch_bounds__(256) void ft_lr_bwd_kernel(const float* __restrict_
 }
 
 }  // namespace
+
+int ft_gen_durations_impl(float* dur, const long* x_len, int B, int Tx, long* mel_len, int* bad, hipStream_t stream) {
+  if (B <= 0) return FT_OK;
+  hipLaunchKernelGGL(ft_gen_durations_kernel, dim3(B), dim3(64), 0, stream, dur, x_len, Tx, mel_len, bad);
+  return ft_check_launch("gen_durations");
+}
 
 int ft_lr_scan_impl(float* dur, int B, int Tx, int* cum, int* total, hipStream_t stream) {
   FT_REQUIRE(B >= 0 && Tx >= 0, "lr_scan: bad dims");

@@ -563,6 +563,29 @@ int ft_gru_fwd(const float* xp, const float* whh_f, const float* whh_r, const fl
                     workspace_bytes, (hipStream_t)stream);
 }
 
+// nn.GRU over a packed batch (pack_padded_sequence semantics, as ft_lstm_fwd has them): item b runs over lens[b] steps,
+// the reverse direction from t = lens[b] - 1, and out is zero at t >= lens[b]
+int ft_gru_fwd_lens(const float* xp, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
+                    const long* lens, float* out, float* gates, int B, int T, int H, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  FT_REQUIRE(B > 0 && T >= 0 && H > 0 && lens != nullptr, "gru_fwd_lens: bad dims / null lens");
+  return rnn_fwd<3>(xp, whh_f, whh_r, bhh_f, bhh_r, out, nullptr, gates, lens, B, T, H, workspace, workspace_bytes,
+                    (hipStream_t)stream);
+}
+
+int ft_gru_layer_fwd_lens(const float* x, int in_f, const float* wih_f, const float* wih_r, const float* bih_f,
+                          const float* bih_r, float* xp, const float* whh_f, const float* whh_r, const float* bhh_f,
+                          const float* bhh_r, const long* lens, float* out, float* gates, int B, int T, int H,
+                          void* workspace, size_t workspace_bytes, unsigned* gate, int nchunks, int rev_lead,
+                          void* stream, void* side_stream) {
+  FT_REQUIRE(B > 0 && T >= 0 && H > 0 && in_f > 0 && lens != nullptr, "gru_layer_fwd_lens: bad dims / null lens");
+  const float* wih[2] = {wih_f, wih_r};
+  const float* bih[2] = {bih_f, bih_r};
+  return rnn_layer_fwd<3>(x, in_f, wih, bih, xp, whh_f, whh_r, bhh_f, bhh_r, lens, out, nullptr, gates, B, T, H,
+                          workspace, workspace_bytes, gate, nchunks, rev_lead, (hipStream_t)stream,
+                          (hipStream_t)side_stream);
+}
+
 int ft_gru_bwd(const float* dout, const float* out, const float* gates, const float* whhT_f, const float* whhT_r,
                float* dxp, float* dhp, float* carry, int B, int T, int H, void* workspace, size_t workspace_bytes,
                void* stream) {

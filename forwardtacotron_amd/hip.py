@@ -401,6 +401,20 @@ def conv1d_fwd(x: torch.Tensor, wp: torch.Tensor, relu: bool, Tout: Optional[int
     return y
 
 
+def conv1d_fwd_lens(x: torch.Tensor, wp: torch.Tensor, relu: bool, lens: torch.Tensor,
+                    scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+                    accumulate_into: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv1d_fwd at Tout = T whose epilogue stores zeros at t >= lens[b] (lens int64 [B], device)"""
+    _chk(x, 'x'); _chk(wp, 'wp'); _chk(lens, 'lens', torch.int64)
+    B, T, Cin = x.shape
+    k, Cout, _ = wp.shape
+    assert lens.numel() == B
+    y = accumulate_into if accumulate_into is not None else torch.empty(B, T, Cout, device=x.device, dtype=x.dtype)
+    _lib.call('ft_conv1d_fwd_lens', _p(x), Cin, _p(wp), _p(scale), _p(shift), _p(y), Cout, _p(lens), B, T, Cin, Cout, k,
+              int(relu), int(accumulate_into is not None), _stream())
+    return y
+
+
 def conv_bank_fwd(x: torch.Tensor, wp_all: torch.Tensor, K: int, C: int, relu: bool, Tout: int,
                   scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [B,T,Cin]; wp_all flat packed weights of members k=1..K -> ybank [B,Tout,K*C]"""
@@ -535,6 +549,18 @@ def lr_scan(dur: torch.Tensor):
     total = torch.empty(B, device=dur.device, dtype=torch.int32)
     _lib.call('ft_lr_scan', _p(dur), B, Tx, _p(cum), _p(total), _stream())
     return cum, total
+
+
+def gen_durations(dur: torch.Tensor, x_len: torch.Tensor):
+    """Per-item duration fallback, mask and clamp of a ragged inference batch, in place on dur [B,Tx] (ft_gen_durations).
+    -> (mel_len int64 [B], bad int32 [1]: non-zero if an x_len was outside [1, Tx])"""
+    _chk(dur, 'dur'); _chk(x_len, 'x_len', torch.int64)
+    B, Tx = dur.shape
+    assert x_len.numel() == B
+    mel_len = torch.empty(B, device=dur.device, dtype=torch.int64)
+    bad = torch.zeros(1, device=dur.device, dtype=torch.int32)
+    _lib.call('ft_gen_durations', _p(dur), _p(x_len), B, Tx, _p(mel_len), _p(bad), _stream())
+    return mel_len, bad
 
 
 def lr_expand(x: torch.Tensor, cum: torch.Tensor, Tm: int, want_src: bool = False):
@@ -730,6 +756,17 @@ def embedding_fwd(idx: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def embedding_fwd_lens(idx: torch.Tensor, lens: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """idx [B,T], lens int64 [B] (device) -> [B,T,C]: embedding_fwd with zeros at t >= lens[b], where idx is not read"""
+    _chk(idx, 'idx', torch.int64); _chk(lens, 'lens', torch.int64); _chk(w, 'w')
+    B, T = idx.shape
+    assert lens.numel() == B
+    V, C = w.shape
+    out = torch.empty(B, T, C, device=w.device, dtype=w.dtype)
+    _lib.call('ft_embedding_fwd_lens', _p(idx), _p(lens), _p(w), _p(out), B, T, C, V, _p(_err_flag(w.device)), _stream())
+    return out
+
+
 _err_flags = {}
 
 
@@ -836,6 +873,16 @@ def maxpool2_fwd(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def maxpool2_fwd_lens(x: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """maxpool2_fwd with zeros at t >= lens[b]"""
+    _chk(x, 'x'); _chk(lens, 'lens', torch.int64)
+    B, T, C = x.shape
+    assert lens.numel() == B
+    out = torch.empty_like(x)
+    _lib.call('ft_maxpool2_fwd_lens', _p(x), _p(lens), _p(out), B, T, C, _stream())
+    return out
+
+
 def maxpool2_bwd(dout: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     _chk(dout, 'dout')
     B, T, C = x.shape
@@ -909,6 +956,16 @@ def transpose_pad_fwd(x: torch.Tensor, Tout: int, pad: float) -> torch.Tensor:
     B, T, C = x.shape
     out = torch.empty(B, C, Tout, device=x.device, dtype=x.dtype)
     _lib.call('ft_transpose_pad_fwd', _p(x), _p(out), B, T, C, Tout, pad, _stream())
+    return out
+
+
+def transpose_pad_lens_fwd(x: torch.Tensor, lens: torch.Tensor, Tout: int, pad: float) -> torch.Tensor:
+    """[B,T,C] -> [B,C,Tout] with `pad` at t >= lens[b]"""
+    _chk(x, 'x'); _chk(lens, 'lens', torch.int64)
+    B, T, C = x.shape
+    assert lens.numel() == B
+    out = torch.empty(B, C, Tout, device=x.device, dtype=x.dtype)
+    _lib.call('ft_transpose_pad_lens_fwd', _p(x), _p(lens), _p(out), B, T, C, Tout, pad, _stream())
     return out
 
 
@@ -1025,6 +1082,18 @@ def gru_fwd(xp, whh_f, whh_r, bhh_f, bhh_r, H: int, save_gates: bool):
     return out, gates
 
 
+def gru_fwd_lens(xp, whh_f, whh_r, bhh_f, bhh_r, lens: torch.Tensor, H: int):
+    """gru_fwd over a packed batch: item b runs lens[b] steps (reverse from lens[b] - 1), out is zero beyond"""
+    _chk(xp, 'xp'); _chk(lens, 'lens', torch.int64)
+    T, B, _ = xp.shape
+    assert lens.numel() == B
+    out = torch.empty(T, B, 2 * H, device=xp.device, dtype=xp.dtype)
+    ws, nb = _rnn_workspace(3, B, H, xp.device)
+    _lib.call('ft_gru_fwd_lens', _p(xp), _p(whh_f), _p(whh_r), _p(bhh_f), _p(bhh_r), _p(lens), _p(out), None, B, T, H,
+              _p(ws), nb, _stream())
+    return out
+
+
 def gru_bwd(dout, out, gates, whhT_f, whhT_r, H: int):
     _chk(dout, 'dout')
     T, B, _ = out.shape
@@ -1104,6 +1173,24 @@ def gru_layer_fwd(x, wih_f, wih_r, bih_f, bih_r, whh_f, whh_r, bhh_f, bhh_r, H: 
               _p(bhh_f), _p(bhh_r), _p(out), _p(gates), B, T, H, _p(ws), nb, _p(gate), nchunks, _stream(),
               _proj_stream(dev).cuda_stream)
     return out, gates
+
+
+def gru_layer_fwd_lens(x, wih_f, wih_r, bih_f, bih_r, whh_f, whh_r, bhh_f, bhh_r, lens: torch.Tensor, H: int,
+                       nchunks: int):
+    """gru_layer_fwd over a packed batch (gru_fwd_lens)"""
+    _chk(x, 'x'); _chk(lens, 'lens', torch.int64)
+    B, T, I = x.shape
+    assert lens.numel() == B
+    dev = x.device
+    xp = torch.empty(T, B, 6 * H, device=dev, dtype=x.dtype)
+    out = torch.empty(T, B, 2 * H, device=dev, dtype=x.dtype)
+    gate = torch.empty(16, device=dev, dtype=torch.int32)
+    ws, nb = _rnn_workspace(3, B, H, dev)
+    lead = int(os.environ.get('FT_RNN_REV_LEAD', str(nchunks // 2)))
+    _lib.call('ft_gru_layer_fwd_lens', _p(x), I, _p(wih_f), _p(wih_r), _p(bih_f), _p(bih_r), _p(xp), _p(whh_f),
+              _p(whh_r), _p(bhh_f), _p(bhh_r), _p(lens), _p(out), None, B, T, H, _p(ws), nb, _p(gate), nchunks, lead,
+              _stream(), _proj_stream(dev).cuda_stream)
+    return out
 
 
 def lstm_bwd(dout, raw, cst, gates, whhT_f, whhT_r, lens: Optional[torch.Tensor], H: int):

@@ -54,6 +54,12 @@ class GRU(_RNNParams):
         y = ops.BiGRUFn.apply(x, *self.weights())
         return y if time_major_out else ops.BTTransposeFn.apply(y, False)
 
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, time_major_out: bool = False) -> torch.Tensor:
+        """pack_padded_sequence(x, lens) -> GRU -> pad_packed_sequence: item b runs over lens[b] steps (the reverse
+        direction from lens[b] - 1) and the result is zero at t >= lens[b].  Inference only (no graph)."""
+        y = ops.bigru_lens(x, lens, *self.weights())
+        return y if time_major_out else ops.BTTransposeFn.apply(y, False)
+
 
 class LSTM(_RNNParams):
     """nn.LSTM(in, H, batch_first=True, bidirectional=True) replacement with the pack/unpack semantics of
@@ -126,6 +132,19 @@ class BatchNormConv(nn.Module):
         acc = _c_clone(residual) if residual is not None else None
         return H.conv1d_fwd(x.contiguous(), wp, relu=self.relu is True, Tout=x.shape[1], scale=scale, shift=shift,
                             accumulate_into=acc)
+
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """eval forward of a ragged batch whose rows t >= lens[b] are zero on input: they are stored as zeros again
+        (scale * relu(conv) + shift is not zero there), so the next convolution reads zeros across an item's end"""
+        bn = self.bnorm
+        if self.training:
+            raise H._lib.FtError('BatchNormConv.forward_lens is the eval-mode (inference) path')
+        _eval_needs_no_grad(x, self.conv.weight)
+        scale, shift = H.bn_fold_eval(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+        wp = H.conv_pack_weight(self.conv.weight)
+        acc = _c_clone(residual) if residual is not None else None
+        return H.conv1d_fwd_lens(x.contiguous(), wp, relu=self.relu is True, lens=lens, scale=scale, shift=shift,
+                                 accumulate_into=acc)
 
 
 def _eval_needs_no_grad(x: torch.Tensor, w: torch.Tensor) -> None:
@@ -211,6 +230,26 @@ class CBHG(nn.Module):
         y = ops.highway_stack(y, list(self.highways))     # gates inside the GEMM epilogues (width % 32 == 0)
         return self.rnn(y, time_major_out=time_major_out)
 
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, time_major_out: bool = False) -> torch.Tensor:
+        """eval forward of a ragged batch: x [B,T,in] is zero at t >= lens[b] and so is the result; every valid row
+        is what the item gets alone at T = lens[b] (where each mask sits).  The bank's own store
+        needs no mask: its only reader across time is the max-pool, which masks its output."""
+        if self.training:
+            raise H._lib.FtError('CBHG.forward_lens is the eval-mode (inference) path')
+        K = len(self.bank_kernels)
+        C = self.conv1d_bank[0].conv.weight.shape[0]
+        gamma, beta, rm, rv = self._bank_flat()
+        B, T, Cin = x.shape
+        _eval_needs_no_grad(x, self.conv1d_bank[0].conv.weight)
+        scale, shift = H.bn_fold_eval(gamma, beta, rm, rv, self.conv1d_bank[0].bnorm.eps)
+        wp_all = torch.cat([H.conv_pack_weight(m.conv.weight).reshape(-1) for m in self.conv1d_bank])
+        y = H.maxpool2_fwd_lens(H.conv_bank_fwd(x, wp_all, K, C, relu=True, Tout=T, scale=scale, shift=shift), lens)
+        y = self.conv_project1.forward_lens(y, lens)
+        y = self.conv_project2.forward_lens(y, lens, residual=x)
+        y = ops.LinearFn.apply(y, self.pre_highway.weight, None)
+        y = ops.highway_stack(y, list(self.highways))
+        return self.rnn.forward_lens(y, lens, time_major_out=time_major_out)
+
 
 class SeriesPredictor(nn.Module):
     """forward_tacotron.py:14-39 ; returns [B,T,1]."""
@@ -229,6 +268,15 @@ class SeriesPredictor(nn.Module):
 
     def forward(self, x: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
         return conv_gru_predict(self, predictor_front(x, self.embedding), alpha)
+
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
+        """eval forward of a ragged batch: tokens at t >= lens[b] are ignored, the result [B,T,1] is zero there"""
+        B = x.shape[0]
+        y = H.embedding_fwd_lens(x, lens, self.embedding.weight)             # the pad id has a learned embedding
+        for conv in self.convs:
+            y = conv.forward_lens(y, lens)
+        y = self.rnn.forward_lens(y, lens, time_major_out=True)
+        return H.mask_rows(predictor_tail(y, self.lin, alpha, B), lens)      # (the Linear's bias)
 
 
 def conv_gru_predict(pred: nn.Module, x: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -336,6 +384,30 @@ class ForwardTacotron(AcousticModel):
         with torch.no_grad():
             return self._generate(x, alpha, pitch_function, energy_function)
 
+    def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, alpha=1.0,
+                       pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
+                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
+        """generate() of a RAGGED batch of sentences: for every item b the valid parts of the result equal
+        generate(x[b:b+1, :x_len[b]], alpha, ...) on the same model (to fp32 rounding; `mel_len` exactly).
+
+        x: int64 [B,Tx] on the device; entries at t >= x_len[b] are ignored, whatever they hold.  x_len: int64 [B], on the
+        host or the device, 1 <= x_len[b] <= Tx (anything else raises FtError).  pitch_function / energy_function get
+        [B,1,Tx] (zero at t >= x_len[b]) and must act PER TOKEN -- a function that mixes tokens or items (a mean over
+        the batch, a filter along t) breaks the per-item contract; their results are masked again.
+
+        -> mel, mel_post [B,n_mels,Tm] with Tm = max(mel_len) and padding_value at t >= mel_len[b]; mel_len int64 [B];
+        dur [B,Tx], pitch / energy [B,1,Tx], all three 0 at t >= x_len[b].  Per item: if the truncated durations of the
+        valid tokens sum to <= 0 they all become 2.0 (forward_tacotron.py:176-177); repeats are (clamp(dur, 0) + 0.5).long().
+        One host synchronisation (sizing Tm), as in generate().
+
+        An x_len that lives on the device is range-checked on the device: the FtError is raised only after the trunk up
+        to the decoder LSTM has been enqueued (behind that one synchronisation), and the flag travels through ONE pinned
+        host word kept on the module -- so a model must not run generate_batch with a device-side x_len from two
+        threads or on two streams at once (a host-side x_len is checked up front and has no such limit)."""
+        self.eval()
+        with torch.no_grad():
+            return self._generate_batch(x, x_len, alpha, pitch_function, energy_function)
+
     def generate_jit(self, x: torch.Tensor, alpha: float = 1.0, beta: float = 1.0) -> Dict[str, torch.Tensor]:
         """forward_tacotron.py:186-200: generate with the pitch scaled by beta.  Eager entry; the TorchScript surface
         (`torch.jit.script(model).generate_jit`, README.md:159-171 of the reference) is export.ScriptedForwardTacotron,
@@ -355,6 +427,64 @@ class ForwardTacotron(AcousticModel):
         mel_cl, post_cl = self._trunk(x, None, None, None, None, late_inputs=late_inputs)
         T = mel_cl.shape[1]
         return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0), **pred}
+
+    def _generate_batch(self, x, x_len, alpha, pitch_function, energy_function):
+        if x.dim() != 2 or x_len.dim() != 1 or x_len.numel() != x.shape[0] or x_len.dtype != torch.int64:
+            raise H._lib.FtError(f'generate_batch: x must be [B,Tx] and x_len int64 [B] (got {tuple(x.shape)}, '
+                                 f'{tuple(x_len.shape)} {x_len.dtype})')
+        B, Tx = x.shape
+        on_host = not x_len.is_cuda
+        if on_host and (B == 0 or int(x_len.min()) < 1 or int(x_len.max()) > Tx):
+            raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}] (got {x_len.tolist()})')
+        self._require_device(x)
+        x = x.contiguous()
+        xl = x_len.to(x.device).contiguous()
+
+        def predict():
+            # the three predictors, in generate()'s order; everything they hand on is zero at t >= x_len[b]
+            dur = self.dur_pred.forward_lens(x, xl, alpha=alpha).reshape(B, Tx)
+            mel_len, bad = H.gen_durations(dur, xl)               # per-item fallback, clamp; dur in its returned form
+            out = {'dur': dur, 'mel_len': mel_len, 'bad': bad}
+            for key, pred, fn in (('pitch', self.pitch_pred, pitch_function), ('energy', self.energy_pred, energy_function)):
+                v = fn(pred.forward_lens(x, xl).transpose(1, 2))                 # [B,1,Tx]
+                if tuple(v.shape) != (B, 1, Tx) or v.dtype != torch.float32 or not v.is_cuda:
+                    raise H._lib.FtError(f'generate_batch: {key}_function must return a float32 device tensor of shape '
+                                         f'[B,1,Tx] (got {tuple(v.shape)} {v.dtype})')
+                out[key] = H.mask_rows(v.reshape(B, Tx, 1).contiguous(), xl).reshape(B, 1, Tx)
+            return out
+
+        # the predictors only meet the trunk behind the prenet: side stream, as in _generate_fork
+        fork = self._fork_predictors(x.device, predict, overlap=os.environ.get('FT_GEN_OVERLAP', '1') == '1')
+        pred = fork[2]
+        h = H.embedding_fwd_lens(x, xl, self.embedding.weight)
+        h = self.prenet.forward_lens(h, xl, time_major_out=True)             # [Tx,B,2P], zero at t >= x_len[b]
+        self._join_predictors(fork)
+        bad_host = None
+        if not on_host:     # x_len never visited the host: its range check rides on the one synchronisation below
+            bad_host = self._bad_flag_host()
+            bad_host.copy_(pred['bad'], non_blocking=True)
+        mel_len = pred['mel_len']
+        h = ops.CondAddFn.apply(h, pred['pitch'].reshape(B, Tx), pred['energy'].reshape(B, Tx), self.pitch_proj.weight,
+                                self.pitch_proj.bias, self.energy_proj.weight, self.energy_proj.bias,
+                                self.pitch_strength, self.energy_strength, True)                 # -> [B,Tx,2P]
+        h = regulate_and_decode(self, h, pred['dur'], mel_len)               # packed LSTM; syncs to size Tm
+        if bad_host is not None and int(bad_host[0]) != 0:
+            raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}]')
+        # lin's bias (and the LSTM's padding_value) make the padded frames non-zero: mask before the postnet's convolutions
+        mel = H.mask_rows(ops.LinearFn.apply(h, self.lin.weight, self.lin.bias), mel_len)
+        post = self.postnet.forward_lens(mel, mel_len, time_major_out=True)  # [Tm,B,2Q]
+        post = ops.LinearFn.apply(post, self.post_proj.weight, None, B)      # -> [B,Tm,n_mels]
+        Tm = mel.shape[1]
+        pad = float(self.padding_value)
+        return {'mel': H.transpose_pad_lens_fwd(mel, mel_len, Tm, pad),
+                'mel_post': H.transpose_pad_lens_fwd(post.contiguous(), mel_len, Tm, pad), 'mel_len': mel_len,
+                'dur': pred['dur'], 'pitch': pred['pitch'], 'energy': pred['energy']}
+
+    def _bad_flag_host(self) -> torch.Tensor:
+        """pinned host word the device-side x_len range flag is copied into (asynchronously; read after the trunk's sync)"""
+        if getattr(self, '_bad_host', None) is None:
+            self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        return self._bad_host
 
     def _generate_mel(self, x: torch.Tensor, dur_hat: torch.Tensor, pitch_hat: torch.Tensor,
                       energy_hat: torch.Tensor) -> Dict[str, torch.Tensor]:

@@ -623,6 +623,18 @@ class BiGRUFn(Function):
         return (dx, *g)
 
 
+def bigru_lens(x, lens, w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r):
+    """pack_padded_sequence -> nn.GRU(bidirectional) -> pad_packed_sequence of a ragged inference batch (no graph):
+    x batch-major [B,T,I], lens int64 [B] on the device -> TIME-major [T,B,2H], zero at t >= lens[b]"""
+    x = _c(x)
+    Hh = w_hh_f.shape[1]
+    nch = H.rnn_overlap(x.shape[0] * x.shape[1], x.shape[1])
+    if nch:
+        return H.gru_layer_fwd_lens(x, w_ih_f, w_ih_r, b_ih_f, b_ih_r, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, Hh, nch)
+    xp = H.linear_multi_fwd(x, [w_ih_f, w_ih_r], [b_ih_f, b_ih_r], y_tm_B=x.shape[0])
+    return H.gru_fwd_lens(xp, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, Hh)
+
+
 class BiLSTMFn(Function):
     """pack_padded_sequence -> nn.LSTM(bidirectional) -> pad_packed_sequence(padding_value)
     (forward_tacotron.py:147-152); lens=None runs over the padded length (:224)."""

@@ -112,6 +112,13 @@ int ft_pack_weights(const FtPackDesc* descs, int n, long total_tiles, void* stre
 int ft_conv1d_fwd(const float* x, long ldx, const float* wp, const float* scale, const float* shift, float* y,
                   long ldy, int B, int T, int Cin, int Cout, int k, int Tout, int relu, int accumulate,
                   void* stream);
+/* The eval-mode convolution of a RAGGED inference batch (ForwardTacotron.generate_batch; no reference counterpart: the
+ * reference's generate, forward_tacotron.py:167-234, passes no lengths).  As ft_conv1d_fwd with Tout = T, and the
+ * epilogue stores exactly 0 at rows t >= lens[b] (int64 [B], device) -- relu(conv) * scale + shift of BatchNormConv
+ * (common_layers.py:55-57) is non-zero there, and the next convolution would read it across the item's end. */
+int ft_conv1d_fwd_lens(const float* x, long ldx, const float* wp, const float* scale, const float* shift, float* y,
+                       long ldy, const long* lens, int B, int T, int Cin, int Cout, int k, int relu, int accumulate,
+                       void* stream);
 /* CBHG conv1d_bank (common_layers.py:72-76,97-102): members k=1..K (K<=16) in ONE launch; member i writes
  * ybank[:, :, i*C:(i+1)*C] of ybank[B,Tout,K*C]; wp_all = packed member weights back to back. */
 int ft_conv_bank_fwd(const float* x, long ldx, const float* wp_all, const float* scale, const float* shift,
@@ -213,6 +220,11 @@ int ft_relu_bwd(const float* dy, const float* y, float* dx, long n, void* stream
 /* scan: clamps dur[dur<0]=0 IN PLACE (as the reference does), r=(long)(dur+0.5); cum[b][0..Tx] exclusive
  * frame offsets (int32, [B,Tx+1]); total[b] = cum[b][Tx].  Caller reads max(total) to size the output. */
 int ft_lr_scan(float* dur, int B, int Tx, int* cum, int* total, void* stream);
+/* Durations of a ragged inference batch, per item (forward_tacotron.py:174-177 with common_layers.py:17-24 applied to
+ * item b alone, L = x_len[b]): if sum_{j<L} trunc(dur[b,j]) <= 0 every token j < L gets 2.0; then, in place,
+ * dur[b,j] = 0 at j >= L and negatives are clamped to 0; mel_len[b] (int64) = sum_j (long)(dur[b,j] + 0.5), the total
+ * ft_lr_scan gives.  An x_len[b] outside [1, Tx] sets *bad (int32, device; never cleared here) and is clamped. */
+int ft_gen_durations(float* dur, const long* x_len, int B, int Tx, long* mel_len, int* bad, void* stream);
 /* y[b,t,:] = x[b,tok(t),:] for t < total[b], else 0; optional src_idx[B,Tm] (token or -1). Bit-exact copy. */
 int ft_lr_expand(const float* x, const int* cum, float* y, int* src_idx, int B, int Tx, int Tm, int C,
                  void* stream);
@@ -312,6 +324,12 @@ int ft_copy_segments(const float* const* src, float* const* dst, const long* len
 /* out[row,:] = w[idx[row],:] ; *err_flag set to 1 on an out-of-range index (row zero-filled) */
 int ft_embedding_fwd(const long* idx, const float* w, float* out, long rows, int C, int V, int* err_flag,
                      void* stream);
+/* The embedding of a RAGGED inference batch (ForwardTacotron.generate_batch; the reference's generate,
+ * forward_tacotron.py:167-234, passes no lengths): idx [B,T], lens int64 [B] (device).  out[b,t,:] = w[idx[b,t],:] at
+ * t < lens[b] and exactly 0 at t >= lens[b], where idx is NOT read: the padding may hold any id, also one outside
+ * [0, V), and does not raise *err_flag. */
+int ft_embedding_fwd_lens(const long* idx, const long* lens, const float* w, float* out, int B, int T, int C, int V,
+                          int* err_flag, void* stream);
 /* backward: onehot[rows,V] = (idx == v); dW[V,C] = onehot^T * dout via ft_linear_bwd_weight (ordered, reproducible) */
 int ft_onehot(const long* idx, float* out, long rows, int V, void* stream);
 
@@ -338,6 +356,9 @@ int ft_highway_bwd_data(const float* d12, const float* w1, const float* w2, int 
 
 /* ---- MaxPool1d(kernel 2, stride 1, padding 1)[:T] (common_layers.py:78,105): out[t]=max(x[t-1],x[t]) ---- */
 int ft_maxpool2_fwd(const float* x, float* out, int B, int T, int C, void* stream);
+/* with per-item lengths (ragged inference batch): out[b,t] = 0 at t >= lens[b] -- row lens[b] of the plain form holds
+ * x[lens[b]-1], which CBHG.conv_project1 (common_layers.py:107) would read from row lens[b]-1 */
+int ft_maxpool2_fwd_lens(const float* x, const long* lens, float* out, int B, int T, int C, void* stream);
 int ft_maxpool2_bwd(const float* dout, const float* x, float* dx, int B, int T, int C, void* stream);
 
 /* ---- pitch/energy conditioning (forward_tacotron.py:111-112,137-143): Conv1d(1->C,k3,p1)+bias, scaled add */
@@ -365,6 +386,9 @@ int ft_cross_entropy_bwd(const float* logits, const long* target, const float* i
 /* ---- output layout + ForwardTacotron._pad (forward_tacotron.py:155,159,161-162,236-239) ---------------- */
 /* out[b,c,t] = t < T ? x[b,t,c] : pad, t < Tout   ([B,T,C] -> [B,C,Tout]) ; bwd is the masked transpose back */
 int ft_transpose_pad_fwd(const float* x, float* out, int B, int T, int C, int Tout, float pad, void* stream);
+/* per-item lengths (ragged inference batch): out[b,c,t] = t < min(lens[b], T) ? x[b,t,c] : pad, t < Tout */
+int ft_transpose_pad_lens_fwd(const float* x, const long* lens, float* out, int B, int T, int C, int Tout, float pad,
+                              void* stream);
 int ft_transpose_pad_bwd(const float* dout, float* dx, int B, int T, int C, int Tout, void* stream);
 
 /* ---- MaskedL1 (trainer/common.py:69-92) on [B,C,T] with int64 lens ----------------------------------- */
@@ -423,6 +447,12 @@ int ft_rnn_waited_launches(void);
 int ft_gru_fwd(const float* xp, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
                float* out, float* gates, int B, int T, int H, void* workspace, size_t workspace_bytes,
                void* stream);
+/* pack_padded_sequence -> nn.GRU -> pad_packed_sequence (common_layers.py:89,123 over a ragged inference batch; the
+ * semantics of ft_lstm_fwd): item b runs over lens[b] (int64 [B], device) steps in both directions, the reverse one
+ * from t = lens[b] - 1; out is ZERO at t >= lens[b]. */
+int ft_gru_fwd_lens(const float* xp, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
+                    const long* lens, float* out, float* gates, int B, int T, int H, void* workspace,
+                    size_t workspace_bytes, void* stream);
 /* BPTT: dout[T,B,2H]; whhT = W_hh^T [H,3H]; dxp / dhp [T,B,2*3H] = d(pre-activations) wrt input / hidden
  * projections; carry [B,2,H] scratch.  Weight grads follow from ft_linear_bwd_weight on dxp / dhp. */
 int ft_gru_bwd(const float* dout, const float* out, const float* gates, const float* whhT_f, const float* whhT_r,
@@ -465,6 +495,12 @@ int ft_gru_layer_fwd(const float* x, int in_f, const float* wih_f, const float* 
                      const float* bih_r, float* xp, const float* whh_f, const float* whh_r, const float* bhh_f,
                      const float* bhh_r, float* out, float* gates, int B, int T, int H, void* workspace,
                      size_t workspace_bytes, unsigned* gate, int nchunks, void* stream, void* side_stream);
+/* ft_gru_layer_fwd over a packed batch (ft_gru_fwd_lens); rev_lead as in ft_lstm_layer_fwd */
+int ft_gru_layer_fwd_lens(const float* x, int in_f, const float* wih_f, const float* wih_r, const float* bih_f,
+                          const float* bih_r, float* xp, const float* whh_f, const float* whh_r, const float* bhh_f,
+                          const float* bhh_r, const long* lens, float* out, float* gates, int B, int T, int H,
+                          void* workspace, size_t workspace_bytes, unsigned* gate, int nchunks, int rev_lead,
+                          void* stream, void* side_stream);
 int ft_fill_padded(const float* raw, const long* lens, float* out, int B, int T, int C, float pad, void* stream);
 int ft_mask_rows(const float* src, const long* lens, float* dst, int B, int T, int C, void* stream);
 /* [B,T,C] -> [T,B,C] (dst_time_major = 1) or back (0) */
