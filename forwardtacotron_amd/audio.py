@@ -8,6 +8,7 @@ of preprocess.py:78-89 `Preprocessor._convert_file` (trim_silence, peak normalis
     out = dsp.preprocess_batch([y0, y1, ...])        # ragged batch, one pass, no host synchronisation inside
     items = split_items(out)                         # per-item numpy arrays for np.save (this is the one sync)
     wav = dsp.griffinlim(mel)                        # vocoder.GriffinLim, which shares the bases
+    wavs = split_wavs(dsp.griffinlim_batch(mel, mel_len))    # a ragged batch of mels (generate_batch's) -> wavs
 
 HIP device only, like vocoder.GriffinLim: without a device the constructor raises FtError.  The wavs are first gathered
 into one zero-padded [B, ld] device buffer (numpy inputs: one host-to-device copy; device tensors: a fill and one copy
@@ -175,6 +176,15 @@ class DSP:
         wav = self.gl.griffinlim(mel, n_iter, **kw)
         return wav.cpu().numpy() if isinstance(mel, np.ndarray) else wav
 
+    def griffinlim_batch(self, mel: Wav, mel_len: Wav, n_iter: int = 32, **kw) -> Dict[str, Wav]:
+        """vocoder.GriffinLim.griffinlim_batch: mel [B, n_mels, Tmax], mel_len [B] -> {'wav' [B, hop * (Tmax - 1)],
+        'wav_len' [B]}; numpy in -> numpy out (one copy each way), device tensors in -> device tensors out"""
+        if not isinstance(mel, np.ndarray):
+            return self.gl.griffinlim_batch(mel, mel_len, n_iter, **kw)
+        dev = torch.from_numpy(np.ascontiguousarray(mel, dtype=np.float32)).to(self.device)
+        out = self.gl.griffinlim_batch(dev, torch.from_numpy(np.ascontiguousarray(mel_len, dtype=np.int64)), n_iter, **kw)
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
 
 def sparse_mel_basis(basis: np.ndarray):
     """dense [n_mels, F] triangular basis -> (weights [nnz] fp32, meta [n_mels, 3] int32 = first bin, bin count, offset):
@@ -206,4 +216,11 @@ def split_items(out: Dict[str, torch.Tensor]) -> List[Dict[str, Any]]:
     return items
 
 
-__all__ = ['DSP', 'MEL_PAD_VALUE', 'sparse_mel_basis', 'split_items']
+def split_wavs(out: Dict[str, Wav]) -> List[np.ndarray]:
+    """griffinlim_batch's result -> the per-item wavs as numpy arrays cut to wav_len[b].  Copies to the host: this is the
+    synchronisation point."""
+    wav, wav_len = (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v) for v in (out['wav'], out['wav_len']))
+    return [np.ascontiguousarray(wav[b, :int(wav_len[b])]) for b in range(wav.shape[0])]
+
+
+__all__ = ['DSP', 'MEL_PAD_VALUE', 'sparse_mel_basis', 'split_items', 'split_wavs']

@@ -1271,3 +1271,64 @@ def mel_project(spec: torch.Tensor, Fp: int, rows_per_item: int, mel_len: torch.
     _lib.call('ft_mel_project', _p(spec), spec.shape[1], Fp, rows_per_item, _p(mel_len), _p(w), _p(meta), w.numel(),
               n_mels, B, Tmax, int(log_clip), float(pad_value), _p(mel), _stream())
     return mel
+
+
+# ---------------------------------------------------------------------------------------------------
+# Griffin-Lim on a ragged batch (csrc/ft_dsp.hip, the *_ragged entries; the public interface is
+# vocoder.GriffinLim.griffinlim_batch).  Item b owns rows [b * Tcap, (b + 1) * Tcap); mel_len int64 [B] on the device.
+# ---------------------------------------------------------------------------------------------------
+def gl_exp_transpose_ragged(mel: torch.Tensor, mel_len: torch.Tensor, Tcap: int, err: Optional[torch.Tensor] = None,
+                            alloc=torch.empty) -> torch.Tensor:
+    """log-mel [B, C, Tmax] -> exp, frames-major [B * Tcap, C]; rows n >= mel_len[b] are zero"""
+    _chk(mel, 'mel'); _chk(mel_len, 'mel_len', torch.int64)
+    B, C, Tmax = mel.shape
+    out = alloc(B * Tcap, C, dtype=torch.float32, device=mel.device)
+    _lib.call('ft_gl_exp_transpose_ragged', _p(mel), _p(mel_len), _p(out), B, C, Tmax, Tcap, _p(err), _stream())
+    return out
+
+
+def gl_relu(x: torch.Tensor) -> torch.Tensor:
+    """x = max(x, 0) in place"""
+    _chk(x, 'x')
+    _lib.call('ft_gl_relu', _p(x), x.numel(), _stream())
+    return x
+
+
+def gl_init_ragged(S: torch.Tensor, mel_len: torch.Tensor, B: int, Tcap: int, Tmax: int,
+                   u: Optional[torch.Tensor] = None, seed: int = 0, err: Optional[torch.Tensor] = None,
+                   want_u: bool = False, alloc=torch.empty):
+    """S [B * Tcap, Fp] -> proj [B * Tcap, 2 Fp] = S exp(2 pi i u), zero rows at n >= mel_len[b]; u given, or drawn on the
+    device from (seed, n, m).  want_u: also return the u that was used -> (proj, u)"""
+    _chk(S, 'S'); _chk(mel_len, 'mel_len', torch.int64)
+    rows, Fp = S.shape
+    if rows != B * Tcap or (u is not None and tuple(u.shape) != (rows, Fp)):
+        raise _lib.FtError(f'gl_init_ragged: S (and init_u) must be [B * Tcap = {B * Tcap}, Fp], got {tuple(S.shape)}'
+                           + ('' if u is None else f' and {tuple(u.shape)}'))
+    if u is not None:
+        _chk(u, 'init_u')
+    proj = alloc(rows, 2 * Fp, dtype=torch.float32, device=S.device)
+    u_out = alloc(rows, Fp, dtype=torch.float32, device=S.device) if want_u else None
+    _lib.call('ft_gl_init_ragged', _p(u), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(S), _p(mel_len), _p(proj), _p(u_out), B,
+              Tcap, Tmax, Fp, _p(err), _stream())
+    return (proj, u_out) if want_u else proj
+
+
+def gl_phase_ragged(rebuilt: torch.Tensor, tprev: torch.Tensor, S: torch.Tensor, mel_len: torch.Tensor,
+                    proj: torch.Tensor, B: int, Tcap: int, Tmax: int, alpha: float, has_prev: bool) -> None:
+    """the fast Griffin-Lim update in place on proj / tprev [B * Tcap, 2 Fp]; rows n >= mel_len[b] become zero"""
+    _lib.call('ft_gl_phase_ragged', _p(rebuilt), _p(tprev), _p(S), _p(mel_len), _p(proj), B, Tcap, Tmax, S.shape[1],
+              float(alpha), int(has_prev), _stream())
+
+
+def overlap_add_ragged(frames: torch.Tensor, w2: torch.Tensor, mel_len: torch.Tensor, B: int, Tcap: int, Tmax: int,
+                       n_fft: int, hop: int, as_wav: bool = False, alloc=torch.empty) -> torch.Tensor:
+    """frames [B * Tcap, n_fft] -> the packed padded signals [B * Tcap * hop + n_fft] (the next STFT's operand), or with
+    as_wav the signals themselves [B, hop * (Tmax - 1)], zero beyond hop * (mel_len[b] - 1)"""
+    if as_wav:
+        out = alloc(B, hop * (Tmax - 1), dtype=torch.float32, device=frames.device)
+    else:
+        out = alloc(B * Tcap * hop + n_fft, dtype=torch.float32, device=frames.device)
+    if out.numel():                            # Tmax == 1: every wav is empty
+        _lib.call('ft_overlap_add_ragged', _p(frames), _p(w2), _p(mel_len), None if as_wav else _p(out),
+                  _p(out) if as_wav else None, B, Tcap, Tmax, n_fft, hop, _stream())
+    return out

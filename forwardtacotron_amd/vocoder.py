@@ -13,6 +13,12 @@ one GEMM against the [n_fft, 2F] inverse basis (window folded in again) followed
 phase update and the mel pseudo-inverse steps are small element-wise kernels (csrc/ft_dsp.hip).  32 iterations on a
 ~800-frame utterance are 64 GEMMs of 1.7 GFLOP.
 
+A RAGGED BATCH goes through `griffinlim_batch(mel, mel_len)` (generate_batch's 'mel_post' and 'mel_len'): every item
+sits at a fixed stride of Tcap rows in one packed buffer (`gl_batch_geometry`), so each transform of every iteration is
+ONE GEMM for the whole batch and each element-wise step ONE launch (the *_ragged kernels of csrc/ft_dsp.hip, lengths
+read on the device).  Every GEMM of that path is `ft_linear_multi_fwd_as` with the fixed `_AS_ROWS`, so the kernel --
+and the rounding -- never depends on the batch: an item's samples are bit-identical alone and inside any batch.
+
 PARITY UNPINNED against the reference: librosa is not installed in this image and the reference ships no audio
 fixture.  The oracle is oracle/gl_oracle.py (numpy, FFT-based -- an independent route to the same published algorithm);
 tests/test_gpu_vocoder.py compares step by step.  Differences from librosa that are ours, not the reference's:
@@ -20,6 +26,8 @@ tests/test_gpu_vocoder.py compares step by step.  Differences from librosa that 
     followed by `nnls_iter` projected-gradient steps (GEMMs), see the oracle's header;
   * the random initial phases come from numpy's default_rng(seed) on the host (librosa: default_rng(random_state)).
 """
+import ctypes
+import os
 from typing import Any, Dict, Optional, Union
 
 import numpy as np
@@ -50,6 +58,44 @@ def slaney_mel_basis(sr: int, n_fft: int, n_mels: int, fmin: float, fmax: float)
     down = (pts[2:, None] - freqs[None, :]) / (pts[2:] - pts[1:-1])[:, None]
     w = np.clip(np.minimum(up, down), 0, None)
     return w * (2.0 / (pts[2:] - pts[:-2]))[:, None]
+
+
+# every GEMM of the batched path is rounded like a launch over this many rows (the 128 x 128 tile), whatever the batch holds
+_AS_ROWS = 1 << 20
+
+
+def _empty(*shape, dtype=torch.float32, device=None) -> torch.Tensor:
+    """every device buffer of the batched path is allocated here (tests replace it with a poison-filling allocator)"""
+    return torch.empty(*shape, dtype=dtype, device=device)
+
+
+def _alloc(*shape, **kw) -> torch.Tensor:
+    return _empty(*shape, **kw)               # looked up at call time, so a replaced _empty takes effect
+
+
+def gl_batch_geometry(B: int, Tmax: int, n_fft: int, hop: int) -> Dict[str, int]:
+    """Layout of a ragged batch of B items of at most Tmax frames (pure host arithmetic).  Item b owns rows
+    [b * Tcap, (b + 1) * Tcap) of every frame-major buffer and samples [b * stride, (b + 1) * stride) of the packed
+    signal, stride = Tcap * hop >= n_fft + hop * (Tmax - 1) = its longest padded signal; the packed signal has an n_fft
+    zero tail so that the last row of the one STFT GEMM (ldx = hop) reads inside the buffer."""
+    if B < 1 or Tmax < 1 or hop < 1 or n_fft < hop:
+        raise _lib.FtError(f'gl_batch_geometry: bad sizes (B {B}, Tmax {Tmax}, n_fft {n_fft}, hop {hop})')
+    Tcap = Tmax - 1 + -(-n_fft // hop)
+    rows = B * Tcap
+    return {'Tcap': Tcap, 'rows': rows, 'stride': Tcap * hop, 'packed': rows * hop + n_fft,
+            'last_read_end': (rows - 1) * hop + n_fft, 'wav_ld': hop * (Tmax - 1)}
+
+
+def window_sumsquare_f32(w2: np.ndarray, N: int, n_fft: int, hop: int) -> np.ndarray:
+    """What ft_overlap_add_ragged divides an N-frame item by, restated on the host: for every sample t of the padded
+    signal, the fp32 sum of w2[t - n * hop] over the frames n < N that cover t, in ascending n (w2 = the squared window
+    rounded to fp32).  Head, periodic middle and tail -- and their overlap for N < n_fft / hop -- all come out of the one
+    rule.  At most ceil(n_fft / hop) positive terms: within (1 + ceil(n_fft / hop)) * 2^-24 relative of the exact sum."""
+    w2 = np.asarray(w2, dtype=np.float32)
+    out = np.zeros(n_fft + hop * (N - 1), dtype=np.float32)
+    for n in range(N):                         # ascending n: every sample adds its frames in the kernel's order
+        out[n * hop:n * hop + n_fft] += w2
+    return out
 
 
 class GriffinLim:
@@ -186,6 +232,147 @@ class GriffinLim:
             mel = mel[0]
         return self.griffinlim_from_stft(self.mel_to_stft(mel), n_iter, init_u, seed)
 
+    # ---- ragged batch --------------------------------------------------------------------------------
+    def _batch_ctx(self):
+        """operands of the forced-tile GEMMs (host arrays of device pointers) and the fp32 squared window"""
+        ctx = getattr(self, '_bctx', None)
+        if ctx is None:
+            if self.n_fft % 8:
+                raise _lib.FtError('griffinlim_batch: n_fft must be a multiple of 8')
+            mk = lambda w: (H._ptr_array([w]), (ctypes.c_int * 1)(0), (ctypes.c_int * 1)(int(w.shape[0])), w)
+            ctx = {k: mk(w) for k, w in (('pinv', self.mel_pinv), ('basis', self.mel_basis), ('basis_t', self.mel_basis_t),
+                                         ('fwd', self.w_fwd), ('inv', self.w_inv))}
+            ctx['w2'] = torch.from_numpy((self.window ** 2).astype(np.float32)).to(self.device)
+            ctx['bad_host'] = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._bctx = ctx
+        return ctx
+
+    def _gemm_as(self, x: torch.Tensor, ldx: int, key: str, rows: int, in_f: int) -> torch.Tensor:
+        """y [rows, out_f] = x (row stride ldx) * w^T on the kernel a launch over _AS_ROWS rows takes"""
+        wp, col0, outf, w = self._batch_ctx()[key]
+        y = _alloc(rows, int(w.shape[0]), device=self.device)
+        c = ctypes.c_void_p
+        _lib.call('ft_linear_multi_fwd_as', x.data_ptr(), ldx, 1, ctypes.cast(wp, c), None, y.data_ptr(), int(w.shape[0]),
+                  ctypes.cast(col0, c), ctypes.cast(outf, c), rows, in_f, _AS_ROWS, H._stream())
+        return y
+
+    def _batch_lens(self, what: str, mel_len: torch.Tensor, B: int, Tmax: int):
+        """-> (mel_len on the device, error flag or None).  A host-side mel_len is checked here, before any launch; a
+        device-side one gets a zeroed device flag that the kernels raise."""
+        if not isinstance(mel_len, torch.Tensor) or mel_len.dim() != 1 or mel_len.numel() != B \
+                or mel_len.dtype != torch.int64:
+            raise _lib.FtError(f'{what}: mel_len must be an int64 tensor [B = {B}]')
+        if B < 1 or Tmax < 1:
+            raise _lib.FtError(f'{what}: an empty batch')
+        if not mel_len.is_cuda:
+            if int(mel_len.min()) < 1 or int(mel_len.max()) > Tmax:
+                raise _lib.FtError(f'{what}: every mel_len must be in [1, Tmax = {Tmax}] (got {mel_len.tolist()})')
+            return mel_len.pin_memory().to(self.device, non_blocking=True), None
+        return mel_len.contiguous(), torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _batch_raise(self, what: str, err: Optional[torch.Tensor], Tmax: int) -> None:
+        if err is not None:
+            bad = self._batch_ctx()['bad_host']
+            bad.copy_(err, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            if int(bad[0]) != 0:
+                raise _lib.FtError(f'{what}: every mel_len must be in [1, Tmax = {Tmax}]')
+
+    def _mel_to_stft_batch(self, mel: torch.Tensor, ml: torch.Tensor, err: Optional[torch.Tensor]) -> torch.Tensor:
+        B, C, Tmax = mel.shape
+        g = gl_batch_geometry(B, Tmax, self.n_fft, self.hop)
+        rows, st = g['rows'], H._stream()
+        M = H.gl_exp_transpose_ragged(mel, ml, g['Tcap'], err, alloc=_alloc)          # [rows, C], zero rows at n >= N_b
+        X = H.gl_relu(self._gemm_as(M, C, 'pinv', rows, C))                           # clipped least squares [rows, Fp]
+        for _ in range(self.nnls_iter):                                              # row-local: zero rows stay zero
+            R = self._gemm_as(X, self.Fp, 'basis', rows, self.Fp)                     # [rows, n_mels]
+            _lib.call('ft_sub', R.data_ptr(), M.data_ptr(), R.data_ptr(), R.numel(), st)
+            G = self._gemm_as(R, C, 'basis_t', rows, C)                               # [rows, Fp]
+            _lib.call('ft_nnls_step', X.data_ptr(), G.data_ptr(), self.inv_lip, X.numel(), st)
+        return X
+
+    def _check_mel_batch(self, what: str, mel: torch.Tensor) -> torch.Tensor:
+        if not isinstance(mel, torch.Tensor) or mel.dim() != 3:
+            raise _lib.FtError(f'{what}: mel must be a [B, n_mels, Tmax] tensor')
+        if mel.dtype != torch.float32:
+            raise _lib.FtError(f'{what}: mel must be float32, got {mel.dtype}')
+        if mel.shape[1] != self.n_mels:
+            raise _lib.FtError(f'{what}: expected {self.n_mels} mel channels, got {mel.shape[1]}')
+        return mel.to(self.device).contiguous()
+
+    def mel_to_stft_batch(self, mel: torch.Tensor, mel_len: torch.Tensor) -> torch.Tensor:
+        """log-mel [B, n_mels, Tmax], mel_len int64 [B] -> magnitudes packed [B * Tcap, Fp] (item b's frame n at row
+        b * Tcap + n, Tcap from gl_batch_geometry); the rows n >= mel_len[b] of an item are all zero"""
+        mel = self._check_mel_batch('mel_to_stft_batch', mel)
+        ml, err = self._batch_lens('mel_to_stft_batch', mel_len, mel.shape[0], mel.shape[2])
+        X = self._mel_to_stft_batch(mel, ml, err)
+        self._batch_raise('mel_to_stft_batch', err, mel.shape[2])
+        return X
+
+    def _gl_from_stft_batch(self, S, ml, B, Tmax, n_iter, init_u, seed, err) -> Dict[str, torch.Tensor]:
+        g = gl_batch_geometry(B, Tmax, self.n_fft, self.hop)
+        Tcap, rows, Fp = g['Tcap'], g['rows'], self.Fp
+        H._chk(S, 'S')
+        if tuple(S.shape) != (rows, Fp):
+            raise _lib.FtError(f'griffinlim_from_stft_batch: expected S [B * Tcap = {rows}, Fp = {Fp}], got {tuple(S.shape)}')
+        if init_u is None and seed is None:
+            seed = int.from_bytes(os.urandom(8), 'little')
+        w2 = self._batch_ctx()['w2']
+        proj = H.gl_init_ragged(S, ml, B, Tcap, Tmax, u=init_u, seed=seed or 0, err=err, alloc=_alloc)
+        tprev = _alloc(rows, 2 * Fp, device=self.device)
+        alpha = self.momentum / (1.0 + self.momentum)
+        ola = lambda fr, as_wav: H.overlap_add_ragged(fr, w2, ml, B, Tcap, Tmax, self.n_fft, self.hop, as_wav, alloc=_alloc)
+        for it in range(n_iter):
+            frames = self._gemm_as(proj, 2 * Fp, 'inv', rows, 2 * Fp)                 # inverse STFT of every item
+            ypad = ola(frames, False)
+            rebuilt = self._gemm_as(ypad, self.hop, 'fwd', rows, self.n_fft)          # frames read in place, ldx = hop
+            H.gl_phase_ragged(rebuilt, tprev, S, ml, proj, B, Tcap, Tmax, alpha, it > 0)
+        wav = ola(self._gemm_as(proj, 2 * Fp, 'inv', rows, 2 * Fp), True)
+        return {'wav': wav, 'wav_len': (ml - 1) * self.hop}
+
+    def griffinlim_from_stft_batch(self, S: torch.Tensor, mel_len: torch.Tensor, Tmax: int, n_iter: int = 32,
+                                   init_u: Optional[torch.Tensor] = None, seed: Optional[int] = None
+                                   ) -> Dict[str, torch.Tensor]:
+        """S packed [B * Tcap, Fp] (mel_to_stft_batch's layout for this Tmax) -> {'wav' [B, hop * (Tmax - 1)], zero at
+        j >= wav_len[b]; 'wav_len' int64 [B] = hop * (mel_len - 1)}.  init_u [B * Tcap, Fp] in [0, 1): the initial phases
+        / (2 pi) in the same layout (rows n >= mel_len[b] are ignored); without it they are drawn on the device from
+        (seed, frame, bin) -- see griffinlim_batch."""
+        B = int(mel_len.numel()) if isinstance(mel_len, torch.Tensor) else 0
+        ml, err = self._batch_lens('griffinlim_from_stft_batch', mel_len, B, int(Tmax))
+        out = self._gl_from_stft_batch(S, ml, B, int(Tmax), n_iter, init_u, seed, err)
+        self._batch_raise('griffinlim_from_stft_batch', err, int(Tmax))
+        return out
+
+    def griffinlim_batch(self, mel: torch.Tensor, mel_len: torch.Tensor, n_iter: int = 32, seed: Optional[int] = None,
+                         init_u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """griffinlim() of a RAGGED batch of mels (generate_batch's 'mel_post' and 'mel_len'): item b of the result is
+        what griffinlim gives mel[b, :, :mel_len[b]] alone, to fp32 rounding, given the same initial phases.
+
+        mel: float32 [B, n_mels, Tmax] on the device; entries at t >= mel_len[b] are ignored, whatever they hold
+        (padding_value, NaN, Inf).  mel_len: int64 [B], on the host or the device, 1 <= mel_len[b] <= Tmax.
+        -> {'wav': float32 [B, hop * (Tmax - 1)], zero at j >= wav_len[b]; 'wav_len': int64 [B] = hop * (mel_len - 1)}.
+
+        Two guarantees are exact.  (1) With the same `seed` or `init_u`, an item's wav_len[b] samples are bit-identical
+        whether it is passed alone (B = 1, Tmax = its own length) or inside any batch, at any position: every GEMM runs
+        on one fixed kernel and every other step is per frame, bin or sample.  (2) A NaN or Inf item, or NaN in the
+        padding of mel, changes no other item's bits.  The phases of `seed` are drawn on the device by a counter-based
+        generator keyed on (seed, frame, bin) (include/fwdtaco_hip.h: ft_gl_init_ragged); they deliberately differ from
+        the numpy draw of griffinlim(seed=...).  seed=None takes a fresh seed from the operating system.
+
+        Nothing is sized from device values and, with mel_len on the host, nothing synchronises.  A mel_len that lives
+        on the device is range-checked on the device (lengths are clamped inside the kernels, so nothing indexes out of
+        bounds): the FtError is raised at the end of the call, after one synchronisation, and the flag travels through
+        ONE pinned host word kept on this object -- so one GriffinLim must not run the batched calls with a device-side
+        mel_len from two threads or on two streams at once (a host-side mel_len is checked up front and has no such
+        limit)."""
+        mel = self._check_mel_batch('griffinlim_batch', mel)
+        B, _, Tmax = mel.shape
+        ml, err = self._batch_lens('griffinlim_batch', mel_len, B, Tmax)
+        S = self._mel_to_stft_batch(mel, ml, err)
+        out = self._gl_from_stft_batch(S, ml, B, Tmax, n_iter, init_u, seed, err)
+        self._batch_raise('griffinlim_batch', err, Tmax)
+        return out
+
 
 def spectral_convergence(gl: GriffinLim, wav: torch.Tensor, S: torch.Tensor) -> float:
     """|| |STFT(wav)| - S ||_F / ||S||_F on the device (diagnostic)"""
@@ -195,4 +382,4 @@ def spectral_convergence(gl: GriffinLim, wav: torch.Tensor, S: torch.Tensor) -> 
     return float(torch.linalg.norm(mag - S[:N]) / torch.linalg.norm(S[:N]).clamp_min(1e-30))
 
 
-__all__ = ['GriffinLim', 'slaney_mel_basis', 'spectral_convergence']
+__all__ = ['GriffinLim', 'gl_batch_geometry', 'slaney_mel_basis', 'spectral_convergence', 'window_sumsquare_f32']

@@ -602,6 +602,40 @@ int ft_gl_init(const float* u, const float* S, float* proj, int N, int Fp, void*
 int ft_gl_phase(const float* rebuilt, float* tprev, const float* S, float* proj, int N, int Fp, float alpha,
                 int has_prev, void* stream);
 int ft_overlap_add(const float* frames, const float* inv_wss, float* ypad, int N, int n_fft, int hop, void* stream);
+/* The same for a RAGGED BATCH, one launch per call for all items (vocoder.GriffinLim.griffinlim_batch).  Item b has N_b =
+ * mel_len[b] frames (int64 [B] on the device, read there) and owns rows [b*Tcap, (b+1)*Tcap) of every frame-major buffer
+ * and samples [b*Tcap*hop, (b+1)*Tcap*hop) of the packed signal [B*Tcap*hop + n_fft]; Tcap*hop >= n_fft + hop*(Tmax-1), so
+ * its padded signal fits, and all frames of all items are the rows of ONE GEMM with ldx = hop (rows n >= N_b of that
+ * GEMM read the item's tail and its neighbour's head: garbage that gl_phase_ragged discards).  What an item gets depends
+ * on its own data, N_b and (seed, n, m) alone -- not on B, Tcap, Tmax or its position -- and every mask is a select, so a
+ * NaN elsewhere never reaches it.  A length outside [1, Tmax] is clamped into it (nothing indexes out of bounds) and sets
+ * *err_flag = 1 (int32 on the device, zeroed by the caller; NULL = no report) in the two entries that take one.  All
+ * buffers 16-byte aligned; Fp % 4 == 0, n_fft % 8 == 0, hop % 4 == 0: the accesses are 16 bytes wide.
+ * gl_exp_transpose_ragged: mel [B,C,Tmax] -> out [B*Tcap, C] = exp(mel[b,c,n]) for n < N_b, 0 otherwise (mel is not read
+ *   at n >= N_b).  gl_relu: x = max(x, 0) in place (the clip of the least-squares start; the forced-tile GEMM entry
+ *   ft_linear_multi_fwd_as has no ReLU flag).
+ * gl_init_ragged: proj [B*Tcap, 2Fp] = S * exp(2 pi i u) for n < N_b, zero rows otherwise; u = the given u [B*Tcap, Fp],
+ *   or with u == NULL the counter-based draw u(seed, n, m) = (ft_hash32(seed, n*Fp + m) >> 8) * 2^-24 in [0, 1), where
+ *   ft_hash32 is the library's 32-bit mixer of (seed, index) (csrc/ft_common.h; three multiply-xorshift rounds, the
+ *   dropout generator): keyed on the frame n and bin m, NOT on b.  u_out (optional) [B*Tcap, Fp] receives the u used,
+ *   0 at n >= N_b.
+ * gl_phase_ragged: gl_phase on rows n < N_b; proj = 0 and tprev = 0 on the others, whatever `rebuilt` holds there.
+ * overlap_add_ragged: ypad_b[t] = (sum over the item's own frames n < N_b, ascending, of frames[b*Tcap + n][t - n*hop]) /
+ *   wss_{N_b}[t] for t in [n_fft/2, n_fft/2 + hop*(N_b-1)), 0 in the rest of the item's stride and in the n_fft tail
+ *   behind the last item.  wss is accumulated beside the frames from w2 [n_fft] = the squared window in fp32 (same
+ *   frames, same order; the quotient is acc * (1.0f / wss), and acc itself where wss <= FLT_MIN), so it holds for every
+ *   N_b, including N_b < n_fft/hop where head and tail overlap.  Exactly one of ypad / wav is non-NULL: with wav
+ *   [B, hop*(Tmax-1)] the same sums are written as the signal itself, wav[b][j] = ypad_b[n_fft/2 + j] for j <
+ *   hop*(N_b-1), 0 beyond. */
+int ft_gl_exp_transpose_ragged(const float* mel, const long* mel_len, float* out, int B, int C, int Tmax, int Tcap,
+                               int* err_flag, void* stream);
+int ft_gl_relu(float* x, long n, void* stream);
+int ft_gl_init_ragged(const float* u, uint64_t seed, const float* S, const long* mel_len, float* proj, float* u_out,
+                      int B, int Tcap, int Tmax, int Fp, int* err_flag, void* stream);
+int ft_gl_phase_ragged(const float* rebuilt, float* tprev, const float* S, const long* mel_len, float* proj, int B,
+                       int Tcap, int Tmax, int Fp, float alpha, int has_prev, void* stream);
+int ft_overlap_add_ragged(const float* frames, const float* w2, const long* mel_len, float* ypad, float* wav, int B,
+                          int Tcap, int Tmax, int n_fft, int hop, void* stream);
 
 /* ---- audio front end: trim, peak-normalise, wav -> mel (utils/dsp.py:62-78,96-104 DSP.wav_to_mel / normalize /
  *      trim_silence ; preprocess.py:78-89, the audio half of Preprocessor._convert_file) ------------------------- */
