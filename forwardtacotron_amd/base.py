@@ -194,6 +194,35 @@ class AcousticModel(nn.Module):
 
         return pred, late_inputs
 
+    # -- generate_batch plumbing ------------------------------------------------------------------------------------
+    def _check_ragged_batch(self, x: torch.Tensor, x_len: torch.Tensor) -> bool:
+        """argument checks of generate_batch; an x_len on the host is range-checked here -> whether it was"""
+        if x.dim() != 2 or x_len.dim() != 1 or x_len.numel() != x.shape[0] or x_len.dtype != torch.int64:
+            raise H._lib.FtError(f'generate_batch: x must be [B,Tx] and x_len int64 [B] (got {tuple(x.shape)}, '
+                                 f'{tuple(x_len.shape)} {x_len.dtype})')
+        B, Tx = x.shape
+        on_host = not x_len.is_cuda
+        if on_host and (B == 0 or int(x_len.min()) < 1 or int(x_len.max()) > Tx):
+            raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}] (got {x_len.tolist()})')
+        self._require_device(x)
+        return on_host
+
+    def _masked_user_series(self, key: str, fn: Callable[[torch.Tensor], torch.Tensor], v: torch.Tensor,
+                            lens: torch.Tensor) -> torch.Tensor:
+        """pitch_function / energy_function of generate_batch on v [B,1,Tx]: shape-checked, masked again -> [B,1,Tx]"""
+        B, _, Tx = v.shape
+        v = fn(v)
+        if tuple(v.shape) != (B, 1, Tx) or v.dtype != torch.float32 or not v.is_cuda:
+            raise H._lib.FtError(f'generate_batch: {key}_function must return a float32 device tensor of shape '
+                                 f'[B,1,Tx] (got {tuple(v.shape)} {v.dtype})')
+        return H.mask_rows(v.reshape(B, Tx, 1).contiguous(), lens).reshape(B, 1, Tx)
+
+    def _bad_flag_host(self) -> torch.Tensor:
+        """pinned host word the device-side generate_batch flag is copied into (asynchronously; read after the trunk's sync)"""
+        if getattr(self, '_bad_host', None) is None:
+            self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        return self._bad_host
+
     # -------------------------------------------------------------------------------------------------------------
     def get_step(self) -> int:
         return self.step.data.item()

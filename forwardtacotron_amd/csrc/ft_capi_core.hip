@@ -673,6 +673,18 @@ int ft_conv1d_bias_fwd(const float* x, long ldx, const float* wp, const float* b
   return ft_launch_gemm_rows(&b, 1, false, (hipStream_t)stream);
 }
 
+// the same on a ragged batch: the epilogue stores zeros at t >= lens[b] (FtGemmBatch.out_lens); x must be zero there
+int ft_conv1d_bias_fwd_lens(const float* x, long ldx, const float* wp, const float* bias, float* y, long ldy,
+                            const long* lens, int B, int T, int Cin, int Cout, int k, int relu, void* stream) {
+  FT_REQUIRE(k >= 1 && (k % 2) == 1 && lens != nullptr, "conv1d_bias_fwd_lens: odd kernel sizes only / null lens");
+  FtGemmBatch b;
+  memset(&b, 0, sizeof(b));
+  conv_fwd_task(b.t[0], x, ldx, wp, y, ldy, B, T, Cin, Cout, k, T, relu);
+  b.t[0].bias = bias;
+  b.out_lens = lens;
+  return ft_launch_gemm_rows(&b, 1, false, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // strided-batch GEMMs: instance z -> (z0, z1) = (z / nb1, z % nb1), X_z = X + z0*sX0 + z1*sX1
 static void set_batch(FtGemmTask& t, int nb0, int nb1, long sA0, long sA1, long sB0, long sB1, long sC0, long sC1) {

@@ -135,6 +135,16 @@ __global__ void ft_embedding_fwd_lens_kernel(const long* __restrict__ idx, const
   out[i] = w[v * C + c];
 }
 
+// flag |= 2 if a token id inside an item's length is the pad id 0 (FastPitch.generate_batch: valid tokens are non-zero);
+// ids at t >= lens[b] are not read
+__global__ void ft_check_tokens_lens_kernel(const long* __restrict__ idx, const long* __restrict__ lens, int B, int T,
+                                            int* __restrict__ flag) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * T) return;
+  int b = (int)(i / T), t = (int)(i - (long)b * T);
+  if (t < lens[b] && idx[i] == 0) atomicOr(flag, 2);
+}
+
 // onehot[row][v] = (idx[row] == v): the embedding weight gradient is then onehot^T * dout, one TN MFMA GEMM
 // (ordered split reduction -> reproducible), shared by every embedding table fed by the same ids
 __global__ void ft_onehot_kernel(const long* __restrict__ idx, float* __restrict__ out, long rows, int V) {
@@ -628,6 +638,15 @@ int ft_embedding_fwd_lens(const long* idx, const long* lens, const float* w, flo
   hipLaunchKernelGGL(ft_embedding_fwd_lens_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, idx,
                      lens, w, out, B, T, C, V, err_flag);
   return ft_check_launch("embedding_fwd_lens");
+}
+
+int ft_check_tokens_lens(const long* idx, const long* lens, int B, int T, int* flag, void* stream) {
+  FT_REQUIRE(B >= 0 && T >= 0 && lens != nullptr && flag != nullptr, "check_tokens_lens: bad dims / null pointer");
+  const long total = (long)B * T;
+  if (total == 0) return FT_OK;
+  hipLaunchKernelGGL(ft_check_tokens_lens_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, idx, lens,
+                     B, T, flag);
+  return ft_check_launch("check_tokens_lens");
 }
 
 int ft_onehot(const long* idx, float* out, long rows, int V, void* stream) {

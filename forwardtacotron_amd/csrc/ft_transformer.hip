@@ -127,6 +127,44 @@ __global__ __launch_bounds__(256) void ft_layernorm_fwd_kernel(const float* __re
   }
 }
 
+// Inference form for a ragged batch: y = LayerNorm(x + res) at t < lens[b], exactly 0 at t >= lens[b] (where x and res
+// are not read) -- what feeds the k > 1 convolutions of an FFTBlock must be zero past the item's length.  No dropout, no
+// saved sum / statistics.  The valid rows go through ft_layernorm_fwd_kernel's arithmetic, operation for operation.
+__global__ __launch_bounds__(256) void ft_add_layernorm_fwd_lens_kernel(const float* __restrict__ x, const float* __restrict__ res,
+                                                                        const float* __restrict__ gamma,
+                                                                        const float* __restrict__ beta,
+                                                                        const long* __restrict__ lens, float* __restrict__ y,
+                                                                        long rows, int T, int D, float eps) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  const long b = row / T;
+  if (row - b * T >= lens[b]) {
+    for (int c = lane; c < D; c += 64) y[row * D + c] = 0.f;
+    return;
+  }
+  const float* xr = x + row * D;
+  const float* rr = res ? res + row * D : nullptr;
+  auto elem = [&](int c) {
+    float v = xr[c];
+    if (rr) v += rr[c];
+    return v;
+  };
+  float s1 = 0.f;
+  for (int c = lane; c < D; c += 64) s1 += elem(c);
+  const float mu = wave_sum_all(s1) / (float)D;
+  float s2 = 0.f;
+  for (int c = lane; c < D; c += 64) {
+    float v = elem(c) - mu;
+    s2 += v * v;
+  }
+  const float rs = 1.0f / sqrtf(wave_sum_all(s2) / (float)D + eps);
+  for (int c = lane; c < D; c += 64) {
+    float v = elem(c);
+    y[row * D + c] = (v - mu) * rs * gamma[c] + beta[c];
+  }
+}
+
 // dx = rstd * (g - mean(g) - xhat*mean(g*xhat)), g = dy*gamma ; also t_xhat = dy*xhat (for dgamma via column sums);
 // dres (optional) = the gradient of the dropped-out residual branch = mask * dx / (1-p)
 __global__ __launch_bounds__(256) void ft_layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ s,
@@ -233,6 +271,16 @@ int ft_layernorm_fwd(const float* x, const float* res, const float* gamma, const
   hipLaunchKernelGGL(ft_layernorm_fwd_kernel, dim3(ft_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, res, gamma,
                      beta, sum_out, y, mean, rstd, rows, D, eps, res_dropout_p, res_dropout_seed);
   return ft_check_launch("layernorm_fwd");
+}
+
+int ft_add_layernorm_fwd_lens(const float* x, const float* res, const float* gamma, const float* beta, const long* lens,
+                              float* y, int B, int T, int D, float eps, void* stream) {
+  FT_REQUIRE(B >= 0 && T >= 0 && lens != nullptr, "add_layernorm_fwd_lens: bad dims / null lens");
+  const long rows = (long)B * T;
+  if (rows <= 0 || D <= 0) return FT_OK;
+  hipLaunchKernelGGL(ft_add_layernorm_fwd_lens_kernel, dim3(ft_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, res,
+                     gamma, beta, lens, y, rows, T, D, eps);
+  return ft_check_launch("add_layernorm_fwd_lens");
 }
 
 int ft_layernorm_bwd(const float* dy, const float* s, const float* gamma, const float* mean, const float* rstd,

@@ -54,6 +54,29 @@ def precision_scoped(fn):
     return wrapped
 
 
+def _attn_unfused(qkv, key_pad, nh, scale, p_drop, seed):
+    """softmax(scale Q K^T + key mask) V through three launches with the [B,nh,T,T] matrices in memory
+    -> (att [B,T,d], P, dropout(P))"""
+    B, T, d3 = qkv.shape
+    d = d3 // 3
+    hd = d // nh
+    # the [T,T] score / probability matrices are kept with their row stride rounded up to 4 floats (pad columns
+    # are zeros): T = 841 frames would otherwise push four of the six attention GEMMs off the 16-B-load paths
+    Tp = (T + 3) // 4 * 4
+    P = torch.empty(B, nh, T, Tp, device=qkv.device, dtype=qkv.dtype)
+    q0 = qkv.data_ptr()
+    _bgemm('nt', q0, 3 * d, T * 3 * d, hd, q0 + d * _F4, 3 * d, T * 3 * d, hd, P.data_ptr(), Tp, nh * T * Tp, T * Tp,
+           T, T, hd, B, nh, qkv.device)
+    # softmax and nn.MultiheadAttention's attention dropout in one pass; both P and dropout(P) are kept for backward
+    Pd = torch.empty_like(P) if p_drop > 0 else P
+    _lib.call('ft_softmax_fwd', P.data_ptr(), _p(key_pad), B, nh, T, T, Tp, scale,
+              Pd.data_ptr() if p_drop > 0 else None, float(p_drop), int(seed), H._stream())
+    att = torch.empty(B, T, d, device=qkv.device, dtype=qkv.dtype)
+    _bgemm('nn', Pd.data_ptr(), Tp, nh * T * Tp, T * Tp, q0 + 2 * d * _F4, 3 * d, T * 3 * d, hd, att.data_ptr(), d,
+           T * d, hd, T, hd, T, B, nh, qkv.device, padded=True)
+    return att, P, Pd
+
+
 def mha_fwd(x, key_pad, in_w, in_b, out_w, out_b, nheads, p_drop, seed):
     """nn.MultiheadAttention(d, nheads, dropout)(x, x, x, key_padding_mask=key_pad)[0]  (common_layers.py:172-174) on
     batch-major x [B,T,d]; key_pad uint8 [B,T] (1 = padded key) or None.  -> (out, tape for mha_bwd)"""
@@ -69,22 +92,37 @@ def mha_fwd(x, key_pad, in_w, in_b, out_w, out_b, nheads, p_drop, seed):
         att, lse2 = H.attn_fwd(qkv, key_pad, nh, scale, p_drop, seed)
         tape.update(fused=True, att=att, lse2=lse2)
         return H.linear_fwd(att, out_w, out_b), tape
-    # the [T,T] score / probability matrices are kept with their row stride rounded up to 4 floats (pad columns
-    # are zeros): T = 841 frames would otherwise push four of the six attention GEMMs off the 16-B-load paths
-    Tp = (T + 3) // 4 * 4
-    P = torch.empty(B, nh, T, Tp, device=x.device, dtype=x.dtype)
-    q0 = qkv.data_ptr()
-    _bgemm('nt', q0, 3 * d, T * 3 * d, hd, q0 + d * _F4, 3 * d, T * 3 * d, hd, P.data_ptr(), Tp, nh * T * Tp, T * Tp,
-           T, T, hd, B, nh, x.device)
-    # softmax and nn.MultiheadAttention's attention dropout in one pass; both P and dropout(P) are kept for backward
-    Pd = torch.empty_like(P) if p_drop > 0 else P
-    _lib.call('ft_softmax_fwd', P.data_ptr(), _p(key_pad), B, nh, T, T, Tp, scale,
-              Pd.data_ptr() if p_drop > 0 else None, float(p_drop), int(seed), H._stream())
-    att = torch.empty(B, T, d, device=x.device, dtype=x.dtype)
-    _bgemm('nn', Pd.data_ptr(), Tp, nh * T * Tp, T * Tp, q0 + 2 * d * _F4, 3 * d, T * 3 * d, hd, att.data_ptr(), d,
-           T * d, hd, T, hd, T, B, nh, x.device, padded=True)
+    att, P, Pd = _attn_unfused(qkv, key_pad, nh, scale, p_drop, seed)
     tape.update(fused=False, att=att, P=P, Pd=Pd)
     return H.linear_fwd(att, out_w, out_b), tape
+
+
+def attn_lens_fused(hd: int) -> bool:
+    """the length-aware fused kernel serves head widths 64 and 128; FT_ATTN_LENS=0 forces the masked routes (A/B aid)"""
+    return hd in (64, 128) and os.environ.get('FT_ATTN_LENS', '1') == '1'
+
+
+def mha_fwd_lens(x, lens, in_w, in_b, out_w, out_b, nheads):
+    """Inference self-attention of a ragged batch (torch.no_grad only, no tape): x [B,T,d], lens int64 [B] on the device.
+    Rows t < lens[b] attend to keys < lens[b] only; the attention output is exactly 0 at t >= lens[b] (the result holds
+    the out-projection's bias there).  Head widths 64 / 128: ft_attn_fwd_lens, which reads the lengths on the device and
+    skips what lies past them; every other width: mha_fwd's route for the current precision with a byte mask derived
+    from lens, followed by mask_rows."""
+    B, T, d = x.shape
+    nh = int(nheads)
+    hd = d // nh
+    scale = 1.0 / math.sqrt(hd)
+    qkv = H.linear_fwd(x, in_w, in_b)                                   # [B,T,3d]
+    if attn_lens_fused(hd):
+        att = H.attn_fwd_lens(qkv, lens, nh, scale)
+    else:
+        key_pad = (torch.arange(T, device=x.device).unsqueeze(0) >= lens.unsqueeze(1)).to(torch.uint8).contiguous()
+        if H.gemm_precision_mode() == 'bf16' and hd in (64, 128) and os.environ.get('FT_ATTN_FUSED', '1') == '1':
+            att = H.attn_fwd(qkv, key_pad, nh, scale, 0.0, 0)[0]
+        else:
+            att = _attn_unfused(qkv, key_pad, nh, scale, 0.0, 0)[0]
+        att = H.mask_rows(att, lens)
+    return H.linear_fwd(att, out_w, out_b)
 
 
 def mha_bwd(tape, dout, in_w, in_b, out_w, out_b, need_dx=True, dx_into=None):
@@ -583,6 +621,18 @@ class FFTBlock(nn.Module):
         return AddLayerNormFn.apply(src, src2, self.norm2.weight, self.norm2.bias, self.norm2.eps, p,
                                     _seed() if p > 0 else 0)
 
+    def forward_lens(self, src: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """eval forward of a ragged batch (torch.no_grad): no valid row reads a row at t >= lens[b].  The attention
+        guarantees that itself; the k > 1 convolutions need their input zero there, so both LayerNorms store zeros past
+        the item's length (a LayerNorm would turn a zero row into its beta) and both convolutions mask their output.
+        -> [B,T,d], exactly 0 at t >= lens[b]"""
+        a = self.self_attn
+        src2 = mha_fwd_lens(src, lens, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, self.nhead)
+        src = H.add_layernorm_fwd_lens(src, src2, self.norm1.weight, self.norm1.bias, lens, self.norm1.eps)
+        h = H.conv1d_bias_fwd_lens(src, H.conv_pack_weight(self.conv1.weight), self.conv1.bias, True, lens)
+        h = H.conv1d_bias_fwd_lens(h, H.conv_pack_weight(self.conv2.weight), self.conv2.bias, False, lens)
+        return H.add_layernorm_fwd_lens(src, h, self.norm2.weight, self.norm2.bias, lens, self.norm2.eps)
+
 
 class ForwardTransformer(nn.Module):
     """common_layers.py:188-223; x [B,T,d] -> [B,T,d].  Like the reference, every layer is a deepcopy of ONE
@@ -625,6 +675,20 @@ class ForwardTransformer(nn.Module):
         return TransformerFn.apply(x, key_pad, self.pos_encoder.pe, self.pos_encoder.scale, self.norm.weight,
                                    self.norm.bias, cfg, *flat)
 
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """eval forward of a ragged batch, operation by operation in both precisions (the C-issued composite is the
+        training path): x [B,T,d], lens int64 [B] on the device -> [B,T,d], exactly 0 at t >= lens[b].  Rows of x at
+        t >= lens[b] are never read into a valid row (with the fused attention kernel they may even hold NaN)."""
+        x = _c(x)
+        B, T, D = x.shape
+        check_posenc_length(T, self.pos_encoder.pe)
+        h = torch.empty_like(x)
+        _lib.call('ft_posenc_fwd', x.data_ptr(), self.pos_encoder.pe.data_ptr(), self.pos_encoder.scale.data_ptr(),
+                  h.data_ptr(), B, T, D, H._stream())
+        for layer in self.layers:
+            h = layer.forward_lens(h, lens)
+        return H.add_layernorm_fwd_lens(h, None, self.norm.weight, self.norm.bias, lens, self.norm.eps)
+
 
 class SeriesPredictor(nn.Module):
     """fast_pitch.py:14-41"""
@@ -639,6 +703,11 @@ class SeriesPredictor(nn.Module):
 
     def forward(self, x: torch.Tensor, src_pad_mask: Optional[torch.Tensor] = None, alpha: float = 1.0):
         return transformer_predict(self, predictor_front(x, self.embedding), src_pad_mask, alpha)
+
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
+        """eval forward of a ragged batch: tokens at t >= lens[b] are ignored, the result [B,T,1] is zero there"""
+        y = self.transformer.forward_lens(H.embedding_fwd_lens(x, lens, self.embedding.weight), lens)
+        return H.mask_rows(predictor_tail(y, self.lin, alpha), lens)            # (the Linear's bias)
 
 
 def transformer_predict(pred: nn.Module, x: torch.Tensor, src_pad_mask: Optional[torch.Tensor], alpha: float):
@@ -743,3 +812,68 @@ class FastPitch(AcousticModel):
                                energy_hat.reshape(B, -1).contiguous(), None)
             m = H.transpose_pad_fwd(mel_cl, mel_cl.shape[1], 0.0)
             return {'mel': m, 'mel_post': m, 'dur': dur_in, 'pitch': pitch_hat, 'energy': energy_hat}
+
+    @precision_scoped
+    def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, alpha=1.0,
+                       pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
+                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
+        """generate() of a RAGGED batch of sentences -- the contract of ForwardTacotron.generate_batch (same arguments,
+        result keys and errors): for every item b the valid parts of the result equal
+        generate(x[b:b+1, :x_len[b]], alpha, ...) on the same model (to the rounding of the matmul mode; `mel_len`
+        exactly in fp32 mode).
+
+        x: int64 [B,Tx] on the device; entries at t >= x_len[b] are ignored, whatever they hold.  x_len: int64 [B], on the
+        host or the device, 1 <= x_len[b] <= Tx (anything else raises FtError).  pitch_function / energy_function get
+        [B,1,Tx] (zero at t >= x_len[b]) and must act PER TOKEN; their results are masked again.
+
+        Valid tokens are NON-ZERO.  generate() masks the prenet's keys where x == 0 (fast_pitch.py:199), which inside a
+        sentence only happens if the pad symbol itself is used as a token; here the lengths say what is padding, and a 0
+        at t < x_len[b] raises FtError instead of being silently treated either way.
+
+        -> mel, mel_post (one tensor, as in generate) [B,n_mels,Tm] with Tm = max(mel_len) and padding_value at
+        t >= mel_len[b]; mel_len int64 [B]; dur [B,Tx], pitch / energy [B,1,Tx], all three 0 at t >= x_len[b].  Per item: if
+        the truncated durations of the valid tokens sum to <= 0 they all become 2.0 (fast_pitch.py:176-177); repeats are
+        (clamp(dur, 0) + 0.5).long().  One host synchronisation (sizing Tm), as in generate().
+
+        The zero-token check and the range check of an x_len that lives on the device run on the device: the FtError is
+        raised behind that one synchronisation, and the flag travels through ONE pinned host word kept on the module -- so
+        a model must not run generate_batch from two threads or on two streams at once."""
+        self.eval()
+        with torch.no_grad():
+            on_host = self._check_ragged_batch(x, x_len)
+            B, Tx = x.shape
+            x = x.contiguous()
+            xl = x_len.to(x.device).contiguous()
+
+            def predict():
+                # the three predictors, in generate()'s order; everything they hand on is zero at t >= x_len[b]
+                dur = self.dur_pred.forward_lens(x, xl, alpha=alpha).reshape(B, Tx)
+                mel_len, bad = H.gen_durations(dur, xl)           # per-item fallback, clamp; dur in its returned form
+                H.check_tokens_lens(x, xl, bad)
+                out = {'dur': dur, 'mel_len': mel_len, 'bad': bad}
+                for key, pred, fn in (('pitch', self.pitch_pred, pitch_function),
+                                      ('energy', self.energy_pred, energy_function)):
+                    out[key] = self._masked_user_series(key, fn, pred.forward_lens(x, xl).transpose(1, 2), xl)
+                return out
+
+            # the predictors only meet the trunk behind the prenet: side stream
+            fork = self._fork_predictors(x.device, predict, overlap=os.environ.get('FT_GEN_OVERLAP', '1') == '1')
+            h = self.prenet.forward_lens(H.embedding_fwd_lens(x, xl, self.embedding.weight), xl)
+            pred = self._join_predictors(fork)
+            bad_host = self._bad_flag_host()
+            bad_host.copy_(pred['bad'], non_blocking=True)
+            mel_len = pred['mel_len']
+            h = ops.CondAddFn.apply(h, pred['pitch'].reshape(B, Tx), pred['energy'].reshape(B, Tx), self.pitch_proj.weight,
+                                    self.pitch_proj.bias, self.energy_proj.weight, self.energy_proj.bias,
+                                    self.pitch_strength, self.energy_strength, False)
+            h = self.lr(h, pred['dur'])                           # zero rows at t >= mel_len[b]; syncs to size Tm
+            flags = int(bad_host[0])
+            if flags & 1 and not on_host:
+                raise _lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}]')
+            if flags & 2:
+                raise _lib.FtError('generate_batch: token id 0 inside a sentence (t < x_len[b]); valid tokens are non-zero')
+            h = self.postnet.forward_lens(h, mel_len)
+            mel = ops.LinearFn.apply(h, self.lin.weight, self.lin.bias)       # [B,Tm,n_mels]
+            m = H.transpose_pad_lens_fwd(mel, mel_len, mel.shape[1], float(self.padding_value))
+            return {'mel': m, 'mel_post': m, 'mel_len': mel_len, 'dur': pred['dur'], 'pitch': pred['pitch'],
+                    'energy': pred['energy']}

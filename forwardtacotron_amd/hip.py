@@ -127,6 +127,21 @@ def attn_fwd(qkv: torch.Tensor, key_pad: Optional[torch.Tensor], nheads: int, sc
     return att, lse2
 
 
+def attn_fwd_lens(qkv: torch.Tensor, lens: torch.Tensor, nheads: int, scale: float) -> torch.Tensor:
+    """Inference attention of a ragged batch: qkv [B,T,3d], lens int64 [B] (device) -> att [B,T,d] with rows t < lens[b]
+    attending to keys < lens[b] and rows t >= lens[b] exactly 0 (qkv is not read there).  The precision is
+    gemm_precision_mode()'s: bf16 = ft_attn_fwd's arithmetic, fp32 = fp32-exact products.  Head width 64 or 128 only
+    (include/fwdtaco_hip.h: ft_attn_fwd_lens)."""
+    _chk(qkv, 'qkv'); _chk(lens, 'lens', torch.int64)
+    B, T, d3 = qkv.shape
+    d = d3 // 3
+    assert lens.numel() == B
+    att = torch.empty(B, T, d, device=qkv.device, dtype=qkv.dtype)
+    _lib.call('ft_attn_fwd_lens', _p(qkv), _p(lens), _p(att), B, T, nheads, d // nheads, float(scale),
+              int(gemm_precision_mode() == 'bf16'), _stream())
+    return att
+
+
 def attn_bwd(qkv, att, datt, key_pad, lse2, nheads: int, scale: float, p_drop: float, seed: int) -> torch.Tensor:
     _chk(datt, 'datt')
     B, T, d3 = qkv.shape
@@ -412,6 +427,34 @@ def conv1d_fwd_lens(x: torch.Tensor, wp: torch.Tensor, relu: bool, lens: torch.T
     y = accumulate_into if accumulate_into is not None else torch.empty(B, T, Cout, device=x.device, dtype=x.dtype)
     _lib.call('ft_conv1d_fwd_lens', _p(x), Cin, _p(wp), _p(scale), _p(shift), _p(y), Cout, _p(lens), B, T, Cin, Cout, k,
               int(relu), int(accumulate_into is not None), _stream())
+    return y
+
+
+def conv1d_bias_fwd_lens(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, relu: bool, lens: torch.Tensor) -> torch.Tensor:
+    """nn.Conv1d with bias (+ ReLU) on a ragged batch: x [B,T,Cin] (zero at t >= lens[b]), wp [k,Cout,Cin], k odd ->
+    y [B,T,Cout], exactly 0 at t >= lens[b]"""
+    _chk(x, 'x'); _chk(wp, 'wp'); _chk(bias, 'bias'); _chk(lens, 'lens', torch.int64)
+    B, T, Cin = x.shape
+    k, Cout, _ = wp.shape
+    assert lens.numel() == B
+    y = torch.empty(B, T, Cout, device=x.device, dtype=x.dtype)
+    _lib.call('ft_conv1d_bias_fwd_lens', _p(x), Cin, _p(wp), _p(bias), _p(y), Cout, _p(lens), B, T, Cin, Cout, k,
+              int(relu), _stream())
+    return y
+
+
+def add_layernorm_fwd_lens(x: torch.Tensor, res: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
+                           lens: torch.Tensor, eps: float) -> torch.Tensor:
+    """LayerNorm(x + res) (res may be None) of a ragged batch [B,T,D]: exactly 0 at t >= lens[b], where neither input
+    is read.  Inference only: nothing is saved for a backward."""
+    _chk(x, 'x'); _chk(lens, 'lens', torch.int64)
+    if res is not None:
+        _chk(res, 'res')
+    B, T, D = x.shape
+    assert lens.numel() == B
+    y = torch.empty_like(x)
+    _lib.call('ft_add_layernorm_fwd_lens', _p(x), _p(res), _p(gamma), _p(beta), _p(lens), _p(y), B, T, D, float(eps),
+              _stream())
     return y
 
 
@@ -765,6 +808,14 @@ def embedding_fwd_lens(idx: torch.Tensor, lens: torch.Tensor, w: torch.Tensor) -
     out = torch.empty(B, T, C, device=w.device, dtype=w.dtype)
     _lib.call('ft_embedding_fwd_lens', _p(idx), _p(lens), _p(w), _p(out), B, T, C, V, _p(_err_flag(w.device)), _stream())
     return out
+
+
+def check_tokens_lens(idx: torch.Tensor, lens: torch.Tensor, flag: torch.Tensor) -> None:
+    """flag[0] |= 2 (int32, device) if idx [B,T] holds the pad id 0 at some t < lens[b]"""
+    _chk(idx, 'idx', torch.int64); _chk(lens, 'lens', torch.int64); _chk(flag, 'flag', torch.int32)
+    B, T = idx.shape
+    assert lens.numel() == B
+    _lib.call('ft_check_tokens_lens', _p(idx), _p(lens), B, T, _p(flag), _stream())
 
 
 _err_flags = {}

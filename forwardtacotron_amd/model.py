@@ -429,14 +429,8 @@ class ForwardTacotron(AcousticModel):
         return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0), **pred}
 
     def _generate_batch(self, x, x_len, alpha, pitch_function, energy_function):
-        if x.dim() != 2 or x_len.dim() != 1 or x_len.numel() != x.shape[0] or x_len.dtype != torch.int64:
-            raise H._lib.FtError(f'generate_batch: x must be [B,Tx] and x_len int64 [B] (got {tuple(x.shape)}, '
-                                 f'{tuple(x_len.shape)} {x_len.dtype})')
+        on_host = self._check_ragged_batch(x, x_len)
         B, Tx = x.shape
-        on_host = not x_len.is_cuda
-        if on_host and (B == 0 or int(x_len.min()) < 1 or int(x_len.max()) > Tx):
-            raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}] (got {x_len.tolist()})')
-        self._require_device(x)
         x = x.contiguous()
         xl = x_len.to(x.device).contiguous()
 
@@ -446,11 +440,7 @@ class ForwardTacotron(AcousticModel):
             mel_len, bad = H.gen_durations(dur, xl)               # per-item fallback, clamp; dur in its returned form
             out = {'dur': dur, 'mel_len': mel_len, 'bad': bad}
             for key, pred, fn in (('pitch', self.pitch_pred, pitch_function), ('energy', self.energy_pred, energy_function)):
-                v = fn(pred.forward_lens(x, xl).transpose(1, 2))                 # [B,1,Tx]
-                if tuple(v.shape) != (B, 1, Tx) or v.dtype != torch.float32 or not v.is_cuda:
-                    raise H._lib.FtError(f'generate_batch: {key}_function must return a float32 device tensor of shape '
-                                         f'[B,1,Tx] (got {tuple(v.shape)} {v.dtype})')
-                out[key] = H.mask_rows(v.reshape(B, Tx, 1).contiguous(), xl).reshape(B, 1, Tx)
+                out[key] = self._masked_user_series(key, fn, pred.forward_lens(x, xl).transpose(1, 2), xl)   # [B,1,Tx]
             return out
 
         # the predictors only meet the trunk behind the prenet: side stream, as in _generate_fork
@@ -479,12 +469,6 @@ class ForwardTacotron(AcousticModel):
         return {'mel': H.transpose_pad_lens_fwd(mel, mel_len, Tm, pad),
                 'mel_post': H.transpose_pad_lens_fwd(post.contiguous(), mel_len, Tm, pad), 'mel_len': mel_len,
                 'dur': pred['dur'], 'pitch': pred['pitch'], 'energy': pred['energy']}
-
-    def _bad_flag_host(self) -> torch.Tensor:
-        """pinned host word the device-side x_len range flag is copied into (asynchronously; read after the trunk's sync)"""
-        if getattr(self, '_bad_host', None) is None:
-            self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        return self._bad_host
 
     def _generate_mel(self, x: torch.Tensor, dur_hat: torch.Tensor, pitch_hat: torch.Tensor,
                       energy_hat: torch.Tensor) -> Dict[str, torch.Tensor]:

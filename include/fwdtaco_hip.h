@@ -547,6 +547,25 @@ int ft_attn_bwd(const float* qkv, const float* att, const float* datt, const uns
                 float* dqkv, int B, int T, int nheads, int hd, float scale, float p_drop, uint64_t seed, void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* ---- length-aware fused self-attention, inference, both matmul modes (FastPitch.generate_batch) ------------------- */
+/* qkv [B,T,3d] as ft_attn_fwd; lens int64 [B] on the device.  For item b, L = min(max(lens[b], 0), T): rows t < L of att
+ * [B,T,d] hold softmax(scale q_h k_h^T over the keys < L) v_h, rows t >= L hold exactly 0.  No dropout, no log-sum-exp, no
+ * byte mask.  qkv rows at t >= L are never read into arithmetic (they may hold NaN); workgroups whose queries all lie past
+ * L store zeros and leave, every other key loop ends at ceil(L / 64) blocks.  bf16 = 1: ft_attn_fwd's arithmetic (valid
+ * rows bit-equal to it with the byte mask t >= L at p_drop = 0); bf16 = 0: fp32-exact products (v_mfma_f32_32x32x2_f32).
+ * hd = 64 or 128; qkv and att 16-byte aligned. */
+int ft_attn_fwd_lens(const float* qkv, const int64_t* lens, float* att, int B, int T, int nheads, int hd, float scale,
+                     int bf16, void* stream);
+/* y [B,T,D] = LayerNorm(x + res) (res may be NULL) at t < lens[b], exactly 0 at t >= lens[b], where x / res are not read:
+ * the inference add + LayerNorm in front of an FFTBlock's k > 1 convolutions on a ragged batch */
+int ft_add_layernorm_fwd_lens(const float* x, const float* res, const float* gamma, const float* beta, const long* lens,
+                              float* y, int B, int T, int D, float eps, void* stream);
+/* ft_conv1d_bias_fwd whose epilogue stores zeros at t >= lens[b]; x must be zero there */
+int ft_conv1d_bias_fwd_lens(const float* x, long ldx, const float* wp, const float* bias, float* y, long ldy,
+                            const long* lens, int B, int T, int Cin, int Cout, int k, int relu, void* stream);
+/* flag[0] |= 2 if idx [B,T] holds the pad id 0 at some t < lens[b] (ids at t >= lens[b] are not read) */
+int ft_check_tokens_lens(const long* idx, const long* lens, int B, int T, int* flag, void* stream);
+
 /* ---- a whole FFTBlock per call (common_layers.py:148-185), bf16 matmul mode with the fused attention ------------ */
 /* The FastPitch step is ~900 launches for ~13 ms of GPU work: issued one entry point at a time from Python it is bound by
  * the host (15 us per launch).  These two calls issue every launch of n consecutive FFTBlocks -- forward: in-projection,
