@@ -37,6 +37,11 @@ def _side_priority() -> int:
     return -1 if os.environ.get('FT_PRED_PRIORITY', '1') == '1' else 0
 
 
+def _gen_overlap() -> bool:
+    """inference runs the predictors on the side stream, beside the prenet; FT_GEN_OVERLAP=0: in front of it"""
+    return os.environ.get('FT_GEN_OVERLAP', '1') == '1'
+
+
 def _dropout(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
     if not training or p <= 0.0:
         return x
@@ -182,7 +187,7 @@ class AcousticModel(nn.Module):
         side stream while the main stream does embedding + prenet CBHG (its 128-step GRU is latency-bound: a single
         utterance spends 84 % of its time in recurrences), joined where their outputs are needed.  FT_GEN_OVERLAP=0: no
         overlap.  -> (outputs, late_inputs for _trunk); after the trunk outputs['dur'] is the tensor the trunk consumed"""
-        fork = self._fork_predictors(x.device, run, overlap=os.environ.get('FT_GEN_OVERLAP', '1') == '1')
+        fork = self._fork_predictors(x.device, run, overlap=_gen_overlap())
         pred, B = fork[2], x.shape[0]
 
         def late_inputs():
@@ -194,7 +199,88 @@ class AcousticModel(nn.Module):
 
         return pred, late_inputs
 
-    # -- generate_batch plumbing ------------------------------------------------------------------------------------
+    # -- generate_batch: the driver, its helpers and the hooks a model supplies --------------------------------------
+    checks_tokens: bool = False     # token id 0 at t < x_len[b] raises (the models whose generate() masks keys where x == 0)
+
+    def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, alpha=1.0,
+                       pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
+                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
+        """generate() of a RAGGED batch of sentences: for every item b the valid parts of the result equal
+        generate(x[b:b+1, :x_len[b]], alpha, ...) on the same model (to the rounding of the matmul mode; `mel_len` exactly
+        in fp32 mode).
+
+        x: int64 [B,Tx] on the device; entries at t >= x_len[b] are ignored, whatever they hold.  x_len: int64 [B], on the
+        host or the device, 1 <= x_len[b] <= Tx (anything else raises FtError).  pitch_function / energy_function get
+        [B,1,Tx] (zero at t >= x_len[b]) and must act PER TOKEN -- a function that mixes tokens or items (a mean over
+        the batch, a filter along t) breaks the per-item contract; their results are masked again.
+
+        A model with `checks_tokens` (FastPitch) wants valid tokens NON-ZERO.  Its generate() masks the prenet's keys where
+        x == 0 (fast_pitch.py:199), which inside a sentence only happens if the pad symbol itself is used as a token; here
+        the lengths say what is padding, and a 0 at t < x_len[b] raises FtError instead of being silently treated either way.
+
+        -> mel, mel_post [B,n_mels,Tm] with Tm = max(mel_len) and padding_value at t >= mel_len[b] (one tensor where the
+        model's generate() returns one); mel_len int64 [B]; dur [B,Tx], pitch / energy [B,1,Tx], all three 0 at
+        t >= x_len[b].  Per item: if the truncated durations of the valid tokens sum to <= 0 they all become 2.0
+        (forward_tacotron.py:176-177, fast_pitch.py:176-177); repeats are (clamp(dur, 0) + 0.5).long().  One host
+        synchronisation (sizing Tm), as in generate().
+
+        The zero-token check and the range check of an x_len that lives on the device run on the device: the FtError is
+        raised only after the trunk up to the regulator has been enqueued (behind that one synchronisation), and the flag
+        travels through ONE pinned host word kept on the module -- so a model must not run such a call from two threads or
+        on two streams at once (without `checks_tokens` a host-side x_len is checked up front and has no such limit).
+
+        A model plugs in through three hooks, run in this order:
+          _ragged_prenet(x, xl) -> h            token-side trunk up to where the predictors are needed
+          _ragged_regulate(h, pred) -> h        behind the join: CondAddFn (_cond_add), then the step that synchronises
+          _ragged_finish(h, mel_len) -> (mel, mel_post)   behind the flag check, up to H.transpose_pad_lens_fwd
+        and overrides _ragged_predict if its predictors take more than (x, lens)."""
+        if not hasattr(self, '_ragged_prenet'):
+            raise H._lib.FtError(f'{type(self).__name__} has no generate_batch: it supplies no _ragged_* hooks')
+        self.eval()
+        with torch.no_grad():
+            on_host = self._check_ragged_batch(x, x_len)
+            x = x.contiguous()
+            xl = x_len.to(x.device).contiguous()
+            # the predictors only meet the trunk behind the prenet: side stream, as in _generate_fork
+            fork = self._fork_predictors(x.device, lambda: self._ragged_predict(x, xl, alpha, pitch_function, energy_function),
+                                         overlap=_gen_overlap())
+            h = self._ragged_prenet(x, xl)
+            pred = self._join_predictors(fork)
+            # a host-side x_len was range-checked up front; what was not rides on the one synchronisation of the regulator
+            read_flag = (not on_host) or self.checks_tokens
+            if read_flag:
+                bad_host = self._bad_flag_host()
+                bad_host.copy_(pred['bad'], non_blocking=True)
+            h = self._ragged_regulate(h, pred)
+            flags = int(bad_host[0]) if read_flag else 0
+            if flags & 1 and not on_host:
+                raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {x.shape[1]}]')
+            if flags & 2:
+                raise H._lib.FtError('generate_batch: token id 0 inside a sentence (t < x_len[b]); valid tokens are non-zero')
+            mel, mel_post = self._ragged_finish(h, pred['mel_len'])
+            return {'mel': mel, 'mel_post': mel_post, 'mel_len': pred['mel_len'], 'dur': pred['dur'],
+                    'pitch': pred['pitch'], 'energy': pred['energy']}
+
+    def _ragged_predict(self, x: torch.Tensor, xl: torch.Tensor, alpha: float, pitch_function, energy_function):
+        """the three predictors, in generate()'s order; everything they hand on is zero at t >= x_len[b]
+        -> dur [B,Tx] (in its returned form), mel_len, bad (the flag word), pitch / energy [B,1,Tx]"""
+        B, Tx = x.shape
+        dur = self.dur_pred.forward_lens(x, xl, alpha=alpha).reshape(B, Tx)
+        mel_len, bad = H.gen_durations(dur, xl)                   # per-item fallback, clamp; raises bit 1 of bad
+        if self.checks_tokens:
+            H.check_tokens_lens(x, xl, bad)                       # raises bit 2
+        out = {'dur': dur, 'mel_len': mel_len, 'bad': bad}
+        for key, pred, fn in (('pitch', self.pitch_pred, pitch_function), ('energy', self.energy_pred, energy_function)):
+            out[key] = self._masked_user_series(key, fn, pred.forward_lens(x, xl).transpose(1, 2), xl)
+        return out
+
+    def _cond_add(self, h: torch.Tensor, pitch: torch.Tensor, energy: torch.Tensor, x_time_major: bool) -> torch.Tensor:
+        """h + the model's pitch / energy projections of pitch, energy ([B,Tx] or [B,1,Tx]) -> [B,Tx,C]"""
+        B = pitch.shape[0]
+        return ops.CondAddFn.apply(h, pitch.reshape(B, -1), energy.reshape(B, -1), self.pitch_proj.weight,
+                                   self.pitch_proj.bias, self.energy_proj.weight, self.energy_proj.bias,
+                                   self.pitch_strength, self.energy_strength, x_time_major)
+
     def _check_ragged_batch(self, x: torch.Tensor, x_len: torch.Tensor) -> bool:
         """argument checks of generate_batch; an x_len on the host is range-checked here -> whether it was"""
         if x.dim() != 2 or x_len.dim() != 1 or x_len.numel() != x.shape[0] or x_len.dtype != torch.int64:

@@ -77,6 +77,21 @@ def _attn_unfused(qkv, key_pad, nh, scale, p_drop, seed):
     return att, P, Pd
 
 
+def attn_route(hd: int, ragged: bool = False) -> str:
+    """Which attention serves head width hd under the current matmul mode (the switches are read per call):
+    'lens'    ragged batches only: ft_attn_fwd_lens reads the lengths on the device, head widths 64 / 128 in both modes;
+              FT_ATTN_LENS=0 forces the masked routes below (A/B aid)
+    'fused'   bf16 mode, head widths 64 / 128: ONE flash-style kernel between the two projections -- no [B,h,T,T] tensor
+              in memory, the backward recomputes the probabilities (csrc/ft_attn.hip); FT_ATTN_FUSED=0 turns it off
+    'unfused' everything else: _attn_unfused"""
+    if hd in (64, 128):
+        if ragged and os.environ.get('FT_ATTN_LENS', '1') == '1':
+            return 'lens'
+        if H.gemm_precision_mode() == 'bf16' and os.environ.get('FT_ATTN_FUSED', '1') == '1':
+            return 'fused'
+    return 'unfused'
+
+
 def mha_fwd(x, key_pad, in_w, in_b, out_w, out_b, nheads, p_drop, seed):
     """nn.MultiheadAttention(d, nheads, dropout)(x, x, x, key_padding_mask=key_pad)[0]  (common_layers.py:172-174) on
     batch-major x [B,T,d]; key_pad uint8 [B,T] (1 = padded key) or None.  -> (out, tape for mha_bwd)"""
@@ -86,20 +101,13 @@ def mha_fwd(x, key_pad, in_w, in_b, out_w, out_b, nheads, p_drop, seed):
     scale = 1.0 / math.sqrt(hd)
     qkv = H.linear_fwd(x, in_w, in_b)                                   # [B,T,3d]
     tape = dict(x=x, qkv=qkv, key_pad=key_pad, nh=nh, hd=hd, scale=scale, p=float(p_drop), seed=int(seed))
-    # bf16 mode: ONE flash-style kernel between the two projections -- no [B,h,T,T] tensor in memory, the backward
-    # recomputes the probabilities (csrc/ft_attn.hip); FT_ATTN_FUSED=0: the five-launch form below in bf16 too
-    if H.gemm_precision_mode() == 'bf16' and hd in (64, 128) and os.environ.get('FT_ATTN_FUSED', '1') == '1':
+    if attn_route(hd) == 'fused':
         att, lse2 = H.attn_fwd(qkv, key_pad, nh, scale, p_drop, seed)
         tape.update(fused=True, att=att, lse2=lse2)
         return H.linear_fwd(att, out_w, out_b), tape
     att, P, Pd = _attn_unfused(qkv, key_pad, nh, scale, p_drop, seed)
     tape.update(fused=False, att=att, P=P, Pd=Pd)
     return H.linear_fwd(att, out_w, out_b), tape
-
-
-def attn_lens_fused(hd: int) -> bool:
-    """the length-aware fused kernel serves head widths 64 and 128; FT_ATTN_LENS=0 forces the masked routes (A/B aid)"""
-    return hd in (64, 128) and os.environ.get('FT_ATTN_LENS', '1') == '1'
 
 
 def mha_fwd_lens(x, lens, in_w, in_b, out_w, out_b, nheads):
@@ -113,11 +121,12 @@ def mha_fwd_lens(x, lens, in_w, in_b, out_w, out_b, nheads):
     hd = d // nh
     scale = 1.0 / math.sqrt(hd)
     qkv = H.linear_fwd(x, in_w, in_b)                                   # [B,T,3d]
-    if attn_lens_fused(hd):
+    route = attn_route(hd, ragged=True)
+    if route == 'lens':
         att = H.attn_fwd_lens(qkv, lens, nh, scale)
     else:
         key_pad = (torch.arange(T, device=x.device).unsqueeze(0) >= lens.unsqueeze(1)).to(torch.uint8).contiguous()
-        if H.gemm_precision_mode() == 'bf16' and hd in (64, 128) and os.environ.get('FT_ATTN_FUSED', '1') == '1':
+        if route == 'fused':
             att = H.attn_fwd(qkv, key_pad, nh, scale, 0.0, 0)[0]
         else:
             att = _attn_unfused(qkv, key_pad, nh, scale, 0.0, 0)[0]
@@ -287,31 +296,40 @@ def check_posenc_length(T: int, pe: torch.Tensor) -> None:
         raise _lib.FtError(f'PositionalEncoding: sequence of {T} positions exceeds the pe buffer ({pe.shape[0]})')
 
 
+def posenc_fwd(x, pe, scale):
+    """x + scale * pe[:T] on contiguous x [B,T,D]: the one place that checks the length and launches ft_posenc_fwd"""
+    B, T, D = x.shape
+    check_posenc_length(T, pe)
+    out = torch.empty_like(x)
+    _lib.call('ft_posenc_fwd', x.data_ptr(), pe.data_ptr(), scale.data_ptr(), out.data_ptr(), B, T, D, H._stream())
+    return out
+
+
+def posenc_bwd_scale(dout, pe, scale):
+    """gradient of the learnable scale, sum(dout * pe[:T]), emitted like every other parameter gradient"""
+    B, T, D = dout.shape
+
+    def dscale(o):
+        ws = H.workspace(_lib.query('ft_posenc_workspace'), dout.device)
+        _lib.call('ft_posenc_bwd_scale', dout.data_ptr(), pe.data_ptr(), o.data_ptr(), B, T, D, ws.data_ptr(),
+                  ws.numel(), H._stream())
+
+    return _emit(scale, dscale, heavy=False)
+
+
 class PosEncFn(Function):
     """x + scale * pe[:T]  (PositionalEncoding.forward, common_layers.py:143-145)."""
 
     @staticmethod
     def forward(ctx, x, pe, scale):
-        x = _c(x)
-        B, T, D = x.shape
-        check_posenc_length(T, pe)
-        out = torch.empty_like(x)
-        _lib.call('ft_posenc_fwd', x.data_ptr(), pe.data_ptr(), scale.data_ptr(), out.data_ptr(), B, T, D, H._stream())
         ctx.save_for_backward(pe, scale)
-        return out
+        return posenc_fwd(_c(x), pe, scale)
 
     @staticmethod
     def backward(ctx, dout):
         pe, scale = ctx.saved_tensors
         dout = _c(dout)
-        B, T, D = dout.shape
-
-        def dscale(o):
-            ws = H.workspace(_lib.query('ft_posenc_workspace'), dout.device)
-            _lib.call('ft_posenc_bwd_scale', dout.data_ptr(), pe.data_ptr(), o.data_ptr(), B, T, D, ws.data_ptr(),
-                      ws.numel(), H._stream())
-
-        return dout, None, _emit(scale, dscale, heavy=False)
+        return dout, None, posenc_bwd_scale(dout, pe, scale)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -354,6 +372,13 @@ _GRAD_FIELDS = ('g_in_w', 'g_in_b', 'g_out_w', 'g_out_b', 'g_c1_w', 'g_c1_b', 'g
 _side_ws = {}
 
 
+def _block_params(l: nn.Module):
+    """the twelve parameter tensors of an FFTBlock in the order TransformerFn takes them, which is _GRAD_FIELDS' order"""
+    a = l.self_attn
+    return [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, l.conv1.weight, l.conv1.bias,
+            l.conv2.weight, l.conv2.bias, l.norm1.weight, l.norm1.bias, l.norm2.weight, l.norm2.bias]
+
+
 def _carve(buf: torch.Tensor, sizes):
     """16-byte aligned float sub-buffers of one allocation -> (device addresses, element offsets)"""
     base, off, out, offs = buf.data_ptr(), 0, [], []
@@ -370,8 +395,7 @@ def _arena(sizes, device):
 
 def composite_ok(d: int, nheads: int) -> bool:
     """whole blocks per C call: the bf16 mode with the fused attention (head width 64 / 128)"""
-    return (H.gemm_precision_mode() == 'bf16' and d % nheads == 0 and d // nheads in (64, 128)
-            and os.environ.get('FT_ATTN_FUSED', '1') == '1' and os.environ.get('FT_FFT_COMPOSITE', '1') == '1')
+    return d % nheads == 0 and attn_route(d // nheads) == 'fused' and os.environ.get('FT_FFT_COMPOSITE', '1') == '1'
 
 
 def blocks_fwd_composite(h, key_pad, params, nhead, p, eps1, eps2, seeds):
@@ -505,10 +529,8 @@ class TransformerFn(Function):
     def forward(ctx, x, key_pad, pe, pe_scale, norm_g, norm_b, cfg, *params):
         nhead, p_blk, p_pe, training, eps1, eps2, eps_f = cfg
         x = _c(x)
-        B, T, D = x.shape
-        check_posenc_length(T, pe)
-        h = torch.empty_like(x)
-        _lib.call('ft_posenc_fwd', x.data_ptr(), pe.data_ptr(), pe_scale.data_ptr(), h.data_ptr(), B, T, D, H._stream())
+        D = x.shape[2]
+        h = posenc_fwd(x, pe, pe_scale)
         pe_seed = 0
         if training and p_pe > 0:
             pe_seed = _seed()
@@ -558,14 +580,7 @@ class TransformerFn(Function):
         ctx.tapes = None
         if p_pe > 0:
             d = H.dropout(d, p_pe, pe_seed)
-        B, T, D = d.shape
-
-        def dscale(o):
-            ws = H.workspace(_lib.query('ft_posenc_workspace'), d.device)
-            _lib.call('ft_posenc_bwd_scale', d.data_ptr(), pe.data_ptr(), o.data_ptr(), B, T, D, ws.data_ptr(),
-                      ws.numel(), H._stream())
-
-        g_scale = _emit(pe_scale, dscale, heavy=False)
+        g_scale = posenc_bwd_scale(d, pe, pe_scale)
         return (d if ctx.needs_input_grad[0] else None, None, None, g_scale, g_ng, g_nb, None, *grads)
 
 
@@ -585,8 +600,6 @@ class PositionalEncoding(nn.Module):
         self.register_buffer('pe', pe.unsqueeze(0).transpose(0, 1))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:            # x [B,T,d]
-        if x.shape[1] > self.pe.shape[0]:
-            raise _lib.FtError(f'sequence length {x.shape[1]} exceeds PositionalEncoding max_len {self.pe.shape[0]}')
         x = PosEncFn.apply(x, self.pe, self.scale)
         return _dropout(x, self.p, self.training)
 
@@ -662,14 +675,7 @@ class ForwardTransformer(nn.Module):
             for layer in self.layers:
                 x = layer(x, key_pad)
             return AddLayerNormFn.apply(x, None, self.norm.weight, self.norm.bias, self.norm.eps)
-        if x.shape[1] > self.pos_encoder.pe.shape[0]:
-            raise _lib.FtError(f'sequence length {x.shape[1]} exceeds PositionalEncoding max_len '
-                               f'{self.pos_encoder.pe.shape[0]}')
-        flat = []
-        for l in self.layers:
-            a = l.self_attn
-            flat += [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, l.conv1.weight, l.conv1.bias,
-                     l.conv2.weight, l.conv2.bias, l.norm1.weight, l.norm1.bias, l.norm2.weight, l.norm2.bias]
+        flat = [t for l in self.layers for t in _block_params(l)]
         l0 = self.layers[0]
         cfg = (l0.nhead, l0.p, self.pos_encoder.p, self.training, l0.norm1.eps, l0.norm2.eps, self.norm.eps)
         return TransformerFn.apply(x, key_pad, self.pos_encoder.pe, self.pos_encoder.scale, self.norm.weight,
@@ -679,12 +685,7 @@ class ForwardTransformer(nn.Module):
         """eval forward of a ragged batch, operation by operation in both precisions (the C-issued composite is the
         training path): x [B,T,d], lens int64 [B] on the device -> [B,T,d], exactly 0 at t >= lens[b].  Rows of x at
         t >= lens[b] are never read into a valid row (with the fused attention kernel they may even hold NaN)."""
-        x = _c(x)
-        B, T, D = x.shape
-        check_posenc_length(T, self.pos_encoder.pe)
-        h = torch.empty_like(x)
-        _lib.call('ft_posenc_fwd', x.data_ptr(), self.pos_encoder.pe.data_ptr(), self.pos_encoder.scale.data_ptr(),
-                  h.data_ptr(), B, T, D, H._stream())
+        h = posenc_fwd(_c(x), self.pos_encoder.pe, self.pos_encoder.scale)
         for layer in self.layers:
             h = layer.forward_lens(h, lens)
         return H.add_layernorm_fwd_lens(h, None, self.norm.weight, self.norm.bias, lens, self.norm.eps)
@@ -759,9 +760,7 @@ class FastPitch(AcousticModel):
     def _mel(self, x_idx, tok_mask, dur, pitch, energy, frame_lens: Optional[torch.Tensor]):
         x = ops.EmbeddingFn.apply(x_idx, self.embedding.weight)
         x = self.prenet(x, src_pad_mask=tok_mask)
-        x = ops.CondAddFn.apply(x, pitch, energy, self.pitch_proj.weight, self.pitch_proj.bias,
-                                self.energy_proj.weight, self.energy_proj.bias, self.pitch_strength,
-                                self.energy_strength, False)
+        x = self._cond_add(x, pitch, energy, False)
         x = self.lr(x, dur)
         frame_mask = None
         if frame_lens is not None:          # fast_pitch.py:152-154
@@ -813,67 +812,24 @@ class FastPitch(AcousticModel):
             m = H.transpose_pad_fwd(mel_cl, mel_cl.shape[1], 0.0)
             return {'mel': m, 'mel_post': m, 'dur': dur_in, 'pitch': pitch_hat, 'energy': energy_hat}
 
+    checks_tokens = True
+
     @precision_scoped
     def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, alpha=1.0,
                        pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
                        energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
-        """generate() of a RAGGED batch of sentences -- the contract of ForwardTacotron.generate_batch (same arguments,
-        result keys and errors): for every item b the valid parts of the result equal
-        generate(x[b:b+1, :x_len[b]], alpha, ...) on the same model (to the rounding of the matmul mode; `mel_len`
-        exactly in fp32 mode).
+        """base.AcousticModel.generate_batch, the whole call under the model's `matmul_dtype`"""
+        return super().generate_batch(x, x_len, alpha, pitch_function, energy_function)
 
-        x: int64 [B,Tx] on the device; entries at t >= x_len[b] are ignored, whatever they hold.  x_len: int64 [B], on the
-        host or the device, 1 <= x_len[b] <= Tx (anything else raises FtError).  pitch_function / energy_function get
-        [B,1,Tx] (zero at t >= x_len[b]) and must act PER TOKEN; their results are masked again.
+    def _ragged_prenet(self, x, xl):
+        return self.prenet.forward_lens(H.embedding_fwd_lens(x, xl, self.embedding.weight), xl)
 
-        Valid tokens are NON-ZERO.  generate() masks the prenet's keys where x == 0 (fast_pitch.py:199), which inside a
-        sentence only happens if the pad symbol itself is used as a token; here the lengths say what is padding, and a 0
-        at t < x_len[b] raises FtError instead of being silently treated either way.
+    def _ragged_regulate(self, h, pred):
+        h = self._cond_add(h, pred['pitch'], pred['energy'], False)
+        return self.lr(h, pred['dur'])                                    # zero rows at t >= mel_len[b]; syncs to size Tm
 
-        -> mel, mel_post (one tensor, as in generate) [B,n_mels,Tm] with Tm = max(mel_len) and padding_value at
-        t >= mel_len[b]; mel_len int64 [B]; dur [B,Tx], pitch / energy [B,1,Tx], all three 0 at t >= x_len[b].  Per item: if
-        the truncated durations of the valid tokens sum to <= 0 they all become 2.0 (fast_pitch.py:176-177); repeats are
-        (clamp(dur, 0) + 0.5).long().  One host synchronisation (sizing Tm), as in generate().
-
-        The zero-token check and the range check of an x_len that lives on the device run on the device: the FtError is
-        raised behind that one synchronisation, and the flag travels through ONE pinned host word kept on the module -- so
-        a model must not run generate_batch from two threads or on two streams at once."""
-        self.eval()
-        with torch.no_grad():
-            on_host = self._check_ragged_batch(x, x_len)
-            B, Tx = x.shape
-            x = x.contiguous()
-            xl = x_len.to(x.device).contiguous()
-
-            def predict():
-                # the three predictors, in generate()'s order; everything they hand on is zero at t >= x_len[b]
-                dur = self.dur_pred.forward_lens(x, xl, alpha=alpha).reshape(B, Tx)
-                mel_len, bad = H.gen_durations(dur, xl)           # per-item fallback, clamp; dur in its returned form
-                H.check_tokens_lens(x, xl, bad)
-                out = {'dur': dur, 'mel_len': mel_len, 'bad': bad}
-                for key, pred, fn in (('pitch', self.pitch_pred, pitch_function),
-                                      ('energy', self.energy_pred, energy_function)):
-                    out[key] = self._masked_user_series(key, fn, pred.forward_lens(x, xl).transpose(1, 2), xl)
-                return out
-
-            # the predictors only meet the trunk behind the prenet: side stream
-            fork = self._fork_predictors(x.device, predict, overlap=os.environ.get('FT_GEN_OVERLAP', '1') == '1')
-            h = self.prenet.forward_lens(H.embedding_fwd_lens(x, xl, self.embedding.weight), xl)
-            pred = self._join_predictors(fork)
-            bad_host = self._bad_flag_host()
-            bad_host.copy_(pred['bad'], non_blocking=True)
-            mel_len = pred['mel_len']
-            h = ops.CondAddFn.apply(h, pred['pitch'].reshape(B, Tx), pred['energy'].reshape(B, Tx), self.pitch_proj.weight,
-                                    self.pitch_proj.bias, self.energy_proj.weight, self.energy_proj.bias,
-                                    self.pitch_strength, self.energy_strength, False)
-            h = self.lr(h, pred['dur'])                           # zero rows at t >= mel_len[b]; syncs to size Tm
-            flags = int(bad_host[0])
-            if flags & 1 and not on_host:
-                raise _lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}]')
-            if flags & 2:
-                raise _lib.FtError('generate_batch: token id 0 inside a sentence (t < x_len[b]); valid tokens are non-zero')
-            h = self.postnet.forward_lens(h, mel_len)
-            mel = ops.LinearFn.apply(h, self.lin.weight, self.lin.bias)       # [B,Tm,n_mels]
-            m = H.transpose_pad_lens_fwd(mel, mel_len, mel.shape[1], float(self.padding_value))
-            return {'mel': m, 'mel_post': m, 'mel_len': mel_len, 'dur': pred['dur'], 'pitch': pred['pitch'],
-                    'energy': pred['energy']}
+    def _ragged_finish(self, h, mel_len):
+        h = self.postnet.forward_lens(h, mel_len)
+        mel = ops.LinearFn.apply(h, self.lin.weight, self.lin.bias)       # [B,Tm,n_mels]
+        m = H.transpose_pad_lens_fwd(mel, mel_len, mel.shape[1], float(self.padding_value))
+        return m, m                                                       # one tensor, as in generate

@@ -125,24 +125,25 @@ class BatchNormConv(nn.Module):
         if self.training:
             return ops.BatchNormConvFn.apply(x, self.conv.weight, bn.weight, bn.bias, residual, bn.running_mean,
                                              bn.running_var, self.relu is True)
-        # eval: BatchNorm folds into the conv epilogue (scale/shift after the ReLU)
-        _eval_needs_no_grad(x, self.conv.weight)
-        scale, shift = H.bn_fold_eval(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-        wp = H.conv_pack_weight(self.conv.weight)
-        acc = _c_clone(residual) if residual is not None else None
-        return H.conv1d_fwd(x.contiguous(), wp, relu=self.relu is True, Tout=x.shape[1], scale=scale, shift=shift,
-                            accumulate_into=acc)
+        return self._eval(x, residual)
 
     def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """eval forward of a ragged batch whose rows t >= lens[b] are zero on input: they are stored as zeros again
         (scale * relu(conv) + shift is not zero there), so the next convolution reads zeros across an item's end"""
-        bn = self.bnorm
         if self.training:
             raise H._lib.FtError('BatchNormConv.forward_lens is the eval-mode (inference) path')
+        return self._eval(x, residual, lens)
+
+    def _eval(self, x: torch.Tensor, residual: Optional[torch.Tensor], lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """eval: BatchNorm folds into the conv epilogue (scale/shift after the ReLU); lens: the ragged-batch form"""
+        bn = self.bnorm
         _eval_needs_no_grad(x, self.conv.weight)
         scale, shift = H.bn_fold_eval(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
         wp = H.conv_pack_weight(self.conv.weight)
         acc = _c_clone(residual) if residual is not None else None
+        if lens is None:
+            return H.conv1d_fwd(x.contiguous(), wp, relu=self.relu is True, Tout=x.shape[1], scale=scale, shift=shift,
+                                accumulate_into=acc)
         return H.conv1d_fwd_lens(x.contiguous(), wp, relu=self.relu is True, lens=lens, scale=scale, shift=shift,
                                  accumulate_into=acc)
 
@@ -208,20 +209,14 @@ class CBHG(nn.Module):
         return out
 
     def forward(self, x: torch.Tensor, time_major_out: bool = False) -> torch.Tensor:
+        if not self.training:
+            return self._eval(x, time_major_out)
         K = len(self.bank_kernels)
-        C = self.conv1d_bank[0].conv.weight.shape[0]
         gamma, beta, rm, rv = self._bank_flat()
-        if self.training:
-            ws = [m.conv.weight for m in self.conv1d_bank]
-            gs = [m.bnorm.weight for m in self.conv1d_bank]
-            bs = [m.bnorm.bias for m in self.conv1d_bank]
-            y = ops.ConvBankFn.apply(x, K, gamma, beta, rm, rv, *ws, *gs, *bs)
-        else:
-            B, T, Cin = x.shape
-            _eval_needs_no_grad(x, self.conv1d_bank[0].conv.weight)
-            scale, shift = H.bn_fold_eval(gamma, beta, rm, rv, self.conv1d_bank[0].bnorm.eps)
-            wp_all = torch.cat([H.conv_pack_weight(m.conv.weight).reshape(-1) for m in self.conv1d_bank])
-            y = H.maxpool2_fwd(H.conv_bank_fwd(x, wp_all, K, C, relu=True, Tout=T, scale=scale, shift=shift))
+        ws = [m.conv.weight for m in self.conv1d_bank]
+        gs = [m.bnorm.weight for m in self.conv1d_bank]
+        bs = [m.bnorm.bias for m in self.conv1d_bank]
+        y = ops.ConvBankFn.apply(x, K, gamma, beta, rm, rv, *ws, *gs, *bs)
         y = _dropout(y, self.dropout, self.training)
         y = self.conv_project1(y)
         y = _dropout(y, self.dropout, self.training)
@@ -236,18 +231,26 @@ class CBHG(nn.Module):
         needs no mask: its only reader across time is the max-pool, which masks its output."""
         if self.training:
             raise H._lib.FtError('CBHG.forward_lens is the eval-mode (inference) path')
+        return self._eval(x, time_major_out, lens)
+
+    def _eval(self, x: torch.Tensor, time_major_out: bool, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """eval: the bank's BatchNorms fold into its convolutions' epilogue; lens: the ragged-batch form of every step
+        that reads across time"""
         K = len(self.bank_kernels)
         C = self.conv1d_bank[0].conv.weight.shape[0]
         gamma, beta, rm, rv = self._bank_flat()
-        B, T, Cin = x.shape
+        T = x.shape[1]
         _eval_needs_no_grad(x, self.conv1d_bank[0].conv.weight)
         scale, shift = H.bn_fold_eval(gamma, beta, rm, rv, self.conv1d_bank[0].bnorm.eps)
         wp_all = torch.cat([H.conv_pack_weight(m.conv.weight).reshape(-1) for m in self.conv1d_bank])
-        y = H.maxpool2_fwd_lens(H.conv_bank_fwd(x, wp_all, K, C, relu=True, Tout=T, scale=scale, shift=shift), lens)
-        y = self.conv_project1.forward_lens(y, lens)
-        y = self.conv_project2.forward_lens(y, lens, residual=x)
+        y = H.conv_bank_fwd(x, wp_all, K, C, relu=True, Tout=T, scale=scale, shift=shift)
+        y = H.maxpool2_fwd(y) if lens is None else H.maxpool2_fwd_lens(y, lens)
+        y = self.conv_project1._eval(y, None, lens)
+        y = self.conv_project2._eval(y, x, lens)
         y = ops.LinearFn.apply(y, self.pre_highway.weight, None)
-        y = ops.highway_stack(y, list(self.highways))
+        y = ops.highway_stack(y, list(self.highways))     # gates inside the GEMM epilogues (width % 32 == 0)
+        if lens is None:
+            return self.rnn(y, time_major_out=time_major_out)
         return self.rnn.forward_lens(y, lens, time_major_out=time_major_out)
 
 
@@ -341,9 +344,7 @@ class ForwardTacotron(AcousticModel):
         x = self.prenet(x, time_major_out=True)                             # [Tx,B,2P] (recurrence layout)
         if late_inputs is not None:
             dur, pitch, energy = late_inputs()
-        x = ops.CondAddFn.apply(x, pitch, energy, self.pitch_proj.weight, self.pitch_proj.bias,
-                                self.energy_proj.weight, self.energy_proj.bias, self.pitch_strength,
-                                self.energy_strength, True)                 # -> [B,Tx,2P]
+        x = self._cond_add(x, pitch, energy, True)                          # -> [B,Tx,2P]
         x = regulate_and_decode(self, x, dur, mel_lens)
         mel = ops.LinearFn.apply(x, self.lin.weight, self.lin.bias)        # [B,T,n_mels]
         post = self.postnet(mel, time_major_out=True)                       # [T,B,2Q]
@@ -384,30 +385,6 @@ class ForwardTacotron(AcousticModel):
         with torch.no_grad():
             return self._generate(x, alpha, pitch_function, energy_function)
 
-    def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, alpha=1.0,
-                       pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
-                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
-        """generate() of a RAGGED batch of sentences: for every item b the valid parts of the result equal
-        generate(x[b:b+1, :x_len[b]], alpha, ...) on the same model (to fp32 rounding; `mel_len` exactly).
-
-        x: int64 [B,Tx] on the device; entries at t >= x_len[b] are ignored, whatever they hold.  x_len: int64 [B], on the
-        host or the device, 1 <= x_len[b] <= Tx (anything else raises FtError).  pitch_function / energy_function get
-        [B,1,Tx] (zero at t >= x_len[b]) and must act PER TOKEN -- a function that mixes tokens or items (a mean over
-        the batch, a filter along t) breaks the per-item contract; their results are masked again.
-
-        -> mel, mel_post [B,n_mels,Tm] with Tm = max(mel_len) and padding_value at t >= mel_len[b]; mel_len int64 [B];
-        dur [B,Tx], pitch / energy [B,1,Tx], all three 0 at t >= x_len[b].  Per item: if the truncated durations of the
-        valid tokens sum to <= 0 they all become 2.0 (forward_tacotron.py:176-177); repeats are (clamp(dur, 0) + 0.5).long().
-        One host synchronisation (sizing Tm), as in generate().
-
-        An x_len that lives on the device is range-checked on the device: the FtError is raised only after the trunk up
-        to the decoder LSTM has been enqueued (behind that one synchronisation), and the flag travels through ONE pinned
-        host word kept on the module -- so a model must not run generate_batch with a device-side x_len from two
-        threads or on two streams at once (a host-side x_len is checked up front and has no such limit)."""
-        self.eval()
-        with torch.no_grad():
-            return self._generate_batch(x, x_len, alpha, pitch_function, energy_function)
-
     def generate_jit(self, x: torch.Tensor, alpha: float = 1.0, beta: float = 1.0) -> Dict[str, torch.Tensor]:
         """forward_tacotron.py:186-200: generate with the pitch scaled by beta.  Eager entry; the TorchScript surface
         (`torch.jit.script(model).generate_jit`, README.md:159-171 of the reference) is export.ScriptedForwardTacotron,
@@ -428,47 +405,24 @@ class ForwardTacotron(AcousticModel):
         T = mel_cl.shape[1]
         return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0), **pred}
 
-    def _generate_batch(self, x, x_len, alpha, pitch_function, energy_function):
-        on_host = self._check_ragged_batch(x, x_len)
-        B, Tx = x.shape
-        x = x.contiguous()
-        xl = x_len.to(x.device).contiguous()
-
-        def predict():
-            # the three predictors, in generate()'s order; everything they hand on is zero at t >= x_len[b]
-            dur = self.dur_pred.forward_lens(x, xl, alpha=alpha).reshape(B, Tx)
-            mel_len, bad = H.gen_durations(dur, xl)               # per-item fallback, clamp; dur in its returned form
-            out = {'dur': dur, 'mel_len': mel_len, 'bad': bad}
-            for key, pred, fn in (('pitch', self.pitch_pred, pitch_function), ('energy', self.energy_pred, energy_function)):
-                out[key] = self._masked_user_series(key, fn, pred.forward_lens(x, xl).transpose(1, 2), xl)   # [B,1,Tx]
-            return out
-
-        # the predictors only meet the trunk behind the prenet: side stream, as in _generate_fork
-        fork = self._fork_predictors(x.device, predict, overlap=os.environ.get('FT_GEN_OVERLAP', '1') == '1')
-        pred = fork[2]
+    # -- generate_batch: what base.AcousticModel's driver needs from this model -----------------------------------
+    def _ragged_prenet(self, x, xl):
         h = H.embedding_fwd_lens(x, xl, self.embedding.weight)
-        h = self.prenet.forward_lens(h, xl, time_major_out=True)             # [Tx,B,2P], zero at t >= x_len[b]
-        self._join_predictors(fork)
-        bad_host = None
-        if not on_host:     # x_len never visited the host: its range check rides on the one synchronisation below
-            bad_host = self._bad_flag_host()
-            bad_host.copy_(pred['bad'], non_blocking=True)
-        mel_len = pred['mel_len']
-        h = ops.CondAddFn.apply(h, pred['pitch'].reshape(B, Tx), pred['energy'].reshape(B, Tx), self.pitch_proj.weight,
-                                self.pitch_proj.bias, self.energy_proj.weight, self.energy_proj.bias,
-                                self.pitch_strength, self.energy_strength, True)                 # -> [B,Tx,2P]
-        h = regulate_and_decode(self, h, pred['dur'], mel_len)               # packed LSTM; syncs to size Tm
-        if bad_host is not None and int(bad_host[0]) != 0:
-            raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}]')
+        return self.prenet.forward_lens(h, xl, time_major_out=True)           # [Tx,B,2P], zero at t >= x_len[b]
+
+    def _ragged_regulate(self, h, pred):
+        h = self._cond_add(h, pred['pitch'], pred['energy'], True)            # -> [B,Tx,2P]
+        return regulate_and_decode(self, h, pred['dur'], pred['mel_len'])     # packed LSTM; syncs to size Tm
+
+    def _ragged_finish(self, h, mel_len):
+        B = h.shape[0]
         # lin's bias (and the LSTM's padding_value) make the padded frames non-zero: mask before the postnet's convolutions
         mel = H.mask_rows(ops.LinearFn.apply(h, self.lin.weight, self.lin.bias), mel_len)
         post = self.postnet.forward_lens(mel, mel_len, time_major_out=True)  # [Tm,B,2Q]
         post = ops.LinearFn.apply(post, self.post_proj.weight, None, B)      # -> [B,Tm,n_mels]
         Tm = mel.shape[1]
         pad = float(self.padding_value)
-        return {'mel': H.transpose_pad_lens_fwd(mel, mel_len, Tm, pad),
-                'mel_post': H.transpose_pad_lens_fwd(post.contiguous(), mel_len, Tm, pad), 'mel_len': mel_len,
-                'dur': pred['dur'], 'pitch': pred['pitch'], 'energy': pred['energy']}
+        return H.transpose_pad_lens_fwd(mel, mel_len, Tm, pad), H.transpose_pad_lens_fwd(post.contiguous(), mel_len, Tm, pad)
 
     def _generate_mel(self, x: torch.Tensor, dur_hat: torch.Tensor, pitch_hat: torch.Tensor,
                       energy_hat: torch.Tensor) -> Dict[str, torch.Tensor]:

@@ -1,16 +1,14 @@
-"""GPU: FastPitch.generate_batch -- every item of a ragged batch gets what generate() gives it alone.  Mirrors
-test_gpu_generate_batch.py; the length-aware attention kernel under it is tested alone in test_gpu_attn_lens.py."""
+"""GPU: FastPitch.generate_batch -- every item of a ragged batch gets what generate() gives it alone.  The shared
+contract is tests/generate_batch_contract.py; the length-aware attention kernel under it is tested alone in test_gpu_attn_lens.py."""
 import numpy as np
 import pytest
 import torch
 
+import generate_batch_contract as contract
+from generate_batch_contract import KEYS
 from helpers import TINY_FP, fp_state, load_npz, maxdiff
 
 pytestmark = pytest.mark.gpu
-
-PAD = float(np.float32(-11.5129))
-KEYS = ('mel', 'mel_post', 'dur', 'pitch', 'energy')
-BAR = 5e-5              # test_gpu_generate_batch.py / test_gpu_fastpitch.py (generate vs the golden fixture)
 
 
 @pytest.fixture(scope='module')
@@ -28,77 +26,34 @@ def fx():
     return G, m, x, x_len, {k: v.cpu() for k, v in out.items()}
 
 
-def _valid(out, b, L, n):
-    return {'mel': out['mel'][b:b + 1, :, :n], 'mel_post': out['mel_post'][b:b + 1, :, :n], 'dur': out['dur'][b:b + 1, :L],
-            'pitch': out['pitch'][b:b + 1, :, :L], 'energy': out['energy'][b:b + 1, :, :L]}
-
-
-def _check_padding(out, b, L, n):
-    for k in ('mel', 'mel_post'):
-        assert bool((out[k][b, :, n:] == PAD).all()), (b, k, 'padded frames must hold padding_value exactly')
-    assert bool((out['dur'][b, L:] == 0).all()) and bool((out['pitch'][b, :, L:] == 0).all()) and \
-        bool((out['energy'][b, :, L:] == 0).all()), (b, 'padded tokens must be exactly 0')
-
-
 def test_golden(fx):
-    G, m, x, x_len, out = fx
-    B, Tx = x.shape
-    frames = [G[f'item{b}/mel'].shape[2] for b in range(B)]
-    assert out['mel_len'].dtype == torch.int64 and out['mel_len'].tolist() == frames
-    Tm = max(frames)
-    assert out['mel'].shape == out['mel_post'].shape == (B, TINY_FP['n_mels'], Tm)
-    assert out['dur'].shape == (B, Tx) and out['pitch'].shape == out['energy'].shape == (B, 1, Tx)
-    for b in range(B):
-        L, n = int(x_len[b]), frames[b]
-        for k, v in _valid(out, b, L, n).items():
-            d = maxdiff(v, G[f'item{b}/{k}'])
-            print(f'item {b} {k}: {d:.3e}')
-            assert d < BAR, (b, k, d)
-        _check_padding(out, b, L, n)
+    contract.check_golden(fx, TINY_FP)
 
 
 def test_pad_content_is_irrelevant(fx):
-    G, m, x, x_len, out = fx
-    g = torch.Generator().manual_seed(3)
-    junk = torch.randint(1, TINY_FP['num_chars'], x.shape, generator=g)
-    pad = torch.arange(x.shape[1])[None, :] >= x_len[:, None]
-    x2 = torch.where(pad, junk, x.cpu()).cuda()
-    assert bool((x2.cpu()[pad] != 0).all()) and x2.shape == x.shape
-    out2 = m.generate_batch(x2, x_len.cuda(), alpha=float(G['alpha']))      # (x_len on the device this time)
-    assert set(out2) == set(out)
-    for k in out:
-        assert torch.equal(out2[k].cpu(), out[k]), f'{k} depends on what the padding holds'
+    contract.check_pad_content_is_irrelevant(fx, TINY_FP)
 
 
 def test_neighbours_are_irrelevant(fx):
-    G, m, x, x_len, out = fx
-    alpha = float(G['alpha'])
-    b, L = 2, int(x_len[2])                       # 4 tokens; in the batch of 5 it sits between a 1- and a 7-token item
-    n = int(out['mel_len'][b])
-    in5 = _valid(out, b, L, n)
-    g = torch.Generator().manual_seed(4)
-    x2 = torch.zeros(2, 9, dtype=torch.long)
-    x2[0] = torch.randint(1, TINY_FP['num_chars'], (9,), generator=g)
-    x2[1, :L] = x[b, :L].cpu()
-    o2 = m.generate_batch(x2.cuda(), torch.tensor([9, L]), alpha=alpha)
-    assert int(o2['mel_len'][1]) == n
-    in2 = _valid({k: v.cpu() for k, v in o2.items()}, 1, L, n)
-    alone = m.generate(x[b:b + 1, :L].contiguous(), alpha=alpha)
-    assert alone['mel'].shape[2] == n
-    for k in KEYS:
-        a = alone[k].cpu()
-        assert maxdiff(in5[k], a) < BAR and maxdiff(in2[k], a) < BAR and maxdiff(in5[k], in2[k]) < BAR, k
+    contract.check_neighbours_are_irrelevant(fx, TINY_FP)
 
 
 def test_existing_generate_differs_in_a_padded_batch(fx):
     """why the method exists: generate() runs the predictors and the postnet without any padding mask, so in the
     zero-padded batch a short item's own tokens attend to the pad rows and its convolutions read them"""
-    G, m, x, x_len, out = fx
-    o = m.generate(x, alpha=float(G['alpha']))
-    b, L = 4, int(x_len[4])                       # 2 tokens beside 7-token neighbours
-    d = maxdiff(o['pitch'][b:b + 1, :, :L].cpu(), G[f'item{b}/pitch'])
-    print(f'generate() in the padded batch, item {b} pitch: {d:.3e} off the per-item result')
-    assert d > BAR
+    contract.check_existing_generate_differs_in_a_padded_batch(fx, TINY_FP)
+
+
+def test_user_function_applies_per_token(fx):
+    contract.check_user_function_applies_per_token(fx, TINY_FP)
+
+
+def test_bad_user_function_raises_and_nothing_sticks(fx):
+    contract.check_bad_user_function_raises_and_nothing_sticks(fx, TINY_FP)
+
+
+def test_overlap_switch_is_bit_neutral(fx, monkeypatch):
+    contract.check_overlap_switch_is_bit_neutral(fx, TINY_FP, monkeypatch)
 
 
 def test_zero_token_inside_a_sentence_raises(fx):
@@ -166,11 +121,11 @@ def test_production_widths_vs_oracle_per_item(conv2_kernel, fft, seed):
     assert out['mel_len'].tolist() == [w['mel'].shape[2] for w in want]
     for b, L in enumerate(X_LEN):
         n = want[b]['mel'].shape[2]
-        for k, v in _valid(out, b, L, n).items():
+        for k, v in contract.valid(out, b, L, n).items():
             d = maxdiff(v, want[b][k])
             print(f'conv2 k = {conv2_kernel}, item {b} {k}: {d:.3e}')
             assert d < 1e-4, (b, k, d)              # test_gpu_generate_batch.py::test_production_widths_vs_oracle_per_item
-        _check_padding(out, b, L, n)
+        contract.check_padding(out, b, L, n)
 
 
 def test_production_widths_bf16_vs_per_item_generate():
@@ -200,8 +155,8 @@ def test_production_widths_bf16_vs_per_item_generate():
         alone = m.generate(xd[b:b + 1, :L].contiguous(), alpha=ALPHA)
         n = alone['mel'].shape[2]
         assert int(out['mel_len'][b]) == n, b
-        for k, v in _valid(out, b, L, n).items():
+        for k, v in contract.valid(out, b, L, n).items():
             d = maxdiff(v, alone[k].cpu())
             print(f'bf16 item {b} {k}: {d:.3e} (bar {bar[k]:.3e})')
             assert d <= bar[k], (b, k, d, bar[k])
-        _check_padding(out, b, L, n)
+        contract.check_padding(out, b, L, n)
