@@ -201,10 +201,12 @@ class AcousticModel(nn.Module):
 
     # -- generate_batch: the driver, its helpers and the hooks a model supplies --------------------------------------
     checks_tokens: bool = False     # token id 0 at t < x_len[b] raises (the models whose generate() masks keys where x == 0)
+    speaker_emb_dims: int = 0       # > 0: the model is speaker-conditioned, generate_batch takes one speaker row per item
 
     def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, alpha=1.0,
                        pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
-                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
+                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e, *,
+                       speaker_emb: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """generate() of a RAGGED batch of sentences: for every item b the valid parts of the result equal
         generate(x[b:b+1, :x_len[b]], alpha, ...) on the same model (to the rounding of the matmul mode; `mel_len` exactly
         in fp32 mode).
@@ -217,6 +219,17 @@ class AcousticModel(nn.Module):
         A model with `checks_tokens` (FastPitch) wants valid tokens NON-ZERO.  Its generate() masks the prenet's keys where
         x == 0 (fast_pitch.py:199), which inside a sentence only happens if the pad symbol itself is used as a token; here
         the lengths say what is padding, and a 0 at t < x_len[b] raises FtError instead of being silently treated either way.
+
+        The speaker-conditioned models (`speaker_emb_dims` > 0; their own generate_batch(x, x_len, speaker_emb, alpha, ...)
+        mirrors generate(x, speaker_emb, alpha, ...)) take `speaker_emb`: float32 [B, speaker_emb_dims] on the device, ONE
+        ROW PER ITEM, rows may all differ; any other shape, dtype or device raises FtError.  The contract reads
+        generate(x[b:b+1, :x_len[b]], speaker_emb[b:b+1], alpha, ...) for every item with x_len[b] >= 2; `pitch_cond`
+        matches exactly in fp32 mode, like `mel_len`.  Their generate() raises on a ONE-token sentence, like the reference's
+        (its argmax chain squeezes the time axis away); generate_batch gives such an item the per-token result: the argmax
+        over the classes for that one token, everything else as for longer items.  The result then also holds
+        `pitch_cond`, int64 [B,Tx]: the per-token argmax of the pitch_cond predictor's logits at t < x_len[b], 0 past it.
+        It is decided per item and token on the device and feeds the conditional embedding of that item's dur and pitch
+        predictors.
 
         -> mel, mel_post [B,n_mels,Tm] with Tm = max(mel_len) and padding_value at t >= mel_len[b] (one tensor where the
         model's generate() returns one); mel_len int64 [B]; dur [B,Tx], pitch / energy [B,1,Tx], all three 0 at
@@ -233,45 +246,59 @@ class AcousticModel(nn.Module):
           _ragged_prenet(x, xl) -> h            token-side trunk up to where the predictors are needed
           _ragged_regulate(h, pred) -> h        behind the join: CondAddFn (_cond_add), then the step that synchronises
           _ragged_finish(h, mel_len) -> (mel, mel_post)   behind the flag check, up to H.transpose_pad_lens_fwd
-        and overrides _ragged_predict if its predictors take more than (x, lens)."""
+        and overrides _ragged_predict if its predictors take more than (x, lens).  A speaker-conditioned model's
+        _ragged_prenet, _ragged_regulate and _ragged_predict get the speaker rows as the keyword `semb`; the other models
+        are called exactly as before."""
         if not hasattr(self, '_ragged_prenet'):
             raise H._lib.FtError(f'{type(self).__name__} has no generate_batch: it supplies no _ragged_* hooks')
         self.eval()
         with torch.no_grad():
             on_host = self._check_ragged_batch(x, x_len)
+            kw = self._check_speaker_rows(x, speaker_emb)
             x = x.contiguous()
             xl = x_len.to(x.device).contiguous()
             # the predictors only meet the trunk behind the prenet: side stream, as in _generate_fork
-            fork = self._fork_predictors(x.device, lambda: self._ragged_predict(x, xl, alpha, pitch_function, energy_function),
-                                         overlap=_gen_overlap())
-            h = self._ragged_prenet(x, xl)
+            fork = self._fork_predictors(x.device, lambda: self._ragged_predict(x, xl, alpha, pitch_function, energy_function,
+                                                                                **kw), overlap=_gen_overlap())
+            h = self._ragged_prenet(x, xl, **kw)
             pred = self._join_predictors(fork)
             # a host-side x_len was range-checked up front; what was not rides on the one synchronisation of the regulator
             read_flag = (not on_host) or self.checks_tokens
             if read_flag:
                 bad_host = self._bad_flag_host()
                 bad_host.copy_(pred['bad'], non_blocking=True)
-            h = self._ragged_regulate(h, pred)
+            h = self._ragged_regulate(h, pred, **kw)
             flags = int(bad_host[0]) if read_flag else 0
             if flags & 1 and not on_host:
                 raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {x.shape[1]}]')
             if flags & 2:
                 raise H._lib.FtError('generate_batch: token id 0 inside a sentence (t < x_len[b]); valid tokens are non-zero')
             mel, mel_post = self._ragged_finish(h, pred['mel_len'])
-            return {'mel': mel, 'mel_post': mel_post, 'mel_len': pred['mel_len'], 'dur': pred['dur'],
-                    'pitch': pred['pitch'], 'energy': pred['energy']}
+            out = {'mel': mel, 'mel_post': mel_post, 'mel_len': pred['mel_len'], 'dur': pred['dur'],
+                   'pitch': pred['pitch'], 'energy': pred['energy']}
+            if 'pitch_cond' in pred:
+                out['pitch_cond'] = pred['pitch_cond']
+            return out
 
-    def _ragged_predict(self, x: torch.Tensor, xl: torch.Tensor, alpha: float, pitch_function, energy_function):
-        """the three predictors, in generate()'s order; everything they hand on is zero at t >= x_len[b]
-        -> dur [B,Tx] (in its returned form), mel_len, bad (the flag word), pitch / energy [B,1,Tx]"""
+    def _ragged_predict(self, x: torch.Tensor, xl: torch.Tensor, alpha: float, pitch_function, energy_function,
+                        semb: Optional[torch.Tensor] = None):
+        """the predictors, in generate()'s order; everything they hand on is zero at t >= x_len[b]
+        -> dur [B,Tx] (in its returned form), mel_len, bad (the flag word), pitch / energy [B,1,Tx].
+        semb (the speaker-conditioned models): pitch_cond first, the per-token argmax of its predictor's logits (-> the
+        key `pitch_cond`, int64 [B,Tx]), which conditions dur and pitch; then dur, pitch, energy."""
         B, Tx = x.shape
-        dur = self.dur_pred.forward_lens(x, xl, alpha=alpha).reshape(B, Tx)
+        spk, cond, out = (), {}, {}
+        if semb is not None:
+            # multi_fast_pitch.py:255 divides these logits by alpha: that cannot move an argmax for alpha > 0, no launch for it
+            pitch_cond = H.argmax_lens(self.pitch_cond_pred.forward_lens(x, xl, semb), xl)
+            spk, cond, out = (semb,), {'x_cond': pitch_cond}, {'pitch_cond': pitch_cond}
+        dur = self.dur_pred.forward_lens(x, xl, *spk, **cond, alpha=alpha).reshape(B, Tx)
         mel_len, bad = H.gen_durations(dur, xl)                   # per-item fallback, clamp; raises bit 1 of bad
         if self.checks_tokens:
             H.check_tokens_lens(x, xl, bad)                       # raises bit 2
-        out = {'dur': dur, 'mel_len': mel_len, 'bad': bad}
-        for key, pred, fn in (('pitch', self.pitch_pred, pitch_function), ('energy', self.energy_pred, energy_function)):
-            out[key] = self._masked_user_series(key, fn, pred.forward_lens(x, xl).transpose(1, 2), xl)
+        out.update(dur=dur, mel_len=mel_len, bad=bad)
+        for key, pred, fn, kw in (('pitch', self.pitch_pred, pitch_function, cond), ('energy', self.energy_pred, energy_function, {})):
+            out[key] = self._masked_user_series(key, fn, pred.forward_lens(x, xl, *spk, **kw).transpose(1, 2), xl)
         return out
 
     def _cond_add(self, h: torch.Tensor, pitch: torch.Tensor, energy: torch.Tensor, x_time_major: bool) -> torch.Tensor:
@@ -292,6 +319,21 @@ class AcousticModel(nn.Module):
             raise H._lib.FtError(f'generate_batch: every x_len must be in [1, Tx = {Tx}] (got {x_len.tolist()})')
         self._require_device(x)
         return on_host
+
+    def _check_speaker_rows(self, x: torch.Tensor, speaker_emb: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """the speaker rows of generate_batch -> the keyword the speaker-conditioned models' hooks get ({} for the others)"""
+        S = self.speaker_emb_dims
+        if not S:
+            if speaker_emb is not None:
+                raise H._lib.FtError(f'generate_batch: {type(self).__name__} is not speaker-conditioned, it takes no speaker_emb')
+            return {}
+        t = speaker_emb
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (x.shape[0], S) \
+                or t.device != x.device:
+            what = f'{tuple(t.shape)} {t.dtype} on {t.device}' if torch.is_tensor(t) else type(t).__name__
+            raise H._lib.FtError(f'generate_batch: speaker_emb must be float32 [B = {x.shape[0]}, {S}] on {x.device}, one row '
+                                 f'per item (got {what})')
+        return {'semb': t.contiguous()}
 
     def _masked_user_series(self, key: str, fn: Callable[[torch.Tensor], torch.Tensor], v: torch.Tensor,
                             lens: torch.Tensor) -> torch.Tensor:

@@ -29,12 +29,13 @@ __device__ __forceinline__ bf16x8 load_frag(const float* p, bool ok) {
   return cvt8(a, b);
 }
 
-// row-major [64 rows][HD] bf16 tile image, row stride RS bytes
-template <int HD>
+// row-major [ROWS rows][HD] bf16 tile image, row stride RS bytes (ROWS = 64 keys everywhere but in the wide-head kernels of
+// ft_attn_lens.hip, whose key blocks are 32 rows)
+template <int HD, int ROWS = KB>
 struct Tile {
   static constexpr int RS = HD * 2 + 16;
-  static constexpr int BYTES = KB * RS;
-  static constexpr int F4 = KB * HD / 4 / 256;          // float4 per thread per tile
+  static constexpr int BYTES = ROWS * RS;
+  static constexpr int F4 = ROWS * HD / 4 / 256;        // float4 per thread per tile
   // global -> registers (fp32), rows beyond T read as zeros
   __device__ static void load(float4 (&r)[F4], const float* base, long ld, int row0, int T, int tid) {
 #pragma unroll

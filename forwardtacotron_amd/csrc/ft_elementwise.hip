@@ -145,6 +145,61 @@ __global__ void ft_check_tokens_lens_kernel(const long* __restrict__ idx, const 
   if (t < lens[b] && idx[i] == 0) atomicOr(flag, 2);
 }
 
+// the front of a speaker-conditioned predictor on a ragged batch, one launch: out[b,t,:] = [ emb[idx[b,t]] |
+// cemb[cond[b,t]] | semb[b] ] at t < lens[b] and zeros past it -- the speaker row too, or the k > 1 convolutions behind
+// it would read it from the padding.  idx / cond are not read at t >= lens[b].
+__global__ void ft_predictor_front_lens_kernel(const long* __restrict__ idx, const long* __restrict__ cond,
+                                               const long* __restrict__ lens, const float* __restrict__ emb, int Ce, int V,
+                                               const float* __restrict__ cemb, int Cc, int Vc,
+                                               const float* __restrict__ semb, int S, float* __restrict__ out, int B, int T,
+                                               int* __restrict__ err) {
+  const int C = Ce + Cc + S;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * T * C) return;
+  long r = i / C;
+  int c = (int)(i - r * C);
+  int b = (int)(r / T), t = (int)(r - (long)b * T);
+  if (t >= lens[b]) {
+    out[i] = 0.f;
+    return;
+  }
+  if (c >= Ce + Cc) {
+    out[i] = semb[(long)b * S + (c - Ce - Cc)];
+    return;
+  }
+  const bool tok = c < Ce;
+  const long v = tok ? idx[r] : cond[r];
+  if (v < 0 || v >= (tok ? V : Vc)) {
+    if (c == 0 || c == Ce) atomicExch(err, 1);
+    out[i] = 0.f;
+    return;
+  }
+  out[i] = tok ? emb[v * Ce + c] : cemb[v * Cc + (c - Ce)];
+}
+
+// out[b,t] = torch.argmax(logits[b,t,:K]) at t < lens[b] (first index on ties; a NaN counts as the maximum), 0 past it
+__global__ void ft_argmax_lens_kernel(const float* __restrict__ logits, const long* __restrict__ lens,
+                                      long* __restrict__ out, int B, int T, int K) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * T) return;
+  int b = (int)(i / T), t = (int)(i - (long)b * T);
+  if (t >= lens[b]) {
+    out[i] = 0;
+    return;
+  }
+  const float* x = logits + i * K;
+  float best = x[0];
+  int at = 0;
+  for (int k = 1; k < K; ++k) {
+    const float v = x[k];
+    if (best == best && (v > best || v != v)) {      // (a NaN, once found, stays)
+      best = v;
+      at = k;
+    }
+  }
+  out[i] = at;
+}
+
 // onehot[row][v] = (idx[row] == v): the embedding weight gradient is then onehot^T * dout, one TN MFMA GEMM
 // (ordered split reduction -> reproducible), shared by every embedding table fed by the same ids
 __global__ void ft_onehot_kernel(const long* __restrict__ idx, float* __restrict__ out, long rows, int V) {
@@ -647,6 +702,29 @@ int ft_check_tokens_lens(const long* idx, const long* lens, int B, int T, int* f
   hipLaunchKernelGGL(ft_check_tokens_lens_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, idx, lens,
                      B, T, flag);
   return ft_check_launch("check_tokens_lens");
+}
+
+int ft_predictor_front_lens(const long* idx, const long* cond, const long* lens, const float* emb, int Ce, int V,
+                            const float* cond_emb, int Cc, int Vc, const float* semb, int S, float* out, int B, int T,
+                            int* err_flag, void* stream) {
+  FT_REQUIRE(B >= 0 && T >= 0 && Ce > 0 && V > 0 && Cc >= 0 && S >= 0 && idx != nullptr && lens != nullptr && emb != nullptr,
+             "predictor_front_lens: bad dims / null pointer");
+  FT_REQUIRE(Cc == 0 || (cond != nullptr && cond_emb != nullptr && Vc > 0), "predictor_front_lens: Cc > 0 needs cond and cond_emb");
+  FT_REQUIRE(S == 0 || semb != nullptr, "predictor_front_lens: S > 0 needs semb");
+  const long total = (long)B * T * (Ce + Cc + S);
+  if (total == 0) return FT_OK;
+  hipLaunchKernelGGL(ft_predictor_front_lens_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, idx, cond,
+                     lens, emb, Ce, V, cond_emb, Cc, Vc, semb, S, out, B, T, err_flag);
+  return ft_check_launch("predictor_front_lens");
+}
+
+int ft_argmax_lens(const float* logits, const long* lens, long* out, int B, int T, int K, void* stream) {
+  FT_REQUIRE(B >= 0 && T >= 0 && K >= 1 && lens != nullptr, "argmax_lens: bad dims / null lens");
+  const long total = (long)B * T;
+  if (total == 0) return FT_OK;
+  hipLaunchKernelGGL(ft_argmax_lens_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, logits, lens, out,
+                     B, T, K);
+  return ft_check_launch("argmax_lens");
 }
 
 int ft_onehot(const long* idx, float* out, long rows, int V, void* stream) {

@@ -33,6 +33,11 @@ MULTISPEAKER_MODEL = dict(    # configs/multispeaker.yaml:100-138 of the referen
     pitch_cond_conv_dims=256, pitch_cond_rnn_dims=128, pitch_cond_dropout=0.5,
     speaker_emb_dims=256, pitch_cond_emb_dims=4, pitch_cond_categorical_dims=3)
 
+MULTI_FASTPITCH_MODEL = dict(  # configs/multispeaker.yaml:165-210 of the reference (+ num_chars / n_mels)
+    FASTPITCH_MODEL, speaker_emb_dims=256,
+    pitch_cond_d_model=128, pitch_cond_n_heads=2, pitch_cond_layers=4, pitch_cond_d_fft=128, pitch_cond_dropout=0.5,
+    pitch_cond_output_dims=3)
+
 
 def fastpitch_train_flops(n_tok: int, n_frm: int, Tx: int, Tm: int) -> float:
     """valid tokens/frames, attention terms on the padded lengths, train = 3 x forward."""

@@ -77,18 +77,28 @@ def _attn_unfused(qkv, key_pad, nh, scale, p_drop, seed):
     return att, P, Pd
 
 
+# ft_attn_fwd_lens at the multispeaker models' head widths (192 = the unconditioned predictors' 384 on 2 heads, 256 = the
+# trunk's 512 on 2 heads): whether it is the default route of a ragged batch, per matmul mode -- the outcome of the A/B in
+# profiles/multi_generate_batch.txt (tools/bench_multi_generate_batch.py).  FT_ATTN_LENS=1 / 0 forces it on / off.
+WIDE_LENS_DEFAULT = {'fp32': True, 'bf16': True}
+
+
 def attn_route(hd: int, ragged: bool = False) -> str:
     """Which attention serves head width hd under the current matmul mode (the switches are read per call):
-    'lens'    ragged batches only: ft_attn_fwd_lens reads the lengths on the device, head widths 64 / 128 in both modes;
-              FT_ATTN_LENS=0 forces the masked routes below (A/B aid)
+    'lens'    ragged batches only: ft_attn_fwd_lens reads the lengths on the device, head widths 64 / 128 in both modes
+              and 192 / 256 (its wide-head layout) where WIDE_LENS_DEFAULT says so; FT_ATTN_LENS=0 forces the masked
+              routes below (A/B aid), FT_ATTN_LENS=1 forces the kernel at every width it has
     'fused'   bf16 mode, head widths 64 / 128: ONE flash-style kernel between the two projections -- no [B,h,T,T] tensor
               in memory, the backward recomputes the probabilities (csrc/ft_attn.hip); FT_ATTN_FUSED=0 turns it off
-    'unfused' everything else: _attn_unfused"""
-    if hd in (64, 128):
-        if ragged and os.environ.get('FT_ATTN_LENS', '1') == '1':
+    'unfused' everything else: _attn_unfused
+    Head width 196 (the multispeaker models' CONDITIONED predictors, 392 on 2 heads) has no fused kernel: it only occurs
+    on the token side (Tx <= ~128 keys), and stays on the masked 'unfused' route of mha_fwd_lens."""
+    if ragged and hd in (64, 128, 192, 256):
+        switch = os.environ.get('FT_ATTN_LENS')
+        if switch == '1' or (switch is None and (hd <= 128 or WIDE_LENS_DEFAULT[H.gemm_precision_mode()])):
             return 'lens'
-        if H.gemm_precision_mode() == 'bf16' and os.environ.get('FT_ATTN_FUSED', '1') == '1':
-            return 'fused'
+    if hd in (64, 128) and H.gemm_precision_mode() == 'bf16' and os.environ.get('FT_ATTN_FUSED', '1') == '1':
+        return 'fused'
     return 'unfused'
 
 
@@ -113,8 +123,8 @@ def mha_fwd(x, key_pad, in_w, in_b, out_w, out_b, nheads, p_drop, seed):
 def mha_fwd_lens(x, lens, in_w, in_b, out_w, out_b, nheads):
     """Inference self-attention of a ragged batch (torch.no_grad only, no tape): x [B,T,d], lens int64 [B] on the device.
     Rows t < lens[b] attend to keys < lens[b] only; the attention output is exactly 0 at t >= lens[b] (the result holds
-    the out-projection's bias there).  Head widths 64 / 128: ft_attn_fwd_lens, which reads the lengths on the device and
-    skips what lies past them; every other width: mha_fwd's route for the current precision with a byte mask derived
+    the out-projection's bias there).  Head widths 64 / 128 / 192 / 256 (attn_route): ft_attn_fwd_lens, which reads the
+    lengths on the device and skips what lies past them; every other width: mha_fwd's route for the current precision with a byte mask derived
     from lens, followed by mask_rows."""
     B, T, d = x.shape
     nh = int(nheads)

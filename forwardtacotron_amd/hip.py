@@ -130,7 +130,7 @@ def attn_fwd(qkv: torch.Tensor, key_pad: Optional[torch.Tensor], nheads: int, sc
 def attn_fwd_lens(qkv: torch.Tensor, lens: torch.Tensor, nheads: int, scale: float) -> torch.Tensor:
     """Inference attention of a ragged batch: qkv [B,T,3d], lens int64 [B] (device) -> att [B,T,d] with rows t < lens[b]
     attending to keys < lens[b] and rows t >= lens[b] exactly 0 (qkv is not read there).  The precision is
-    gemm_precision_mode()'s: bf16 = ft_attn_fwd's arithmetic, fp32 = fp32-exact products.  Head width 64 or 128 only
+    gemm_precision_mode()'s: bf16 = ft_attn_fwd's arithmetic, fp32 = fp32-exact products.  Head width 64, 128, 192 or 256
     (include/fwdtaco_hip.h: ft_attn_fwd_lens)."""
     _chk(qkv, 'qkv'); _chk(lens, 'lens', torch.int64)
     B, T, d3 = qkv.shape
@@ -807,6 +807,40 @@ def embedding_fwd_lens(idx: torch.Tensor, lens: torch.Tensor, w: torch.Tensor) -
     V, C = w.shape
     out = torch.empty(B, T, C, device=w.device, dtype=w.dtype)
     _lib.call('ft_embedding_fwd_lens', _p(idx), _p(lens), _p(w), _p(out), B, T, C, V, _p(_err_flag(w.device)), _stream())
+    return out
+
+
+def predictor_front_lens(idx: torch.Tensor, lens: torch.Tensor, w: torch.Tensor, cond: Optional[torch.Tensor] = None,
+                         cond_w: Optional[torch.Tensor] = None, semb: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The front of a speaker-conditioned predictor on a ragged batch: idx [B,T] (and cond [B,T]) int64, lens int64 [B]
+    (device), semb [B,S] one row per item -> [B,T,Ce+Cc+S] = [ w[idx] | cond_w[cond] | semb[b] ] at t < lens[b], zeros at
+    t >= lens[b], where idx / cond are not read.  cond (with cond_w) and semb are optional."""
+    _chk(idx, 'idx', torch.int64); _chk(lens, 'lens', torch.int64); _chk(w, 'w')
+    B, T = idx.shape
+    assert lens.numel() == B
+    V, Ce = w.shape
+    Vc = Cc = S = 0
+    if cond is not None:
+        _chk(cond, 'cond', torch.int64); _chk(cond_w, 'cond_w')
+        assert cond.shape == idx.shape
+        Vc, Cc = cond_w.shape
+    if semb is not None:
+        _chk(semb, 'semb')
+        assert semb.dim() == 2 and semb.shape[0] == B
+        S = semb.shape[1]
+    out = torch.empty(B, T, Ce + Cc + S, device=w.device, dtype=w.dtype)
+    _lib.call('ft_predictor_front_lens', _p(idx), _p(cond), _p(lens), _p(w), Ce, V, _p(cond_w) if cond is not None else None,
+              Cc, Vc, _p(semb), S, _p(out), B, T, _p(_err_flag(w.device)), _stream())
+    return out
+
+
+def argmax_lens(logits: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """logits [B,T,K], lens int64 [B] (device) -> int64 [B,T]: torch.argmax over K at t < lens[b], 0 at t >= lens[b]"""
+    _chk(logits, 'logits'); _chk(lens, 'lens', torch.int64)
+    B, T, K = logits.shape
+    assert lens.numel() == B
+    out = torch.empty(B, T, device=logits.device, dtype=torch.int64)
+    _lib.call('ft_argmax_lens', _p(logits), _p(lens), _p(out), B, T, K, _stream())
     return out
 
 

@@ -9,8 +9,8 @@ import torch.nn as nn
 
 from . import hip as H
 from . import ops
-from .base import AcousticModel, LengthRegulator, PAD_VALUE, predictor_front
-from .fastpitch import ForwardTransformer, precision_scoped, transformer_predict
+from .base import AcousticModel, LengthRegulator, PAD_VALUE, predictor_front, predictor_tail
+from .fastpitch import FastPitch, ForwardTransformer, precision_scoped, transformer_predict
 
 
 class _SpeakerSeriesPredictor(nn.Module):
@@ -28,6 +28,16 @@ class _SpeakerSeriesPredictor(nn.Module):
         self.transformer = ForwardTransformer(heads=n_heads, dropout=dropout, d_model=wide, d_fft=d_fft,
                                               conv1_kernel=conv1_kernel, conv2_kernel=conv2_kernel, layers=layers)
         self.lin = nn.Linear(wide, out_dim)
+
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, semb: torch.Tensor, x_cond: Optional[torch.Tensor] = None,
+                     alpha: float = 1.0) -> torch.Tensor:
+        """eval forward of a ragged batch with one speaker row per item (semb [B,S]): tokens and x_cond at t >= lens[b]
+        are ignored, the result [B,T,out_dim] is zero there.  The front stores zeros in the padding, speaker row
+        included (the k > 1 convolutions would read it); x_cond: the conditional predictors."""
+        cond_w = self.conditional_embedding.weight if x_cond is not None else None
+        y = H.predictor_front_lens(x, lens, self.embedding.weight, x_cond, cond_w, semb)
+        y = self.transformer.forward_lens(y, lens)
+        return H.mask_rows(predictor_tail(y, self.lin, alpha), lens)            # (the Linear's bias)
 
 
 class SeriesPredictor(_SpeakerSeriesPredictor):
@@ -84,6 +94,7 @@ class MultiFastPitch(AcousticModel):
         if missing or extra:
             raise TypeError(f'MultiFastPitch(): missing {missing}, unexpected {extra}')
         self.padding_value = padding_value
+        self.speaker_emb_dims = hp['speaker_emb_dims']
         self.lr = LengthRegulator()
         shared = {k: hp[k] for k in ('num_chars', 'conv1_kernel', 'conv2_kernel', 'speaker_emb_dims')}
 
@@ -177,3 +188,23 @@ class MultiFastPitch(AcousticModel):
             m = H.transpose_pad_fwd(mel_cl, mel_cl.shape[1], 0.0)
             return {'mel': m, 'mel_post': m, 'dur': dur_in, 'pitch_cond': pitch_cond_hat, 'pitch': pitch_hat,
                     'energy': energy_hat}
+
+    # -- generate_batch: what base.AcousticModel's driver needs from this model -----------------------------------
+    checks_tokens = True            # generate() masks the prenet's keys where x == 0, as FastPitch's does
+
+    @precision_scoped
+    def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, speaker_emb: torch.Tensor, alpha=1.0,
+                       pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
+                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
+        """base.AcousticModel.generate_batch with one speaker row per item (speaker_emb float32 [B,S] on the device), the
+        whole call under the model's `matmul_dtype`; the result also holds `pitch_cond` int64 [B,Tx]"""
+        return super().generate_batch(x, x_len, alpha, pitch_function, energy_function, speaker_emb=speaker_emb)
+
+    def _ragged_prenet(self, x, xl, semb):
+        return self.prenet.forward_lens(H.predictor_front_lens(x, xl, self.embedding.weight, semb=semb), xl)
+
+    def _ragged_regulate(self, h, pred, semb):
+        h = self._cond_add(h, pred['pitch'], pred['energy'], False)
+        return self.lr(h, pred['dur'])                                    # zero rows at t >= mel_len[b]; syncs to size Tm
+
+    _ragged_finish = FastPitch._ragged_finish                             # postnet, lin, one tensor for mel and mel_post

@@ -10,8 +10,8 @@ import torch.nn as nn
 
 from . import hip as H
 from . import ops
-from .base import AcousticModel, LengthRegulator, PAD_VALUE, predictor_front
-from .model import BatchNormConv, CBHG, GRU, LSTM, conv_gru_predict, regulate_and_decode
+from .base import AcousticModel, LengthRegulator, PAD_VALUE, predictor_front, predictor_tail
+from .model import BatchNormConv, CBHG, ForwardTacotron, GRU, LSTM, conv_gru_predict, regulate_and_decode
 
 
 class _SpeakerSeriesPredictor(nn.Module):
@@ -32,6 +32,19 @@ class _SpeakerSeriesPredictor(nn.Module):
         self.rnn = GRU(conv_dims, rnn_dims)
         self.lin = nn.Linear(2 * rnn_dims, out_dim)
         self.dropout = dropout
+
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor, semb: torch.Tensor, x_cond: Optional[torch.Tensor] = None,
+                     alpha: float = 1.0) -> torch.Tensor:
+        """eval forward of a ragged batch with one speaker row per item (semb [B,S]): tokens and x_cond at t >= lens[b]
+        are ignored, the result [B,T,out_dim] is zero there.  The front stores zeros in the padding, speaker row
+        included (the k = 5 convolutions would read it); x_cond: the conditional predictors."""
+        B = x.shape[0]
+        cond_w = self.pitch_cond_embedding.weight if x_cond is not None else None
+        y = H.predictor_front_lens(x, lens, self.embedding.weight, x_cond, cond_w, semb)
+        for conv in self.convs:
+            y = conv.forward_lens(y, lens)
+        y = self.rnn.forward_lens(y, lens, time_major_out=True)
+        return H.mask_rows(predictor_tail(y, self.lin, alpha, B), lens)      # (the Linear's bias)
 
 
 class SeriesPredictor(_SpeakerSeriesPredictor):
@@ -80,6 +93,7 @@ class MultiForwardTacotron(AcousticModel):
             raise TypeError(f'MultiForwardTacotron(): missing {missing}, unexpected {extra}')
         self.rnn_dims = hp['rnn_dims']
         self.padding_value = padding_value
+        self.speaker_emb_dims = hp['speaker_emb_dims']
         E, P, Q, S = hp['embed_dims'], hp['prenet_dims'], hp['postnet_dims'], hp['speaker_emb_dims']
         self.embedding = nn.Embedding(hp['num_chars'], E)
         self.lr = LengthRegulator()
@@ -175,3 +189,23 @@ class MultiForwardTacotron(AcousticModel):
             T = mel_cl.shape[1]
             return {'mel': H.transpose_pad_fwd(mel_cl, T, 0.0), 'mel_post': H.transpose_pad_fwd(post_cl, T, 0.0),
                     **pred, 'pitch_cond': pred['pitch_cond'].unsqueeze(1)}
+
+    # -- generate_batch: what base.AcousticModel's driver needs from this model -----------------------------------
+    def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, speaker_emb: torch.Tensor, alpha=1.0,
+                       pitch_function: Callable[[torch.Tensor], torch.Tensor] = lambda p: p,
+                       energy_function: Callable[[torch.Tensor], torch.Tensor] = lambda e: e) -> Dict[str, torch.Tensor]:
+        """base.AcousticModel.generate_batch with one speaker row per item (speaker_emb float32 [B,S] on the device); the
+        result also holds `pitch_cond` int64 [B,Tx]"""
+        return super().generate_batch(x, x_len, alpha, pitch_function, energy_function, speaker_emb=speaker_emb)
+
+    def _ragged_prenet(self, x, xl, semb):
+        return ForwardTacotron._ragged_prenet(self, x, xl)                    # the speaker row joins behind the prenet
+
+    def _ragged_regulate(self, h, pred, semb):
+        B, Tx = pred['dur'].shape
+        # the padding rows get their item's speaker row too, but their durations are 0: they never reach the regulator
+        h = ops.ConcatColsFn.apply(h, None, semb, B, Tx, True)                # [Tx,B,2P] -> [B,Tx,2P+S]
+        h = self._cond_add(h, pred['pitch'], pred['energy'], False)
+        return regulate_and_decode(self, h, pred['dur'], pred['mel_len'])     # packed LSTM; syncs to size Tm
+
+    _ragged_finish = ForwardTacotron._ragged_finish

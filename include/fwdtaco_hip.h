@@ -553,7 +553,9 @@ int ft_attn_bwd(const float* qkv, const float* att, const float* datt, const uns
  * byte mask.  qkv rows at t >= L are never read into arithmetic (they may hold NaN); workgroups whose queries all lie past
  * L store zeros and leave, every other key loop ends at ceil(L / 64) blocks.  bf16 = 1: ft_attn_fwd's arithmetic (valid
  * rows bit-equal to it with the byte mask t >= L at p_drop = 0); bf16 = 0: fp32-exact products (v_mfma_f32_32x32x2_f32).
- * hd = 64 or 128; qkv and att 16-byte aligned. */
+ * hd = 64, 128, 192 or 256; qkv and att 16-byte aligned.  192 / 256 (the multispeaker models' 384- and 512-wide stacks on
+ * 2 heads) run in 32-key blocks with the head width split over a pair of waves (csrc/ft_attn_lens.hip): same contract,
+ * key loops end at ceil(L / 32) blocks, workgroups of 64 queries; no byte-mask twin, hence no bit-equality claim. */
 int ft_attn_fwd_lens(const float* qkv, const int64_t* lens, float* att, int B, int T, int nheads, int hd, float scale,
                      int bf16, void* stream);
 /* y [B,T,D] = LayerNorm(x + res) (res may be NULL) at t < lens[b], exactly 0 at t >= lens[b], where x / res are not read:
@@ -565,6 +567,19 @@ int ft_conv1d_bias_fwd_lens(const float* x, long ldx, const float* wp, const flo
                             const long* lens, int B, int T, int Cin, int Cout, int k, int relu, void* stream);
 /* flag[0] |= 2 if idx [B,T] holds the pad id 0 at some t < lens[b] (ids at t >= lens[b] are not read) */
 int ft_check_tokens_lens(const long* idx, const long* lens, int B, int T, int* flag, void* stream);
+
+/* ---- the multispeaker models on a ragged batch (MultiForwardTacotron / MultiFastPitch.generate_batch) ------------- */
+/* The front of a speaker-conditioned predictor (and of MultiFastPitch's trunk), ft_embedding_fwd (+ a second one) +
+ * ft_concat_cols in one launch: out[b,t,:] = [ emb[idx[b,t],:Ce] | cond_emb[cond[b,t],:Cc] | semb[b,:S] ] at
+ * t < lens[b] and exactly 0 at t >= lens[b], where idx and cond are NOT read (any id there, also one out of range, is
+ * harmless and does not raise *err_flag).  idx, cond [B,T] int64, lens int64 [B] on the device, semb [B,S]: one speaker
+ * row per item.  The cond part and the speaker part are optional (Cc = 0 / S = 0, their pointers may then be NULL). */
+int ft_predictor_front_lens(const long* idx, const long* cond, const long* lens, const float* emb, int Ce, int V,
+                            const float* cond_emb, int Cc, int Vc, const float* semb, int S, float* out, int B, int T,
+                            int* err_flag, void* stream);
+/* out[b,t] (int64) = the index of the first maximum of logits[b,t,:K] at t < lens[b], 0 at t >= lens[b] (logits are not
+ * read there).  torch.argmax's semantics: the first index on ties, a NaN counts as the maximum. */
+int ft_argmax_lens(const float* logits, const long* lens, long* out, int B, int T, int K, void* stream);
 
 /* ---- a whole FFTBlock per call (common_layers.py:148-185), bf16 matmul mode with the fused attention ------------ */
 /* The FastPitch step is ~900 launches for ~13 ms of GPU work: issued one entry point at a time from Python it is bound by
