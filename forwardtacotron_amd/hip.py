@@ -539,6 +539,23 @@ def conv1d_bwd_data_raw(dy_ptr: int, lddy: int, wp: torch.Tensor, dx: torch.Tens
               int(accumulate), 0, _stream())
 
 
+def conv1d_bwd_data_relu(dy: torch.Tensor, w: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """The data gradient of nn.Conv1d(Cin, Cout, k, padding=k//2) through the ReLU in front of it, in ONE launch:
+    dy [B,T,Cout], w [Cout,Cin,k], y [B,T,Cin] = the OUTPUT of the conv + ReLU this convolution read -> dx [B,T,Cin] =
+    (dy * w) where y > 0, exactly 0 elsewhere (include/fwdtaco_hip.h: ft_conv1d_bwd_data_relu).  The weight operand goes in
+    the form conv1d_bwd_data_raw picks for the same w."""
+    _chk(dy, 'dy'); _chk(w, 'w'); _chk(y, 'y')
+    B, T, Cout = dy.shape
+    Cin, k = w.shape[1], w.shape[2]
+    if w.shape[0] != Cout or tuple(y.shape) != (B, T, Cin):
+        raise _lib.FtError(f'conv1d_bwd_data_relu: dy {tuple(dy.shape)}, w {tuple(w.shape)}, y {tuple(y.shape)} do not match')
+    flag = int(NT_GRADS and Cout % 4 == 0)
+    wp = conv_pack_weight_t(w) if flag else conv_pack_weight(w)
+    dx = torch.empty(B, T, Cin, device=dy.device, dtype=dy.dtype)
+    _lib.call('ft_conv1d_bwd_data_relu', _p(dy), Cout, _p(wp), _p(y), _p(dx), Cin, B, T, Cin, Cout, k, flag, _stream())
+    return dx
+
+
 def conv_bank_bwd_data(dy: torch.Tensor, wp_all: torch.Tensor, K: int, C: int, Cin: int, T: int,
                        ws: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
     """dy [B,Tbuf,K*C] (gradient of the bank buffer) -> dx [B,T,Cin], all K members in one chained launch.
