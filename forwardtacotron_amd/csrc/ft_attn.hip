@@ -28,9 +28,10 @@ using namespace ft_attn_tile;
 
 
 // ---------------------------------------------------------------------------------------------------
-// forward
+// forward.  DROP = (p_drop > 0), decided at the launch: tested per element inside the softmax's callable the switch cost
+// 2 to 3 % of the kernel, and hoisted in front of it the hd = 64 instantiation spilled.
 // ---------------------------------------------------------------------------------------------------
-template <int HD>
+template <int HD, bool DROP>
 __global__ __launch_bounds__(256, HD > 64 ? 1 : 2) void ft_attn_fwd_kernel(const float* __restrict__ qkv,
                                                              const unsigned char* __restrict__ key_pad,
                                                              float* __restrict__ att, float* __restrict__ lse2, int T,
@@ -49,8 +50,7 @@ __global__ __launch_bounds__(256, HD > 64 ? 1 : 2) void ft_attn_fwd_kernel(const
   const float* vbase = qbase + 2 * dmodel;
   const unsigned char* kp = key_pad ? key_pad + (long)b * T : nullptr;
   const float c = scale * LOG2E;
-  const bool drop = p_drop > 0.f;
-  const float inv_keep = drop ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const float inv_keep = DROP ? 1.0f / (1.0f - p_drop) : 1.0f;
 
   bf16x8 qf[KS];                               // B operand of X = K Q^T: lane (query l31, hf): d = 16 ks + 8 hf + j
 #pragma unroll
@@ -87,36 +87,16 @@ __global__ __launch_bounds__(256, HD > 64 ? 1 : 2) void ft_attn_fwd_kernel(const
       for (int ks = 0; ks < KS; ++ks)
         x[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(TL::row_frag(Kt, 32 * kt + l31, ks, hf), qf[ks], x[kt], 0, 0, 0);
     }
-    // online softmax over the keys (in-lane + the other lane half)
-    float mloc = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int kk = 32 * kt + crow(e, hf);
-        const float v = ((pm >> kk) & 1ull) ? -INFINITY : x[kt][e] * c;
-        x[kt][e] = v;
-        mloc = fmaxf(mloc, v);
+    // online softmax over the keys (ft_attn_tile.h: the code of the inference kernels); what this kernel adds is the
+    // attention dropout on the probabilities, behind the row sum
+    const float alpha = online_softmax<2>(x, pm, c, hf, m, l, [=](float p, int kk) __attribute__((always_inline)) {
+      if constexpr (DROP) {
+        const long idx = ((long)inst * T + myq) * T + (kb * KB + kk);
+        return ft_dropout_keep(seed, idx, p_drop) ? p * inv_keep : 0.f;
+      } else {
+        return p;
       }
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    const float mnew = fmaxf(m, mloc);
-    const float msafe = mnew == -INFINITY ? 0.f : mnew;
-    const float alpha = exp2f(m - msafe);       // m = -inf: 0
-    m = mnew;
-    float lsum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float p = __builtin_amdgcn_exp2f(x[kt][e] - msafe);      // v_exp_f32 (the ocml form was 7 % of the kernel)
-        lsum += p;
-        if (drop) {
-          const long idx = ((long)inst * T + myq) * T + (kb * KB + 32 * kt + crow(e, hf));
-          p = ft_dropout_keep(seed, idx, p_drop) ? p * inv_keep : 0.f;
-        }
-        x[kt][e] = p;
-      }
-    l = l * alpha + lsum;
+    });
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -134,15 +114,7 @@ __global__ __launch_bounds__(256, HD > 64 ? 1 : 2) void ft_attn_fwd_kernel(const
   }
   l += __shfl_xor(l, 32, 64);
   if (myq < T) {
-    const float inv = 1.0f / l;
-    float* orow = att + ((long)b * T + myq) * dmodel + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 v = make_float4(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-        *reinterpret_cast<float4*>(orow + 32 * dt + 8 * g + 4 * hf) = v;
-      }
+    store_rows<DT>(att + ((long)b * T + myq) * dmodel + h * HD, o, hf, 1.0f / l);
     if (hf == 0) lse2[(long)inst * T + myq] = m + log2f(l);
   }
 }
@@ -252,15 +224,7 @@ __global__ __launch_bounds__(256, HD > 64 ? 1 : 2) void ft_attn_bwd_dq_kernel(co
       }
     }
   }
-  if (qok) {
-    float* orow = dqkv + ((long)b * T + myq) * ld + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<float4*>(orow + 32 * dt + 8 * g + 4 * hf) =
-            make_float4(dq[dt][4 * g], dq[dt][4 * g + 1], dq[dt][4 * g + 2], dq[dt][4 * g + 3]);
-  }
+  if (qok) store_rows<DT>(dqkv + ((long)b * T + myq) * ld + h * HD, dq, hf);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -362,16 +326,8 @@ __global__ __launch_bounds__(256, 1) void ft_attn_bwd_dkv_kernel(const float* __
   }
   if (kok) {
     float* krow = dqkv + ((long)b * T + myk) * ld + dmodel + h * HD;
-    float* vrow = krow + dmodel;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        *reinterpret_cast<float4*>(krow + 32 * dt + 8 * g + 4 * hf) =
-            make_float4(dk[dt][4 * g], dk[dt][4 * g + 1], dk[dt][4 * g + 2], dk[dt][4 * g + 3]);
-        *reinterpret_cast<float4*>(vrow + 32 * dt + 8 * g + 4 * hf) =
-            make_float4(dv[dt][4 * g], dv[dt][4 * g + 1], dv[dt][4 * g + 2], dv[dt][4 * g + 3]);
-      }
+    store_rows<DT>(krow, dk, hf);
+    store_rows<DT>(krow + dmodel, dv, hf);
   }
 }
 
@@ -390,12 +346,10 @@ int ft_attn_fwd(const float* qkv, const unsigned char* key_pad, float* att, floa
   const dim3 grid(ft_cdiv(T, 128), B * nheads);
   FT_REQUIRE(grid.y <= 65535, "attn_fwd: too many (batch, head) instances");
   const int dmodel = nheads * hd;
-  if (hd == 128)
-    hipLaunchKernelGGL(ft_attn_fwd_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, qkv, key_pad, att, lse2, T, nheads,
-                       dmodel, scale, p_drop, seed);
-  else
-    hipLaunchKernelGGL(ft_attn_fwd_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, qkv, key_pad, att, lse2, T, nheads,
-                       dmodel, scale, p_drop, seed);
+  typedef void (*Kernel)(const float*, const unsigned char*, float*, float*, int, int, int, float, float, uint64_t);
+  const Kernel k = hd == 128 ? (p_drop > 0.f ? ft_attn_fwd_kernel<128, true> : ft_attn_fwd_kernel<128, false>)
+                             : (p_drop > 0.f ? ft_attn_fwd_kernel<64, true> : ft_attn_fwd_kernel<64, false>);
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, qkv, key_pad, att, lse2, T, nheads, dmodel, scale, p_drop, seed);
   return ft_check_launch("attn_fwd");
 }
 

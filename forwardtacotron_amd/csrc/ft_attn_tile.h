@@ -1,6 +1,7 @@
-// Tile helpers shared by the fused attention kernels (ft_attn.hip: training forward / backward with a byte mask;
-// ft_attn_lens.hip: the length-aware inference forward): bf16 fragments of fp32 rows, the row-major 64-key LDS tile with
-// its row and transposed fragment reads, the accumulator-to-operand conversion and the key mask of one 64-key block.
+// What the fused attention kernels share (ft_attn.hip: training forward / backward with a byte mask; ft_attn_lens.hip: the
+// length-aware inference forward): bf16 fragments of fp32 rows, the row-major key-block LDS tile with its row and transposed
+// fragment reads, the accumulator-to-operand conversion, the key mask of one block, the online softmax of the two forward
+// kernels and the float4 row store of every epilogue.
 // Everything is a template or __forceinline__, in a named namespace that the two files open with a using-directive.
 #pragma once
 #include "ft_common.h"
@@ -29,8 +30,8 @@ __device__ __forceinline__ bf16x8 load_frag(const float* p, bool ok) {
   return cvt8(a, b);
 }
 
-// row-major [ROWS rows][HD] bf16 tile image, row stride RS bytes (ROWS = 64 keys everywhere but in the wide-head kernels of
-// ft_attn_lens.hip, whose key blocks are 32 rows)
+// row-major [ROWS rows][HD] bf16 tile image, row stride RS bytes (ROWS = 64 keys everywhere but in the SPLIT = 2
+// instantiations of ft_attn_lens.hip, whose key blocks are 32 rows)
 template <int HD, int ROWS = KB>
 struct Tile {
   static constexpr int RS = HD * 2 + 16;
@@ -85,6 +86,64 @@ __device__ __forceinline__ unsigned long long pad_mask64(const unsigned char* kp
   const int k = k0 + lane;
   const bool masked = k >= T || (kp && kp[k] != 0);
   return __ballot(masked);
+}
+
+// One key block of the online softmax on the transposed score tiles x[kt][e] = key 32 kt + crow(e, hf), query l31 (KT = 2: a
+// 64-key block, KT = 1: a 32-key block): scaled to the log2 domain, masked by pm (bit k = key k of the block is masked), m / l
+// updated; x becomes post(p, k) of the probabilities p = exp2(x - m_new), k the key's index within the block -- the
+// identity in the inference kernels, attention dropout in ft_attn_fwd_kernel (l sums the probabilities before it);
+// -> the factor the accumulated output has to be rescaled by.
+template <int KT, class Post>
+__device__ __forceinline__ float online_softmax(f32x16 (&x)[KT], unsigned long long pm, float c, int hf, float& m, float& l,
+                                                Post post) {
+  float mloc = -INFINITY;
+#pragma unroll
+  for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int kk = 32 * kt + crow(e, hf);
+      const float v = ((pm >> kk) & 1ull) ? -INFINITY : x[kt][e] * c;
+      x[kt][e] = v;
+      mloc = fmaxf(mloc, v);
+    }
+  mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+  const float mnew = fmaxf(m, mloc);
+  const float msafe = mnew == -INFINITY ? 0.f : mnew;
+  const float alpha = exp2f(m - msafe);       // m = -inf: 0
+  m = mnew;
+  float lsum = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float p = __builtin_amdgcn_exp2f(x[kt][e] - msafe);      // v_exp_f32 (the ocml form was 7 % of the kernel)
+      lsum += p;
+      x[kt][e] = post(p, 32 * kt + crow(e, hf));
+    }
+  l = l * alpha + lsum;
+  return alpha;
+}
+
+// rows of an output from DT transposed 32x32 accumulator tiles: lane (row l31, half hf) stores f * its columns
+// 32 dt + 8 g + 4 hf .. + 3 (f = 1.0f exactly: the accumulator's own bits)
+template <int DT>
+__device__ __forceinline__ void store_rows(float* orow, const f32x16 (&o)[DT], int hf, float f = 1.0f) {
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 v = make_float4(o[dt][4 * g] * f, o[dt][4 * g + 1] * f, o[dt][4 * g + 2] * f, o[dt][4 * g + 3] * f);
+      *reinterpret_cast<float4*>(orow + 32 * dt + 8 * g + 4 * hf) = v;
+    }
+}
+
+template <int DT>
+__device__ __forceinline__ void store_zero_rows(float* orow, int hf) {
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(orow + 32 * dt + 8 * g + 4 * hf) = z;
 }
 
 }  // namespace ft_attn_tile
