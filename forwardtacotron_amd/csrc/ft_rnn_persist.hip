@@ -276,8 +276,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
   // exchange block each)
   // BC = 32-k blocks of W_hh a wave keeps resident (bf16-split form): 1, 2 or 4, sized by the host to ceil(H/32 / NW)
   constexpr int NT = (G * UB + 15) / 16, BCH = BC, CW = UB / 4;
-  // granule hand-off (XCD-local mode): two blocks of granules in flight (32 registers) whatever BC is; the 4-block form
-  // (LSTM-512 on 4 waves) takes it too since round 3 (FT_RNN_GRAN4=0: flag words)
+  // granule hand-off (XCD-local mode): two blocks of granules in flight (32 registers).  The 4-block form (LSTM-512 on
+  // 4 waves) does not have it: it hands over through flag words, with FT_RNN_GRAN4 set or not
   constexpr bool GRAN = B3 && BC <= 2;
   static_assert(UB % 4 == 0 && CW <= NW, "cell waves");
   static_assert(MB == 16 || MB == 8, "rows per workgroup");
@@ -312,7 +312,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void ft_rnn_fwd_persist_k
   if (tid == 0) {
     s_local = 0;
     s_fail = 0;
-    __hip_atomic_store(myxcc + chunk, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // drained before wave 0's first signal
+    // (a group has NXCC id slots: with more chunks the host never lays the grid out aligned, nobody reads the ids, and a
+    //  store past the last group's slots would land in the exchange buffer behind them)
+    if (chunk < NXCC)
+      __hip_atomic_store(myxcc + chunk, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // drained before wave 0's first signal
   }
 
   // ---- resident W_hh fragments of this wave: tile nt, column l15 -> (gate, unit) = ((nt*16+l15)/8, (nt*16+l15)%8)
@@ -671,7 +674,7 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_persist_kernel(RnnBwdArgs 
   if (threadIdx.x == 0) {
     s_local = 0;
     s_fail = 0;
-    __hip_atomic_store(myxcc + chunk, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (chunk < NXCC) __hip_atomic_store(myxcc + chunk, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 
   // ---- resident W_hh^T fragments: column l15 = unit u0+l15 ; K groups [g0,g1)
@@ -1018,7 +1021,7 @@ __global__ __launch_bounds__(NW * 64) void ft_rnn_bwd_rs_kernel(RnnBwdArgs a, Ge
   if (threadIdx.x == 0) {
     s_local = 0;
     s_fail = 0;
-    __hip_atomic_store(myxcc + chunk, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (chunk < NXCC) __hip_atomic_store(myxcc + chunk, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 
   // ---- resident W_hh rows of this workgroup's units, as B fragments: tile nt = consumer chunk wave*NT + nt, column
@@ -1507,23 +1510,40 @@ Layout layout_spread(const Geom& geo) {
   return l;
 }
 
+// the kernel a launch picked, for the FT_RNN_DEBUG line: kind "fwd" <G, NW, B3, UB, BC, MB>, "bwd" (all-gather)
+// <G, NW, GW, B3, MB>, "bwd_rs" (reduce-scatter) <G, NW, NT, MB> with the unused slots -1; gran: the kernel has the
+// granule form of the XCD-local hand-off (the others hand over through flag words there)
+struct FormTag {
+  const char* kind;
+  int v[6];
+  int gran;
+};
+
 // picks the layout, checks admission, fills geo; -1.0 = not admitted in any layout
 template <typename KernelT>
-double plan_launch(KernelT kernel, int block, Geom& geo, int& grid, hipStream_t stream) {
+double plan_launch(KernelT kernel, int block, Geom& geo, int& grid, hipStream_t stream, const FormTag& form) {
   const Layout cand[2] = {layout_aligned(geo), layout_spread(geo)};
   for (int i = 0; i < 2; ++i) {
     if (cand[i].grid == 0) continue;
     const double d = xcd_demand(kernel, block, cand[i].per);
     const bool ok = d <= 1.0 && admit(d, stream);
+    const int local_ok = cand[i].aligned && env_int("FT_RNN_LOCAL", 1);
+    const int gran = env_int("FT_RNN_GRANULES", 1), fast = env_int("FT_RNN_FAST_CELL", 1);
+    // (the hand-off named here is the one the groups take from step 2 on IF their workgroups landed in one XCD;
+    //  ft_rnn_mode_counts tells how many did)
     if (env_int("FT_RNN_DEBUG", 0))
-      fprintf(stderr, "[ft_rnn] block %d total %d nchunks %d: %s layout, %d workgroups per XCD slot, demand %.3f -> %s\n", block,
-              geo.total, geo.nchunks, cand[i].aligned ? "aligned" : "spread", cand[i].per, d, ok ? "admitted" : "refused");
+      fprintf(stderr,
+              "[ft_rnn] %s<%d,%d,%d,%d,%d,%d> block %d total %d nchunks %d: %s layout, %d workgroups per XCD slot, demand %.3f -> %s; "
+              "hand-off %s, cell %s\n",
+              form.kind, form.v[0], form.v[1], form.v[2], form.v[3], form.v[4], form.v[5], block, geo.total, geo.nchunks,
+              cand[i].aligned ? "aligned" : "spread", cand[i].per, d, ok ? "admitted" : "refused",
+              !local_ok ? "agent" : (form.gran && gran ? "local-granules" : "local-flags"), fast ? "fast" : "exact");
     if (!ok) continue;
     grid = cand[i].grid;
     geo.xcd_off = cand[i].xcd_off;
-    geo.local_ok = cand[i].aligned && env_int("FT_RNN_LOCAL", 1);
-    geo.gran = env_int("FT_RNN_GRANULES", 1);
-    geo.fast = env_int("FT_RNN_FAST_CELL", 1);
+    geo.local_ok = local_ok;
+    geo.gran = gran;
+    geo.fast = fast;
     return d;
   }
   ++g_n_refused;
@@ -1541,8 +1561,11 @@ int launch_fwd_persist(const RnnFwdArgs& a, Geom geo, const PersistWs& p, hipStr
     return FT_OK;
   }
   int grid = 0;
-  const double cus = plan_launch(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>, NW * 64, geo, grid, stream);
+  const double cus = plan_launch(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>, NW * 64, geo, grid, stream,
+                                 FormTag{"fwd", {G, NW, B3, UB, BC, MB}, B3 && BC <= 2});
   if (cus < 0.0) return -1;
+  // (no effect today: a kernel with BC > 2 is compiled without the granule hand-off -- GRAN in the kernel -- and never
+  //  reads geo.gran; kept so that the switch holds if the 4-block form gets granules)
   if (BC > 2 && !env_int("FT_RNN_GRAN4", 1)) geo.gran = 0;
   (void)hipMemsetAsync(p.cnt, 0, p.total_bytes, stream);
   hipLaunchKernelGGL((ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb,
@@ -1570,7 +1593,9 @@ int fwd_persistent(RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) 
   if (!wide && NW == 8 && G == 4 && H % 32 == 0 && ft_cdiv(H / 32, 4) <= 4 && env_int("FT_RNN_FWD_NW4", 1)) NW = 4;
   if (ft_cdiv(ngroups, NW) > GCH) return -1;
   const int bpw = H % 32 == 0 ? ft_cdiv(H / 32, NW) : 99;                 // 32-k blocks per wave in the split form
-  const bool b3 = bpw <= 4 && env_int("FT_RNN_B3", 1);                    // matmul on the bf16 pipe (exact split)
+  // matmul on the bf16 pipe (exact split): the 8-wave kernels keep at most 2 resident k-blocks per wave (BC), the 4-wave
+  // ones 4 -- a width beyond that (8 waves: H = 544 .. 1024) takes the f32 form, whose 8 k-groups per wave cover it
+  const bool b3 = bpw <= (NW == 8 ? 2 : 4) && env_int("FT_RNN_B3", 1);
   // GRU, H = 256 (the trunk's two GRUs; the postnet's runs 841 steps): 8 waves with ONE resident k-block each and 16
   // hidden units per workgroup -- 16 producers per group instead of 32, half the operand bytes per wave.  Same box,
   // us per step at T = 841 (lab/gru256_ab.py): 4 waves x 2 blocks x 8 units 2.03 | 8 x 1 x 8: 2.03-2.07 | 4 x 2 x 16:
@@ -1618,7 +1643,8 @@ int launch_bwd_persist(const RnnBwdArgs& a, Geom geo, const PersistWs& p, hipStr
     return FT_OK;
   }
   int grid = 0;
-  const double cus = plan_launch(ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>, NW * 64, geo, grid, stream);
+  const double cus = plan_launch(ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>, NW * 64, geo, grid, stream,
+                                 FormTag{"bwd", {G, NW, GW, B3, MB, -1}, B3 && GW / 2 <= 4});
   if (cus < 0.0) return -1;
   (void)hipMemsetAsync(p.cnt, 0, p.total_bytes, stream);
   hipLaunchKernelGGL((ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb,
@@ -1635,7 +1661,8 @@ int launch_bwd_rs(const RnnBwdArgs& a, Geom geo, const PersistWs& p, hipStream_t
     return FT_OK;
   }
   int grid = 0;
-  const double cus = plan_launch(ft_rnn_bwd_rs_kernel<G, NW, NT, MB>, NW * 64, geo, grid, stream);
+  const double cus = plan_launch(ft_rnn_bwd_rs_kernel<G, NW, NT, MB>, NW * 64, geo, grid, stream,
+                                 FormTag{"bwd_rs", {G, NW, NT, MB, -1, -1}, 0});
   if (cus < 0.0) return -1;
   // only the sync region (counters, flags, XCC ids) needs zeroing: every exchange block is written before it is read
   (void)hipMemsetAsync(p.cnt, 0, p.sync_bytes, stream);
