@@ -23,8 +23,10 @@ from typing import Dict, Optional
 import torch
 import torch.nn.functional as F
 
+import taco_step_cpu as K
+
 BN_EPS = 1e-5
-MAX_R = 20
+MAX_R = K.MAX_R
 
 
 def _bn(y, P, pre):
@@ -54,20 +56,18 @@ def _gru_seq(x, w_ih, w_hh, b_ih, b_hh, reverse):
     return torch.stack(out, 1)
 
 
-def _gru_cell(gx, h, w_hh, b_hh):
-    Hd = h.shape[1]
-    gh = h @ w_hh.t() + b_hh
-    r = torch.sigmoid(gx[:, :Hd] + gh[:, :Hd])
-    z = torch.sigmoid(gx[:, Hd:2 * Hd] + gh[:, Hd:2 * Hd])
-    n = torch.tanh(gx[:, 2 * Hd:] + r * gh[:, 2 * Hd:])
-    return (1 - z) * n + z * h
+_gru_cell = K.gru_cell
 
 
-def _lstm_cell(x, h, c, P, pre):
-    g = x @ P[pre + 'weight_ih'].t() + P[pre + 'bias_ih'] + h @ P[pre + 'weight_hh'].t() + P[pre + 'bias_hh']
-    i, f, gg, o = g.chunk(4, dim=1)
-    c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-    return torch.sigmoid(o) * torch.tanh(c), c
+def lstm_weights(P, pre):
+    return P[pre + 'weight_ih'], P[pre + 'weight_hh'], P[pre + 'bias_ih'], P[pre + 'bias_hh']
+
+
+def attend_weights(P):
+    """the attention operands of taco_step_cpu.attend_step after (ep, epq), in its order"""
+    return (P['decoder.attn_rnn.weight_ih'], P['decoder.attn_rnn.weight_hh'], P['decoder.attn_rnn.bias_hh'],
+            P['decoder.attn_net.W.weight'], P['decoder.attn_net.W.bias'], P['decoder.attn_net.conv.weight'],
+            P['decoder.attn_net.L.weight'], P['decoder.attn_net.L.bias'], P['decoder.attn_net.v.weight'][0])
 
 
 def cbhg(x, P, pre, K, num_highways):
@@ -120,22 +120,12 @@ def forward(P: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: dic
     eq = enc @ P['encoder_proj_query.weight'].t()
 
     D = P['decoder.attn_rnn.weight_hh'].shape[1]
-    w_ih = P['decoder.attn_rnn.weight_ih']
-    b_ih = P['decoder.attn_rnn.bias_ih']
-    w_hh, b_hh = P['decoder.attn_rnn.weight_hh'], P['decoder.attn_rnn.bias_hh']
-    Wc = P['decoder.attn_net.conv.weight']
-    Lw, Lb = P['decoder.attn_net.L.weight'], P['decoder.attn_net.L.bias']
-    Ww, Wb = P['decoder.attn_net.W.weight'], P['decoder.attn_net.W.bias']
-    v = P['decoder.attn_net.v.weight'][0]
-    Ld = P['decoder.res_rnn1.weight_hh'].shape[1] if with_mel else 0
+    w_ih, b_ih = P['decoder.attn_rnn.weight_ih'], P['decoder.attn_rnn.bias_ih']
+    aw = attend_weights(P)
     n_mels = mel.shape[1]
 
-    h = mel.new_zeros(B, D)
-    ctx = mel.new_zeros(B, D)
-    cum = mel.new_zeros(B, Tx)
-    att = mel.new_zeros(B, Tx)
-    h1 = c1 = h2 = c2 = mel.new_zeros(B, Ld)
-    attns, frames = [], []
+    # teacher forcing: the prenet half of the GRU input projection of every step is known in advance
+    Pg = []
     for i in range(S):
         f = mel[:, :, i * r - 1] if i > 0 else mel.new_zeros(B, n_mels)
         p = torch.relu(f @ P['decoder.prenet.fc1.weight'].t() + P['decoder.prenet.fc1.bias'])
@@ -144,23 +134,20 @@ def forward(P: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: dic
         p = torch.relu(p @ P['decoder.prenet.fc2.weight'].t() + P['decoder.prenet.fc2.bias'])
         if 'dec2' in masks:
             p = p * masks['dec2'][i].to(dev, dt)
-        h = _gru_cell(torch.cat([ctx, p], 1) @ w_ih.t() + b_ih, h, w_hh, b_hh)
-        loc = F.conv1d(torch.stack([cum, att], 1), Wc, padding=Wc.shape[2] // 2).transpose(1, 2)
-        e = torch.tanh((h @ Ww.t() + Wb)[:, None, :] + ep + loc @ Lw.t() + Lb) @ v
-        att = torch.softmax(e, dim=1)
-        cum = cum + att
-        ctx = (att[:, None, :] @ eq)[:, 0]
-        attns.append(att)
-        if with_mel:
-            xm = torch.cat([ctx, h], 1) @ P['decoder.rnn_input.weight'].t() + P['decoder.rnn_input.bias']
-            h1, c1 = _lstm_cell(xm, h1, c1, P, 'decoder.res_rnn1.')
-            xm = xm + h1
-            h2, c2 = _lstm_cell(xm, h2, c2, P, 'decoder.res_rnn2.')
-            xm = xm + h2
-            frames.append((xm @ P['decoder.mel_proj.weight'].t()).view(B, n_mels, MAX_R)[:, :, :r])
-    attn = torch.stack(attns, 1)
+        Pg.append(p @ w_ih[:, D:].t() + b_ih)
+    attn, hist = K.attend(ep, eq, torch.stack(Pg, 0), *aw)
     if not with_mel:
         return None, None, attn
+    l1, l2 = lstm_weights(P, 'decoder.res_rnn1.'), lstm_weights(P, 'decoder.res_rnn2.')
+    h1 = c1 = h2 = c2 = mel.new_zeros(B, l1[1].shape[1])
+    frames = []
+    for i in range(S):
+        xm = hist[i] @ P['decoder.rnn_input.weight'].t() + P['decoder.rnn_input.bias']
+        h1, c1 = K.lstm_cell(xm, h1, c1, *l1)
+        xm = xm + h1
+        h2, c2 = K.lstm_cell(xm, h2, c2, *l2)
+        xm = xm + h2
+        frames.append((xm @ P['decoder.mel_proj.weight'].t()).view(B, n_mels, MAX_R)[:, :, :r])
     mel_out = torch.cat(frames, 2)
     post = cbhg(mel_out, P, 'postnet.', cfg['postnet_k'], cfg['num_highways'])
     linear = (post @ P['post_proj.weight'].t()).transpose(1, 2)
