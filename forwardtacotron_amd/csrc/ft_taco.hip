@@ -18,7 +18,8 @@
 //        on MFMA; per token the partial energy v . tanh(q + enc_proj + L conv) over the quarter's columns (hardware
 //        exp / rcp tanh, |error| <= ~2e-7 per term).
 //   3. ft_taco_context_kernel  grid (8 column chunks, B), 256 threads
-//        energies = sum of the 4 partials; softmax over all Tx columns (no mask, like the reference); chunk 0 writes attn[b, s, :], attention := p and
+//        energies = sum of the 4 partials; softmax over all Tx columns (no mask, like the reference; with
+//        AttendArgs.lens over the item's own tokens, see the ragged-batch section below); chunk 0 writes attn[b, s, :], attention := p and
 //        cumulative += p; every chunk forms 32 columns of context = p @ enc_pq (each recomputes the softmax from the
 //        Tx energies, so no chunk waits for another).
 // Each kernel requests all of its global operands before its first dependent use: a step costs three launches and
@@ -66,7 +67,13 @@ struct AttendArgs {
   float* att;              // [B,Tx]
   int B, Tx, S;
   long ldh;                // row stride (floats) of the h / context state rows
+  const long* lens;        // [B] valid tokens per item (ragged batch), or nullptr: every item has Tx
 };
+
+// valid tokens of item b: the energies, the softmax, the LSA state and the context stop there
+__device__ __forceinline__ int item_len(const AttendArgs& a, int b) {
+  return a.lens ? (int)min(max(a.lens[b], 1L), (long)a.Tx) : a.Tx;
+}
 
 __device__ __forceinline__ void mfma4(const float4& a, const float4& b, f32x4& acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
@@ -172,6 +179,8 @@ __global__ __launch_bounds__(256) void ft_taco_energy_kernel(AttendArgs a) {
   const int t0 = blockIdx.x * TC, b = blockIdx.y, cq = blockIdx.z;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
   const int B = a.B, Tx = a.Tx;
+  const int n = item_len(a, b);
+  if (t0 >= n) return;                            // every token of the chunk is padding: nothing to store
   const int col = CQ * cq + 16 * wave + l15;      // this lane's attention column in the MFMA / energy phases
 
   float qv[NUB / SG];
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(256) void ft_taco_energy_kernel(AttendArgs a) {
   }
   for (int i = tid; i < 2 * WIN; i += 256) {
     const int c = i / WIN, o = i - c * WIN, t = t0 - KP + o;
-    locw[c][o] = (t >= 0 && t < Tx) ? (c == 0 ? a.cum : a.att)[(long)b * Tx + t] : 0.f;
+    locw[c][o] = (t >= 0 && t < n) ? (c == 0 ? a.cum : a.att)[(long)b * Tx + t] : 0.f;
   }
   for (int i = tid; i < NF * 2 * KW; i += 256) cws[i / (2 * KW)][i % (2 * KW)] = a.cw[i];
   // L row of the lane's column (MFMA B operand): k = 16c + 4q .. +3
@@ -197,7 +206,7 @@ __global__ __launch_bounds__(256) void ft_taco_energy_kernel(AttendArgs a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int t = t0 + 16 * tt + 4 * q + e;
-      epv[tt][e] = a.enc_proj[((long)b * Tx + min(t, Tx - 1)) * DA + col];
+      epv[tt][e] = a.enc_proj[((long)b * Tx + min(t, n - 1)) * DA + col];
     }
   {
     float v = 0.f;
@@ -253,7 +262,7 @@ __global__ __launch_bounds__(256) void ft_taco_energy_kernel(AttendArgs a) {
       if (l15 == 0) esum[wave][16 * tt + 4 * q + e] = sum;
     }
   __syncthreads();
-  if (tid < TC && t0 + tid < Tx)
+  if (tid < TC && t0 + tid < n)
     a.E[((long)b * NCQ + cq) * Tx + t0 + tid] = ((esum[0][tid] + esum[1][tid]) + esum[2][tid]) + esum[3][tid];
 }
 
@@ -283,31 +292,31 @@ __global__ __launch_bounds__(256) void ft_taco_context_kernel(AttendArgs a, int 
   __shared__ float red[256];
   __shared__ float sh[4];
   const int ac = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int Tx = a.Tx;
+  const int Tx = a.Tx, n = item_len(a, b);
   const int col = CC * ac + tid % CC, tg = tid / CC;
   const float* pq = a.enc_pq + (long)b * Tx * DA + col;
   float xv[PF];
 #pragma unroll
   for (int j = 0; j < PF; ++j) {
     const int t = tg + TG * j;
-    xv[j] = t < Tx ? pq[(long)t * DA] : 0.f;
+    xv[j] = t < n ? pq[(long)t * DA] : 0.f;
   }
   const float* e = a.E + (long)b * NCQ * Tx;
   float m = -INFINITY;
-  for (int t = tid; t < Tx; t += 256) {
+  for (int t = tid; t < n; t += 256) {
     const float v = (e[t] + e[Tx + t]) + (e[2 * Tx + t] + e[3 * Tx + t]);
     p[t] = v;
     m = fmaxf(m, v);
   }
   m = block_max(m, sh);
   float z = 0.f;
-  for (int t = tid; t < Tx; t += 256) {
+  for (int t = tid; t < n; t += 256) {
     const float x = expf(p[t] - m);
     p[t] = x;
     z += x;
   }
   z = block_sum(z, sh);              // (its barriers also order the p[] writes above before the reads below)
-  for (int t = tid; t < Tx; t += 256) {
+  for (int t = tid; t < n; t += 256) {
     const float x = p[t] / z;
     p[t] = x;
     if (ac == 0) {
@@ -317,22 +326,24 @@ __global__ __launch_bounds__(256) void ft_taco_context_kernel(AttendArgs a, int 
       a.cum[o] += x;
     }
   }
+  if (ac == 0)                        // ragged batch: exact zeros past the item's tokens
+    for (int t = n + tid; t < Tx; t += 256) a.attn[((long)b * a.S + s) * Tx + t] = 0.f;
   __syncthreads();
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int j = 0; j < PF; ++j) {
     const int t = tg + TG * j;
-    if (t < Tx) acc[j & 3] = fmaf(p[t], xv[j], acc[j & 3]);
+    if (t < n) acc[j & 3] = fmaf(p[t], xv[j], acc[j & 3]);
   }
   int t = tg + TG * PF;
-  for (; t + 3 * TG < Tx; t += 4 * TG) {
+  for (; t + 3 * TG < n; t += 4 * TG) {
     float x[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = pq[(long)(t + i * TG) * DA];
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] = fmaf(p[t + i * TG], x[i], acc[i]);
   }
-  for (; t < Tx; t += TG) acc[0] = fmaf(p[t], pq[(long)t * DA], acc[0]);
+  for (; t < n; t += TG) acc[0] = fmaf(p[t], pq[(long)t * DA], acc[0]);
   red[tid] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
   __syncthreads();
   if (tid < CC) {
@@ -412,7 +423,7 @@ int ft_taco_attend(const float* enc_proj, const float* enc_pq, const float* P, c
   a.W = W; a.bW = b_W; a.cw = conv_w; a.L = L; a.bL = b_L; a.v = v; a.attn = attn;
   a.qp = (float*)(w + wl.qp); a.E = (float*)(w + wl.E); a.cum = (float*)(w + wl.cum); a.att = (float*)(w + wl.att);
   a.B = B; a.Tx = Tx; a.S = S;
-  a.ldh = 2 * DA;
+  a.ldh = 2 * DA; a.lens = nullptr;
   float* zero = (float*)(w + wl.zero);
   float* ring = (float*)(w + wl.ring);
   (void)hipMemsetAsync(w + wl.cum, 0, wl.ring - wl.cum, st);
@@ -765,7 +776,7 @@ int ft_taco_gen_steps(const float* enc_proj, const float* enc_pq, const float* f
   a.qp = (float*)(w + wl.at.qp); a.E = (float*)(w + wl.at.E); a.cum = (float*)(w + wl.at.cum);
   a.att = (float*)(w + wl.at.att);
   a.B = 1; a.Tx = Tx; a.S = S;
-  a.ldh = 2 * DA;
+  a.ldh = 2 * DA; a.lens = nullptr;
   GenArgs g;
   g.fc1w = fc1_w; g.fc1b = fc1_b; g.fc2w = fc2_w; g.fc2b = fc2_b; g.wih = w_ih; g.ld_wih = ld_w_ih; g.bih = b_ih;
   g.wi = rnn_in_w; g.bi = rnn_in_b;
@@ -802,6 +813,377 @@ int ft_taco_gen_steps(const float* enc_proj, const float* enc_pq, const float* f
     }
   }
   return ft_check_launch("taco_gen_steps");
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// Autoregressive generate of a RAGGED BATCH (Tacotron.generate_batch): B sentences, item b with lens[b] <= Tx tokens.
+//
+// Masking rule (what makes item b equal the sentence run alone at Tx = lens[b]): energies are formed and the softmax
+// runs over t < lens[b] only; attention and cumulative stay exact zeros at t >= lens[b], so the location conv sees at
+// the item's end the zero padding it sees at a sequence end; the context sums t < lens[b]; no row of enc_proj / enc_pq
+// past an item's length is loaded.  ft_taco_energy_kernel and ft_taco_context_kernel take that from AttendArgs.lens.
+//
+// A step is eight launches, as at B = 1, but a tile of 16 items shares every weight read: each decoder cell is a
+// skinny product [16 items x K] x [K x 16 columns] on v_mfma_f32_16x16x4_f32 with K split over the four waves of the
+// workgroup (the shape of ft_taco_gru_kernel), a fixed-order sum of the four partial tiles through LDS, then the cell
+// epilogue.  Grid = (column blocks, ceil(B / 16) item tiles):
+//   1. ft_taco_bgen_prenet_kernel  (12, tiles): the 16 last frames -> fc1 + ReLU -> fc2 + ReLU in LDS (recomputed by
+//        each of the 12 workgroups, as at B = 1: L2 reads instead of two launches), then 64 of P[s]'s 768 columns.
+//        Here the waves split the COLUMNS (16 per wave and tile), each wave sums its whole K in ascending order.
+//   2-4. ft_taco_gru_kernel, ft_taco_energy_kernel, ft_taco_context_kernel with lens.
+//   5. ft_taco_bgen_rnnin_kernel   (ceil(L/16), tiles): K = 512, 128 per wave.
+//   6, 7. ft_taco_bgen_lstm_kernel (ceil(L/4), tiles): 16 columns = 4 units x gates (i, f, g, o); waves 0, 1 take x
+//        against W_ih, waves 2, 3 take h against W_hh; h and c ping-pong on the parity of s; x + h' is the output.
+//   8. ft_taco_bgen_mel_kernel     (ceil(80 r / 16), tiles): rows n*20 + k, k < r -> frames[b][s*r + k][n]; one "not
+//        below" flag word per item, ORed by the workgroups that hold a value of the item that is not below the
+//        threshold; the last workgroup of the launch (ticket counter; the atomics count and flag, they never carry
+//        values) sets s_out[b] = s + 1 the first time item b's test holds.
+// An item that has stopped keeps being stepped (its later slots are masked by the caller); no kernel sums across
+// items, so this cannot touch another item.  lstm_dims = 512 takes the template path whose loads all precede the
+// first dependent MFMA; any other width takes a loop in 16-wide K chunks (float4 loads when lstm_dims % 4 == 0).
+// Rows of a partly filled tile read the last item and columns past the end read the last row; neither is stored.
+namespace {
+
+struct BGenArgs {
+  GenArgs g;      // P [S,B,768], hist [S,B,512], frames [B,S*r,80], sout [B]; xin, x1, x2 [B,L]; h*, c* [2][B,L];
+  int B;          // flag [B] words, ticket one word
+};
+
+// One wave's share of a [16 x K] x [K x 16] product: arow / brow are the lane's operand rows (item l15, column l15),
+// the wave sums k in [k0, k1) in ascending 16-wide chunks.  KC > 0: k1 - k0 == 16 KC and the rows are 16-byte
+// aligned, every load is issued before the first MFMA.  vec: float4 loads (rows aligned, k1 - k0 a multiple of 4).
+template <int KC>
+__device__ __forceinline__ f32x4 skinny16(const float* arow, const float* brow, int k0, int k1, bool vec) {
+  const int q = (threadIdx.x & 63) >> 4;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (KC > 0) {
+    float4 av[KC], bv[KC];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      av[c] = ld4(arow + k0 + 16 * c + 4 * q);
+      bv[c] = ld4(brow + k0 + 16 * c + 4 * q);
+    }
+    __builtin_amdgcn_sched_barrier(0);      // keep the scheduler from sinking loads between the MFMAs
+#pragma unroll
+    for (int c = 0; c < KC; ++c) mfma4(av[c], bv[c], acc);
+  } else {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int kb = k0; kb < k1; kb += 16) {            // wave-uniform trip count: every lane issues every MFMA
+      const int k = kb + 4 * q;
+      float4 a = z, b = z;
+      if (vec) {
+        if (k < k1) { a = ld4(arow + k); b = ld4(brow + k); }
+      } else {
+        if (k < k1) { a.x = arow[k]; b.x = brow[k]; }
+        if (k + 1 < k1) { a.y = arow[k + 1]; b.y = brow[k + 1]; }
+        if (k + 2 < k1) { a.z = arow[k + 2]; b.z = brow[k + 2]; }
+        if (k + 3 < k1) { a.w = arow[k + 3]; b.w = brow[k + 3]; }
+      }
+      mfma4(a, b, acc);
+    }
+  }
+  return acc;
+}
+
+// the K range of wave `w` of `nw` waves that share K in 16-wide chunks
+__device__ __forceinline__ void k_slice(int K, int w, int nw, int& k0, int& k1) {
+  const int cpw = ((K + 15) / 16 + nw - 1) / nw * 16;
+  k0 = min(K, w * cpw);
+  k1 = min(K, k0 + cpw);
+}
+
+__device__ __forceinline__ void store_tile(float (&red)[4][16][17], const f32x4& acc) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, q = lane >> 4;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) red[wave][4 * q + e][l15] = acc[e];
+}
+
+// ---- 1. decoder prenet + prenet half of the GRU input projection, 16 items ----------------------------------------
+constexpr int BPB = 12;          // prenet workgroups per item tile: 64 columns of P each, 16 per wave
+__global__ __launch_bounds__(256) void ft_taco_bgen_prenet_kernel(BGenArgs ba, int s) {
+  constexpr int LF = GNM + 4, L1 = GF1 + 4, L2 = GF2 + 4;       // LDS row strides: 16-byte aligned rows
+  constexpr int C1 = GNM / 16, C2 = GF1 / 16, C3 = GF2 / 16;    // K chunks
+  static_assert(GNM % 16 == 0 && NG == BPB * 64, "prenet shape");
+  __shared__ __attribute__((aligned(16))) float f[16][LF];
+  __shared__ __attribute__((aligned(16))) float p1[16][L1];
+  __shared__ __attribute__((aligned(16))) float p2[16][L2];
+  const GenArgs& g = ba.g;
+  const int B = ba.B, b0 = blockIdx.y * 16;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
+  if (s == 0 && blockIdx.x == 0 && tid < 16 && b0 + tid < B) g.sout[b0 + tid] = g.S;
+  // every weight of the three products is requested with the frames
+  float4 w1[4][C1], w2[2][C2], w3[C3];
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int c = 0; c < C1; ++c) w1[t][c] = ld4(g.fc1w + (long)(64 * wave + 16 * t + l15) * GNM + 16 * c + 4 * q);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int c = 0; c < C2; ++c) w2[t][c] = ld4(g.fc2w + (long)(32 * wave + 16 * t + l15) * GF1 + 16 * c + 4 * q);
+  const int col3 = 64 * blockIdx.x + 16 * wave + l15;
+#pragma unroll
+  for (int c = 0; c < C3; ++c) w3[c] = ld4(g.wih + (long)col3 * g.ld_wih + DA + 16 * c + 4 * q);
+  float b1[4], b2[2];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) b1[t] = g.fc1b[64 * wave + 16 * t + l15];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) b2[t] = g.fc2b[32 * wave + 16 * t + l15];
+  const float b3 = g.bih[col3];
+  for (int i = tid; i < 16 * GNM; i += 256) {
+    const int it = i / GNM, ch = i - it * GNM, b = b0 + it;
+    f[it][ch] = (s > 0 && b < B) ? g.frames[((long)b * g.S * g.r + (long)s * g.r - 1) * GNM + ch] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < C1; ++c) mfma4(ld4(&f[l15][16 * c + 4 * q]), w1[t][c], acc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p1[4 * q + e][64 * wave + 16 * t + l15] = fmaxf(acc[e] + b1[t], 0.f);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < C2; ++c) mfma4(ld4(&p1[l15][16 * c + 4 * q]), w2[t][c], acc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p2[4 * q + e][32 * wave + 16 * t + l15] = fmaxf(acc[e] + b2[t], 0.f);
+  }
+  __syncthreads();
+  {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < C3; ++c) mfma4(ld4(&p2[l15][16 * c + 4 * q]), w3[c], acc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int b = b0 + 4 * q + e;
+      if (b < B) g.P[((long)s * B + b) * NG + col3] = acc[e] + b3;
+    }
+  }
+}
+
+// ---- 5. rnn_input, 16 items x 16 outputs ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ft_taco_bgen_rnnin_kernel(BGenArgs ba, int s) {
+  __shared__ float red[4][16][17];
+  const GenArgs& g = ba.g;
+  const int B = ba.B, L = g.L, b0 = blockIdx.y * 16, j0 = blockIdx.x * 16;
+  const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
+  const int it = tid >> 4, cb = b0 + it, cj = j0 + l15;
+  const bool act = cb < B && cj < L;
+  const float bias = act ? g.bi[cj] : 0.f;
+  const float* arow = g.hist + ((long)s * B + min(b0 + l15, B - 1)) * 2 * DA;
+  const float* brow = g.wi + (long)min(j0 + l15, L - 1) * 2 * DA;
+  constexpr int KW4 = 2 * DA / 4;                 // K per wave
+  store_tile(red, skinny16<KW4 / 16>(arow, brow, KW4 * wave, KW4 * (wave + 1), true));
+  __syncthreads();
+  if (act) g.xin[(long)cb * L + cj] = ((red[0][it][l15] + red[1][it][l15]) + (red[2][it][l15] + red[3][it][l15])) + bias;
+}
+
+// ---- 6, 7. residual LSTMCell, 16 items x 4 units ------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(256) void ft_taco_bgen_lstm_kernel(BGenArgs ba, int s, int layer) {
+  __shared__ float red[4][16][17];
+  const GenArgs& g = ba.g;
+  const int B = ba.B, L = g.L, b0 = blockIdx.y * 16, u0 = blockIdx.x * 4;
+  const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
+  const float *wih = layer ? g.l2ih : g.l1ih, *whh = layer ? g.l2hh : g.l1hh;
+  const float *bih = layer ? g.l2bih : g.l1bih, *bhh = layer ? g.l2bhh : g.l1bhh;
+  const float* x = layer ? g.x1 : g.xin;
+  float* xo = layer ? g.x2 : g.x1;
+  float* hb = layer ? g.h2 : g.h1;
+  float* cbuf = layer ? g.c2 : g.c1;
+  const long par = (long)(s & 1) * B * L, nxt = (long)((s + 1) & 1) * B * L;
+  // cell operands of thread tid < 64 (item tid / 4, unit u0 + tid % 4), requested with the product's operands
+  const int it = tid >> 2, cb = b0 + it, cu = u0 + (tid & 3);
+  const bool act = tid < 64 && cb < B && cu < L;
+  float bi_[4] = {0.f, 0.f, 0.f, 0.f}, bh_[4] = {0.f, 0.f, 0.f, 0.f}, cprev = 0.f, xj = 0.f;
+  if (act) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { bi_[q] = bih[q * L + cu]; bh_[q] = bhh[q * L + cu]; }
+    cprev = cbuf[par + (long)cb * L + cu];
+    xj = x[(long)cb * L + cu];
+  }
+  const int seg = wave >> 1;                         // 0: x against W_ih, 1: h against W_hh
+  const long bA = min(b0 + l15, B - 1);
+  const float* arow = (seg ? hb + par : x) + bA * L;
+  const float* brow = (seg ? whh : wih) + ((long)(l15 & 3) * L + min(u0 + (l15 >> 2), L - 1)) * L;
+  int k0, k1;
+  if constexpr (KC > 0) { k0 = 16 * KC * (wave & 1); k1 = k0 + 16 * KC; } else { k_slice(L, wave & 1, 2, k0, k1); }
+  store_tile(red, skinny16<KC>(arow, brow, k0, k1, (L & 3) == 0));
+  __syncthreads();
+  if (act) {
+    const int c0 = 4 * (tid & 3);
+    float gt[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      gt[q] = (((red[0][it][c0 + q] + red[1][it][c0 + q]) + bi_[q]) + (red[2][it][c0 + q] + red[3][it][c0 + q])) + bh_[q];
+    const float c = ft_sigmoid(gt[1]) * cprev + ft_sigmoid(gt[0]) * ft_tanh(gt[2]);
+    const float h = ft_sigmoid(gt[3]) * ft_tanh(c);
+    hb[nxt + (long)cb * L + cu] = h;
+    cbuf[nxt + (long)cb * L + cu] = c;
+    xo[(long)cb * L + cu] = xj + h;
+  }
+}
+
+// ---- 8. mel_proj + per-item stop test ---------------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(256) void ft_taco_bgen_mel_kernel(BGenArgs ba, int s) {
+  __shared__ float red[4][16][17];
+  __shared__ int last;
+  const GenArgs& g = ba.g;
+  const int B = ba.B, L = g.L, b0 = blockIdx.y * 16, i0 = blockIdx.x * 16, rows = GNM * g.r;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = tid & 15;
+  const int ib = min(i0 + l15, rows - 1);            // output row of the lane's weight row: frame k, channel n
+  const float* arow = g.x2 + (long)min(b0 + l15, B - 1) * L;
+  const float* brow = g.wmel + (long)((ib % GNM) * GMAXR + ib / GNM) * L;
+  int k0, k1;
+  if constexpr (KC > 0) { k0 = 16 * KC * wave; k1 = k0 + 16 * KC; } else { k_slice(L, wave, 4, k0, k1); }
+  store_tile(red, skinny16<KC>(arow, brow, k0, k1, (L & 3) == 0));
+  __syncthreads();
+  const int it = tid >> 4, cb = b0 + it, i = i0 + l15;
+  int notbelow = 0;
+  if (cb < B && i < rows) {
+    const float v = (red[0][it][l15] + red[1][it][l15]) + (red[2][it][l15] + red[3][it][l15]);
+    const int k = i / GNM, n = i - k * GNM;
+    g.frames[((long)cb * g.S * g.r + (long)s * g.r + k) * GNM + n] = v;
+    notbelow = !(v < g.thr);                         // NaN is never below
+  }
+  // the 16 lanes that share lane >> 4 hold one item
+  const unsigned long long m = __ballot(notbelow);
+  if (l15 == 0 && ((m >> (lane & 48)) & 0xFFFFull)) atomicOr(g.flag + cb, 1u);
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) last = atomicAdd(g.ticket, 1u) == gridDim.x * gridDim.y - 1;
+  __syncthreads();
+  if (last) {                                        // last workgroup of the step: one decision per item
+    __threadfence();
+    for (int b = tid; b < B; b += 256) {
+      const unsigned nb = atomicOr(g.flag + b, 0u);
+      if (!nb && (long)s * g.r > 10 && g.sout[b] > s) g.sout[b] = s + 1;
+      atomicExch(g.flag + b, 0u);
+    }
+    if (tid == 0) atomicExch(g.ticket, 0u);
+  }
+}
+
+struct BGenWs {
+  WsLayout at;
+  size_t xin, x1, x2, h1, c1, h2, c2, flag, total;
+};
+BGenWs bgen_layout(int B, int Tx, int L) {
+  BGenWs w;
+  w.at = ws_layout(B, Tx);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t v = sizeof(float) * (size_t)B * L;
+  size_t o = w.at.total;
+  w.xin = o; o = al(o + v);
+  w.x1 = o;  o = al(o + v);
+  w.x2 = o;  o = al(o + v);
+  w.h1 = o;  o = al(o + 2 * v);
+  w.c1 = o;  o = al(o + 2 * v);
+  w.h2 = o;  o = al(o + 2 * v);
+  w.c2 = o;  o = al(o + 2 * v);
+  w.flag = o; o = al(o + ((size_t)B + 1) * sizeof(unsigned));
+  w.total = o;
+  return w;
+}
+
+constexpr int BGEN_MAXB = 65535;     // the energy and context grids carry the item in gridDim.y
+
+}  // namespace
+
+extern "C" {
+
+size_t ft_taco_gen_batch_workspace(int B, int Tx, int lstm_dims, int r) {
+  if (B < 1 || B > BGEN_MAXB || Tx < 1 || Tx > TXMAX || lstm_dims < 1 || r < 1 || r > GMAXR) return 0;
+  return bgen_layout(B, Tx, lstm_dims).total;
+}
+
+int ft_taco_gen_batch_steps(const float* enc_proj, const float* enc_pq, const float* fc1_w, const float* fc1_b,
+                            const float* fc2_w, const float* fc2_b, const float* w_ih, long ld_w_ih, const float* b_ih,
+                            const float* w_hh, const float* b_hh, const float* W, const float* b_W,
+                            const float* conv_w, const float* L, const float* b_L, const float* v,
+                            const float* rnn_in_w, const float* rnn_in_b, const float* r1_w_ih, const float* r1_w_hh,
+                            const float* r1_b_ih, const float* r1_b_hh, const float* r2_w_ih, const float* r2_w_hh,
+                            const float* r2_b_ih, const float* r2_b_hh, const float* mel_w, float stop_threshold,
+                            float* P, float* hist, float* attn, float* frames, int* s_out, const long* lens, int B,
+                            int Tx, int lstm_dims, int r, int S, int s0, int n, void* ws, size_t ws_bytes,
+                            void* stream) {
+  FT_REQUIRE(B >= 1 && B <= BGEN_MAXB, "taco_gen_batch_steps: B must be in 1..%d (got %d)", BGEN_MAXB, B);
+  FT_REQUIRE(Tx >= 1 && Tx <= TXMAX, "taco_gen_batch_steps: Tx must be in 1..%d (got %d)", TXMAX, Tx);
+  FT_REQUIRE(lstm_dims >= 1, "taco_gen_batch_steps: lstm_dims must be >= 1 (got %d)", lstm_dims);
+  FT_REQUIRE(r >= 1 && r <= GMAXR, "taco_gen_batch_steps: r must be in 1..%d (got %d)", GMAXR, r);
+  FT_REQUIRE(S >= 1 && s0 >= 0 && n >= 0 && (long)s0 + n <= S,
+             "taco_gen_batch_steps: steps [%d, %d) must lie in [0, S = %d)", s0, s0 + n, S);
+  FT_REQUIRE(ld_w_ih >= DA + GF2 && ld_w_ih % 4 == 0,
+             "taco_gen_batch_steps: ld_w_ih must be a multiple of 4, >= 384");
+  FT_REQUIRE(enc_proj && enc_pq && fc1_w && fc1_b && fc2_w && fc2_b && w_ih && b_ih && w_hh && b_hh && W && b_W &&
+             conv_w && L && b_L && v && rnn_in_w && rnn_in_b && r1_w_ih && r1_w_hh && r1_b_ih && r1_b_hh && r2_w_ih &&
+             r2_w_hh && r2_b_ih && r2_b_hh && mel_w && P && hist && attn && frames && s_out && lens,
+             "taco_gen_batch_steps: null operand");
+  const bool v4 = lstm_dims % 4 == 0;
+  FT_REQUIRE(al16(fc1_w) && al16(fc2_w) && al16(w_ih) && al16(w_hh) && al16(W) && al16(L) && al16(rnn_in_w) &&
+             al16(hist) && al16(ws) && (!v4 || (al16(r1_w_ih) && al16(r1_w_hh) && al16(r2_w_ih) && al16(r2_w_hh) &&
+                                                al16(mel_w))),
+             "taco_gen_batch_steps: weights, history and workspace must be 16-byte aligned");
+  const BGenWs wl = bgen_layout(B, Tx, lstm_dims);
+  FT_REQUIRE(ws && ws_bytes >= wl.total, "taco_gen_batch_steps: workspace too small (%zu < %zu bytes)", ws_bytes,
+             wl.total);
+  if (n == 0) return FT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)ws;
+  AttendArgs a;
+  a.enc_proj = enc_proj; a.enc_pq = enc_pq; a.P = P; a.wih = w_ih; a.ld_wih = ld_w_ih; a.whh = w_hh; a.bhh = b_hh;
+  a.W = W; a.bW = b_W; a.cw = conv_w; a.L = L; a.bL = b_L; a.v = v; a.attn = attn;
+  a.qp = (float*)(w + wl.at.qp); a.E = (float*)(w + wl.at.E); a.cum = (float*)(w + wl.at.cum);
+  a.att = (float*)(w + wl.at.att);
+  a.B = B; a.Tx = Tx; a.S = S;
+  a.ldh = 2 * DA; a.lens = lens;
+  BGenArgs ba;
+  GenArgs& g = ba.g;
+  g.fc1w = fc1_w; g.fc1b = fc1_b; g.fc2w = fc2_w; g.fc2b = fc2_b; g.wih = w_ih; g.ld_wih = ld_w_ih; g.bih = b_ih;
+  g.wi = rnn_in_w; g.bi = rnn_in_b;
+  g.l1ih = r1_w_ih; g.l1hh = r1_w_hh; g.l1bih = r1_b_ih; g.l1bhh = r1_b_hh;
+  g.l2ih = r2_w_ih; g.l2hh = r2_w_hh; g.l2bih = r2_b_ih; g.l2bhh = r2_b_hh;
+  g.wmel = mel_w; g.thr = stop_threshold;
+  g.P = P; g.hist = hist; g.frames = frames; g.sout = s_out;
+  g.xin = (float*)(w + wl.xin); g.x1 = (float*)(w + wl.x1); g.x2 = (float*)(w + wl.x2);
+  g.h1 = (float*)(w + wl.h1); g.c1 = (float*)(w + wl.c1); g.h2 = (float*)(w + wl.h2); g.c2 = (float*)(w + wl.c2);
+  g.flag = (unsigned*)(w + wl.flag); g.ticket = g.flag + B;
+  g.L = lstm_dims; g.r = r; g.S = S;
+  ba.B = B;
+  // s0 == 0: LSA state, LSTM states, stop flags and ticket from zero (s_out[b] := S by the first prenet launch)
+  if (s0 == 0) (void)hipMemsetAsync(w + wl.at.cum, 0, wl.total - wl.at.cum, st);
+  const unsigned tiles = ft_cdiv(B, 16);
+  const dim3 g1(NUB, tiles), g2(ft_cdiv(Tx, TC), B, NCQ), g3(NAC, B);
+  const dim3 gp(BPB, tiles), gi(ft_cdiv(lstm_dims, 16), tiles), gl(ft_cdiv(lstm_dims, 4), tiles);
+  const dim3 gm(ft_cdiv(GNM * r, 16), tiles);
+  const bool fast = lstm_dims == 512;
+  const long slab = (long)B * 2 * DA;
+  for (int s = s0; s < s0 + n; ++s) {
+    const float* prev = hist + (long)(s > 0 ? s - 1 : 0) * slab;
+    float* cur = hist + (long)s * slab;
+    hipLaunchKernelGGL(ft_taco_bgen_prenet_kernel, gp, dim3(256), 0, st, ba, s);
+    hipLaunchKernelGGL(ft_taco_gru_kernel, g1, dim3(256), 0, st, a, s, prev + DA, prev, cur + DA);
+    hipLaunchKernelGGL(ft_taco_energy_kernel, g2, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(ft_taco_context_kernel, g3, dim3(256), 0, st, a, s, cur);
+    hipLaunchKernelGGL(ft_taco_bgen_rnnin_kernel, gi, dim3(256), 0, st, ba, s);
+    if (fast) {
+      hipLaunchKernelGGL(ft_taco_bgen_lstm_kernel<16>, gl, dim3(256), 0, st, ba, s, 0);
+      hipLaunchKernelGGL(ft_taco_bgen_lstm_kernel<16>, gl, dim3(256), 0, st, ba, s, 1);
+      hipLaunchKernelGGL(ft_taco_bgen_mel_kernel<8>, gm, dim3(256), 0, st, ba, s);
+    } else {
+      hipLaunchKernelGGL(ft_taco_bgen_lstm_kernel<0>, gl, dim3(256), 0, st, ba, s, 0);
+      hipLaunchKernelGGL(ft_taco_bgen_lstm_kernel<0>, gl, dim3(256), 0, st, ba, s, 1);
+      hipLaunchKernelGGL(ft_taco_bgen_mel_kernel<0>, gm, dim3(256), 0, st, ba, s);
+    }
+  }
+  return ft_check_launch("taco_gen_batch_steps");
 }
 
 }  // extern "C"

@@ -6,6 +6,8 @@ seed-identical initialisation; the teacher-forced forward() and align() run on t
     Tacotron.forward(batch), teacher forcing        Tacotron.forward(batch): inference only (no grad, no training mode)
     -- (train_tacotron.py:117-136 runs forward)     Tacotron.align(batch): encoder + attention recurrence only
     Tacotron.generate(x, speaker_emb, steps)        Tacotron.generate: B = 1, eval mode, numpy outputs as the reference
+    -- (generate takes one sentence)                Tacotron.generate_batch(x, x_len, speaker_emb, steps): a ragged batch,
+                                                    every item what generate gives the sentence alone; device tensors
 
 Under teacher forcing the attention recurrence (attn_rnn GRUCell + LSA + context) is closed over
 {h_attn, context, cumulative, attention}; nothing from the decoder LSTMs feeds back into it.  So:
@@ -23,6 +25,13 @@ mel_proj run inside the recurrence: ft_taco_gen_steps enqueues eight launches pe
 input projection, ft_taco_attend's three kernels, rnn_input, res_rnn1, res_rnn2, mel_proj with the stop test) for
 GEN_CHUNK steps per call; the host reads the stop step S_out back once per chunk, then runs the postnet on the
 S_out * r frames.
+
+generate_batch() runs the same loop for B sentences of x_len[b] tokens (ft_taco_gen_batch_steps, eight launches per
+step): the attention kernels mask at t >= x_len[b] (energies, softmax, LSA state and context stop there, attn is exactly
+0 past it), the prenet, rnn_input, both LSTMCells and mel_proj run as 16-item products on the f32 MFMA so that a tile of
+16 items reads each weight once per step, and the stop rule is applied per item (s_out [B]); stopped items are stepped
+on until the slowest stops and masked afterwards.  The encoder (Encoder.forward_lens) and the postnet (_post with
+mel_len) run with lengths.  DESIGN.md section 7 has the masking rule and the tile design.
 
 Dropout: the encoder PreNet and the decoder PreNet apply dropout 0.5 when their own `training` flag is set (extraction
 mode, train_tacotron.py:118-119, is `model.eval(); model.decoder.prenet.train()`); every other module must be in eval
@@ -44,11 +53,12 @@ import torch.nn as nn
 from . import _lib
 from . import hip as H
 from .hip import _p, _stream
+from .base import PAD_VALUE
 from .model import CBHG
 
 NUM_CHARS_DEFAULT = 135      # len(utils.text.symbols.phonemes)
 MAX_TX = 1024                # ft_taco_attend's token bound (the duration kernel's)
-GEN_CHUNK = 32               # decoder steps per ft_taco_gen_steps call in generate (outputs do not depend on it)
+GEN_CHUNK = 32               # decoder steps per ft_taco_gen_steps / ft_taco_gen_batch_steps call (outputs do not depend on it)
 
 FtError = _lib.FtError
 
@@ -73,6 +83,15 @@ class Encoder(nn.Module):
         y = H.embedding_fwd(x.contiguous(), self.embedding.weight)
         y = self.pre_net(y)
         return self.cbhg(y)
+
+    def forward_lens(self, x: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """eval forward of a ragged batch: x [B,Tx] int64 (ids at t >= lens[b] are not read), lens int64 [B] on the
+        device -> [B,Tx,2*cbhg_channels], every valid row what the item gets alone, zero at t >= lens[b]"""
+        if self.training:
+            raise FtError('Encoder.forward_lens is the eval-mode (inference) path')
+        y = H.embedding_fwd_lens(x.contiguous(), lens, self.embedding.weight)
+        y = H.mask_rows(self.pre_net(y), lens)              # the biases make the padded rows non-zero: mask for the CBHG
+        return self.cbhg.forward_lens(y, lens)
 
 
 class PreNet(nn.Module):
@@ -271,6 +290,126 @@ class Tacotron(nn.Module):
         mel_out, lin = self._post(mel_cl)
         return mel_out[0].cpu().numpy(), lin[0].cpu().numpy(), attn[0, :n_out].cpu().numpy()
 
+    # -- generate_batch: the teacher's generate for a ragged batch -----------------------------------------------------
+    def generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, speaker_emb: torch.Tensor = None,
+                       steps=2000) -> Dict[str, torch.Tensor]:
+        """generate() of a RAGGED batch of sentences: for every item b the valid part of the result is what
+        generate(x[b:b+1, :x_len[b]], speaker_emb[b:b+1], steps) gives that sentence alone (the
+        masking rule), the reference's stop rule applied per item.
+
+        x: int64 [B,Tx]; entries at t >= x_len[b] are ignored, whatever valid symbol ids they hold.  x_len: int64 [B], on
+        the host or the device, 1 <= x_len[b] <= Tx <= MAX_TX; a host x_len is range-checked before anything is launched,
+        a device x_len out of range raises FtError through a device flag at the end of the call.  speaker_emb: float32
+        [B, speaker_emb_dim], one row per item, required when speaker_emb_dim > 0.  steps and self.r hold for the whole
+        batch: S = ceil(steps / r) caps every item.
+
+        -> dict of device tensors: mel, linear [B,80,Tm] with Tm = max(mel_len) and base.PAD_VALUE at t >= mel_len[b];
+        attn [B,Sm,Tx] with Sm = max(steps_out), exact zeros at t >= x_len[b] and at s >= steps_out[b]; mel_len int64 [B]
+        = steps_out * r; steps_out int64 [B].  An item that has stopped is stepped on until the slowest item stops (its
+        later slots are masked).  Runs under torch.no_grad(); eval() on entry and train() on return, like generate."""
+        w = self.encoder.embedding.weight
+        if not w.is_cuda:
+            raise FtError('Tacotron.generate_batch runs on an MI355X (HIP) device only: move the model with .cuda()')
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1:
+            raise FtError(f'Tacotron.generate_batch: x must be [B, Tx] with B >= 1, got '
+                          f'{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}')
+        B, Tx = x.shape
+        if not 1 <= Tx <= MAX_TX:
+            raise FtError(f'Tacotron.generate_batch: Tx must be in 1..{MAX_TX} (got {Tx})')
+        if not torch.is_tensor(x_len) or x_len.dim() != 1 or x_len.numel() != B or x_len.dtype != torch.int64:
+            raise FtError(f'Tacotron.generate_batch: x_len must be int64 [B = {B}], got '
+                          f'{(tuple(x_len.shape), x_len.dtype) if torch.is_tensor(x_len) else type(x_len).__name__}')
+        on_host = not x_len.is_cuda
+        if on_host and (int(x_len.min()) < 1 or int(x_len.max()) > Tx):
+            raise FtError(f'Tacotron.generate_batch: every x_len must be in [1, Tx = {Tx}] (got {x_len.tolist()})')
+        steps = int(steps)
+        if steps < 1:
+            raise FtError(f'Tacotron.generate_batch: steps must be >= 1 (got {steps})')
+        if self.speaker_emb_dim > 0:
+            if speaker_emb is None:
+                raise FtError(f'Tacotron.generate_batch: speaker_emb_dim = {self.speaker_emb_dim} needs speaker_emb '
+                              f'[B, {self.speaker_emb_dim}], one row per item (a random speaker per batch has no meaning)')
+            if not torch.is_tensor(speaker_emb) or tuple(speaker_emb.shape) != (B, self.speaker_emb_dim):
+                raise FtError(f'Tacotron.generate_batch: speaker_emb must be [{B}, {self.speaker_emb_dim}], got '
+                              f'{tuple(speaker_emb.shape) if torch.is_tensor(speaker_emb) else type(speaker_emb).__name__}')
+        r = self.r
+        if not 1 <= r <= Decoder.max_r:
+            raise FtError(f'Tacotron.generate_batch: r must be in 1..{Decoder.max_r} (got {r})')
+        self.eval()
+        try:
+            with torch.no_grad():
+                return self._generate_batch(x.to(w.device, torch.int64).contiguous(), x_len, speaker_emb, steps, r)
+        finally:
+            self.train()
+
+    def _generate_batch(self, x: torch.Tensor, x_len: torch.Tensor, semb, steps: int, r: int):
+        dev = x.device
+        B, Tx = x.shape
+        S = math.ceil(steps / r)
+        D, Ld, n_mels = self.decoder_dims, self.lstm_dims, self.n_mels
+        dec = self.decoder
+        xl = x_len.to(dev).contiguous()
+        bad_host = None
+        if x_len.is_cuda:
+            # the kernels get lengths inside [1, Tx] whatever the tensor holds; the flag is read behind the decoder loop
+            bad_host = torch.zeros(1, dtype=torch.bool, pin_memory=True)
+            bad_host.copy_(((xl < 1) | (xl > Tx)).any().reshape(1), non_blocking=True)
+            xl = xl.clamp(1, Tx)
+        enc = self.encoder.forward_lens(x, xl)                                  # [B,Tx,256], zero at t >= x_len[b]
+        if self.speaker_emb_dim > 0:
+            semb = semb.to(device=dev, dtype=torch.float32).contiguous()
+            enc = H.concat_cols(enc, None, semb, B, Tx)                         # one speaker row per item
+        ep = H.linear_fwd(enc, self.encoder_proj.weight)
+        epq = H.linear_fwd(enc, self.encoder_proj_query.weight)
+        f32 = dict(device=dev, dtype=torch.float32)
+        P = torch.empty(S, B, 3 * D, **f32)
+        hist = torch.empty(S, B, 2 * D, **f32)
+        attn = torch.empty(B, S, Tx, **f32)
+        frames = torch.empty(B, S * r, n_mels, **f32)
+        s_out = torch.empty(B, device=dev, dtype=torch.int32)
+        nbytes = _lib.query('ft_taco_gen_batch_workspace', B, Tx, Ld, r)
+        if nbytes == 0:
+            raise FtError(f'Tacotron.generate_batch: no workspace for B = {B}, Tx = {Tx}, lstm_dims = {Ld}, r = {r}')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        gru, lsa, pn = dec.attn_rnn, dec.attn_net, dec.prenet
+        l1, l2 = dec.res_rnn1, dec.res_rnn2
+        ops = (_p(ep), _p(epq), _p(pn.fc1.weight), _p(pn.fc1.bias), _p(pn.fc2.weight), _p(pn.fc2.bias),
+               _p(gru.weight_ih), gru.weight_ih.shape[1], _p(gru.bias_ih), _p(gru.weight_hh), _p(gru.bias_hh),
+               _p(lsa.W.weight), _p(lsa.W.bias), _p(lsa.conv.weight), _p(lsa.L.weight), _p(lsa.L.bias),
+               _p(lsa.v.weight), _p(dec.rnn_input.weight), _p(dec.rnn_input.bias),
+               _p(l1.weight_ih), _p(l1.weight_hh), _p(l1.bias_ih), _p(l1.bias_hh),
+               _p(l2.weight_ih), _p(l2.weight_hh), _p(l2.bias_ih), _p(l2.bias_hh), _p(dec.mel_proj.weight),
+               float(self.stop_threshold), _p(P), _p(hist), _p(attn), _p(frames), _p(s_out), _p(xl), B, Tx, Ld, r, S)
+        # as _generate: chunk c is enqueued before chunk c-1's s_out [B] is waited for; the loop ends once every item
+        # has stopped within the steps already completed
+        host = torch.empty(2, B, dtype=torch.int32, pin_memory=True)
+        events = [torch.cuda.Event(), torch.cuda.Event()]
+        s0, c, last = 0, 0, None
+        while s0 < S:
+            n = min(GEN_CHUNK, S - s0)
+            _lib.call('ft_taco_gen_batch_steps', *ops, s0, n, _p(ws), ws.numel(), _stream())
+            host[c % 2].copy_(s_out, non_blocking=True)
+            events[c % 2].record()
+            s0 += n
+            if c > 0:
+                events[(c - 1) % 2].synchronize()
+                last = host[(c - 1) % 2]
+                if int(last.max()) < S:
+                    break
+            c += 1
+        else:
+            events[(c - 1) % 2].synchronize()
+            last = host[(c - 1) % 2]
+        self._gen_batch_steps_run = s0                                          # for tools/bench_taco_generate_batch.py
+        if bad_host is not None and bool(bad_host[0]):
+            raise FtError(f'Tacotron.generate_batch: every x_len must be in [1, Tx = {Tx}]')
+        Sm = int(last.max())
+        steps_out = last.clone().to(dev, torch.int64)
+        mel_len = steps_out * r
+        mel_out, lin = self._post(frames[:, :Sm * r].contiguous(), mel_len)
+        return {'mel': mel_out, 'linear': lin, 'attn': H.mask_rows(attn[:, :Sm].contiguous(), steps_out),
+                'mel_len': mel_len, 'steps_out': steps_out}
+
     # ------------------------------------------------------------------------------------------------------------------
     def _check(self, batch) -> Tuple[torch.Tensor, torch.Tensor, Any]:
         dropout_ok = {id(m) for pn in (self.encoder.pre_net, self.decoder.prenet) for m in pn.modules()}
@@ -403,9 +542,16 @@ class Tacotron(nn.Module):
         mel_cl = H.bt_transpose(y, False).reshape(B, S * r, n_mels)             # [B,S*r,80], frame i*r + k
         return self._post(mel_cl)
 
-    def _post(self, mel_cl: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """frames [B,T,80] (channels last) -> (mel_outputs, linear) [B,80,T]: the postnet CBHG and post_proj"""
+    def _post(self, mel_cl: torch.Tensor, mel_len: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """frames [B,T,80] (channels last) -> (mel_outputs, linear) [B,80,T]: the postnet CBHG and post_proj.
+        mel_len (int64 [B], device; generate_batch): item b has mel_len[b] frames, the rest is masked in front of the
+        postnet's convolutions and comes back as base.PAD_VALUE (as ForwardTacotron._ragged_finish)"""
         B, T = mel_cl.shape[:2]
-        post = self.postnet(mel_cl, time_major_out=True)                        # [T,B,2*postnet_dims]
-        lin = H.linear_fwd(post, self.post_proj.weight, x_tm_B=B, y_tm_B=0)     # [B,T,80]
-        return H.transpose_pad_fwd(mel_cl, T, 0.0), H.transpose_pad_fwd(lin, T, 0.0)
+        if mel_len is None:
+            post = self.postnet(mel_cl, time_major_out=True)                    # [T,B,2*postnet_dims]
+            lin = H.linear_fwd(post, self.post_proj.weight, x_tm_B=B, y_tm_B=0)     # [B,T,80]
+            return H.transpose_pad_fwd(mel_cl, T, 0.0), H.transpose_pad_fwd(lin, T, 0.0)
+        mel_cl = H.mask_rows(mel_cl, mel_len)
+        post = self.postnet.forward_lens(mel_cl, mel_len, time_major_out=True)
+        lin = H.linear_fwd(post, self.post_proj.weight, x_tm_B=B, y_tm_B=0)
+        return H.transpose_pad_lens_fwd(mel_cl, mel_len, T, PAD_VALUE), H.transpose_pad_lens_fwd(lin, mel_len, T, PAD_VALUE)

@@ -796,6 +796,31 @@ int ft_taco_gen_steps(const float* enc_proj, const float* enc_pq, const float* f
                       int* s_out, int Tx, int lstm_dims, int r, int S, int s0, int n, void* ws, size_t ws_bytes,
                       void* stream);
 
+/* ---- Tacotron generate of a ragged batch (Tacotron.generate_batch) --------------------------------------------- */
+/* ft_taco_gen_steps for B sentences at once, item b with lens[b] tokens (int64 [B], device, 1 <= lens[b] <= Tx; a
+ * value outside is clamped into that range, the caller reports it).  Item b gets what ft_taco_gen_steps gives the
+ * sentence alone at Tx = lens[b]: energies, softmax, LSA state and context stop at lens[b], no row of enc_proj / enc_pq
+ * at t >= lens[b] is read, and attn is exactly 0 there.  Eight launches per step (csrc/ft_taco.hip); the decoder cells
+ * run as [16 items x K] x [K x 16 columns] products on the f32 MFMA, so a tile of 16 items reads each weight once per
+ * step.  The weights are those of ft_taco_gen_steps.  Layouts: enc_proj / enc_pq [B,Tx,256]; P [S,B,768]; hist
+ * [S,B,512] = [context | h_attn]; attn [B,S,Tx]; frames [B,S*r,80] (channels last, frame s*r + k); s_out int32 [B].
+ * s0 == 0 starts from zero states and sets s_out[b] = S; a later call continues from the workspace.  Stop rule, per
+ * item: the first step s whose 80 r values of item b are all < stop_threshold (NaN never is) with s*r > 10 sets
+ * s_out[b] = s + 1.  Every item is stepped for all n steps, stopped or not; slots at s >= s_out[b] are written and mean
+ * nothing.  No sum crosses items.  Alignment, bounds on Tx, r, s0, n as ft_taco_gen_steps; 1 <= B <= 65535; ws:
+ * ft_taco_gen_batch_workspace(B, Tx, lstm_dims, r) bytes (0: bad dims).  Fixed summation order, no atomics on values. */
+size_t ft_taco_gen_batch_workspace(int B, int Tx, int lstm_dims, int r);
+int ft_taco_gen_batch_steps(const float* enc_proj, const float* enc_pq, const float* fc1_w, const float* fc1_b,
+                            const float* fc2_w, const float* fc2_b, const float* w_ih, long ld_w_ih, const float* b_ih,
+                            const float* w_hh, const float* b_hh, const float* W, const float* b_W,
+                            const float* conv_w, const float* L, const float* b_L, const float* v,
+                            const float* rnn_in_w, const float* rnn_in_b, const float* r1_w_ih, const float* r1_w_hh,
+                            const float* r1_b_ih, const float* r1_b_hh, const float* r2_w_ih, const float* r2_w_hh,
+                            const float* r2_b_ih, const float* r2_b_hh, const float* mel_w, float stop_threshold,
+                            float* P, float* hist, float* attn, float* frames, int* s_out, const long* lens, int B,
+                            int Tx, int lstm_dims, int r, int S, int s0, int n, void* ws, size_t ws_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
