@@ -673,7 +673,9 @@ int ft_conv1d_bias_fwd(const float* x, long ldx, const float* wp, const float* b
   return ft_launch_gemm_rows(&b, 1, false, (hipStream_t)stream);
 }
 
-// the same on a ragged batch: the epilogue stores zeros at t >= lens[b] (FtGemmBatch.out_lens); x must be zero there
+// the same on a ragged batch: the epilogue stores zeros at t >= lens[b] (FtGemmBatch.out_lens).  x must be zero at
+// lens[b] <= t < lens[b] + k/2, the rows a valid row's taps reach; rows at t >= lens[b] + k/2 are never read into a valid
+// row (they may hold NaN: the mask is an assignment), and a length above T counts as T
 int ft_conv1d_bias_fwd_lens(const float* x, long ldx, const float* wp, const float* bias, float* y, long ldy,
                             const long* lens, int B, int T, int Cin, int Cout, int k, int relu, void* stream) {
   FT_REQUIRE(k >= 1 && (k % 2) == 1 && lens != nullptr, "conv1d_bias_fwd_lens: odd kernel sizes only / null lens");

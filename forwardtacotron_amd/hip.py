@@ -432,7 +432,9 @@ def conv1d_fwd_lens(x: torch.Tensor, wp: torch.Tensor, relu: bool, lens: torch.T
 
 def conv1d_bias_fwd_lens(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, relu: bool, lens: torch.Tensor) -> torch.Tensor:
     """nn.Conv1d with bias (+ ReLU) on a ragged batch: x [B,T,Cin] (zero at t >= lens[b]), wp [k,Cout,Cin], k odd ->
-    y [B,T,Cout], exactly 0 at t >= lens[b]"""
+    y [B,T,Cout], exactly +0.0 at t >= lens[b] (stored, not multiplied: neither the bias nor a NaN survives there).  The
+    rows lens[b] <= t < lens[b] + k//2 of x are read into valid rows and must be zero; rows at t >= lens[b] + k//2 are
+    never read into a valid row and may hold anything.  A length above T counts as T."""
     _chk(x, 'x'); _chk(wp, 'wp'); _chk(bias, 'bias'); _chk(lens, 'lens', torch.int64)
     B, T, Cin = x.shape
     k, Cout, _ = wp.shape
