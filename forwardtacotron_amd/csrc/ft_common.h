@@ -55,6 +55,16 @@ __device__ __forceinline__ double ft_wave_sum_d(double v) {
 // the backward re-derives the same mask from the seed, so no mask tensor is stored.  32-bit mixing (three multiplies:
 // the attention kernels draw one decision per score element, forward and twice in the backward -- the 64-bit finalizer
 // used until round 3 was 19 % of the fused attention forward); index and seed enter in full.
+// THE SEED CONTRACT.  The low seed word is XORed onto the index in front of the first multiply and the high word is added
+// behind it, so the mixer is weaker in the seed than in the index (figures: tests/test_dropout_cpu.py):
+//   * seeds of different sites must differ in the HIGH word, and not only in its top ten bits (bits 54..63 of the seed
+//     meet the last round only: two seeds that differ in one of them give masks correlated up to 0.3);
+//   * two seeds with EQUAL high words give one mask permuted by an XOR of the index,
+//     mask(s_b, i) == mask(s_a, i ^ lo(s_a) ^ lo(s_b)) -- seeds 1, 2, 3, ... are shuffles of one mask;
+//   * base._seed() (a stream with stride 0x9E3779B97F4A7C15 below 2^62) and tacotron.dropout_seed() (62 random bits)
+//     satisfy this; a caller that passes seeds of its own must spread them over both words.
+// tests/dropout_cpu.py restates the two functions below bit for bit in numpy; tests/test_gpu_dropout.py holds every kernel
+// that calls them to it.
 __device__ __forceinline__ uint32_t ft_hash32(uint64_t seed, uint64_t i) {
   uint32_t h = (uint32_t)i ^ ((uint32_t)(i >> 32) * 0x9E3779B1u);
   h = (h ^ (uint32_t)seed) * 0x85EBCA6Bu;

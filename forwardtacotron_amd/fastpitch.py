@@ -515,7 +515,10 @@ def blocks_bwd_composite(state, dy, params):
     if sink is None:
         dx._ft_keep = (scratch, state['arenas'], state['keep'])       # no sink: everything ran on this stream, in order
     if sink is not None:
-        sink.keep.append((scratch, state['arenas'], state['keep'], dy))     # read by the weight-gradient stream until joined
+        # read by the weight-gradient stream until joined; state['h'] is block 0's input, the operand of the LAST weight
+        # gradient issued (its in-projection's): the caller drops `state` as soon as this returns, and a freed `h` is the
+        # main stream's to reuse while that GEMM still reads it
+        sink.keep.append((scratch, state['arenas'], state['keep'], dy, state['h'], state['key_pad']))
         if side is not None:
             sink.used.add(side)
         for idx in sunk:

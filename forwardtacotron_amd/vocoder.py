@@ -357,7 +357,10 @@ class GriffinLim:
         on one fixed kernel and every other step is per frame, bin or sample.  (2) A NaN or Inf item, or NaN in the
         padding of mel, changes no other item's bits.  The phases of `seed` are drawn on the device by a counter-based
         generator keyed on (seed, frame, bin) (include/fwdtaco_hip.h: ft_gl_init_ragged); they deliberately differ from
-        the numpy draw of griffinlim(seed=...).  seed=None takes a fresh seed from the operating system.
+        the numpy draw of griffinlim(seed=...).  seed=None takes a fresh seed from the operating system.  Seeds whose
+        draws are meant to be independent must differ in the high 32-bit word, and not only in its top ten bits: two
+        seeds with equal high words -- seed=1 and seed=2 -- give the same phases permuted by an XOR of the index
+        (csrc/ft_common.h: the seed contract of ft_hash32).
 
         Nothing is sized from device values and, with mel_len on the host, nothing synchronises.  A mel_len that lives
         on the device is range-checked on the device (lengths are clamped inside the kernels, so nothing indexes out of

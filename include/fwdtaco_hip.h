@@ -312,7 +312,11 @@ int ft_colsum_batch(int n, const float* const* x, const long* ld, float* const* 
 
 /* ---- F.dropout (forward_tacotron.py:35 ; common_layers.py:106,110) and scalar scale (x/alpha, :39) ----- */
 /* out = keep ? x/(1-p) : 0 with keep(i) = hash(seed,i) >= p; calling it on the gradient with the same seed
- * is the backward (no mask tensor).  torch's RNG stream cannot be matched: parity runs use p = 0. */
+ * is the backward (no mask tensor).  torch's RNG stream cannot be matched: parity runs use p = 0, or rebuild the mask
+ * on the host (tests/dropout_cpu.py).  hash = ft_hash32 (csrc/ft_common.h), keep(i) = (hash >> 8) * 2^-24 >= p.
+ * SEED CONTRACT (every entry below that takes a dropout or draw seed): seeds of different sites must differ in the HIGH
+ * 32-bit word, and not only in its top ten bits; two seeds with equal high words give one mask permuted by an XOR of
+ * the index (seeds 1, 2, 3, ... are shuffles of one mask).  base._seed() and tacotron.dropout_seed() satisfy this. */
 int ft_dropout(const float* x, float* out, long n, float p, uint64_t seed, void* stream);
 int ft_scale(const float* x, float* out, long n, float s, void* stream);
 /* n <= 64 independent device-to-device copies in ONE launch: dst[i][0:len[i]] = src[i][0:len[i]]  (src / dst / len are
@@ -539,7 +543,8 @@ int ft_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
  * staged (bf16 MFMA, fp32 statistics / accumulation / outputs): this IS the bf16 mode, there is no fp32-exact variant (the
  * fp32 mode keeps ft_bgemm_* + ft_softmax_*).  hd = 64 or 128.
  * ft_attn_bwd: dqkv [B,T,3d] (every element written) from datt = d(att); recomputes the probabilities from qkv and lse2
- * (three launches: row sums of datt*att, dQ, dK+dV; no atomics, bitwise reproducible).  workspace: ft_attn_workspace. */
+ * (three launches: row sums of datt*att, dQ, dK+dV; no atomics, bitwise reproducible).  workspace: ft_attn_workspace.
+ * seed: under ft_dropout's seed contract (distinct high words between sites; equal high words = XOR-permuted masks). */
 size_t ft_attn_workspace(int B, int T, int nheads);
 int ft_attn_fwd(const float* qkv, const unsigned char* key_pad, float* att, float* lse2, int B, int T, int nheads, int hd,
                 float scale, float p_drop, uint64_t seed, void* stream);
@@ -591,7 +596,7 @@ int ft_argmax_lens(const float* logits, const long* lens, long* out, int B, int 
 typedef struct FtFFTBlock {
   int B, T, d, nheads, dfft, k1, k2;
   float p_drop, eps1, eps2;
-  uint64_t seed_attn, seed_ln1, seed_ln2;
+  uint64_t seed_attn, seed_ln1, seed_ln2;          /* three sites: ft_dropout's seed contract (distinct HIGH words) */
   const unsigned char* key_pad;                  /* [B,T] or NULL */
   /* parameters: torch layouts, the convolutions as tap-major packs [k][Cout][Cin] */
   const float *in_w, *in_b, *out_w, *out_b, *c1_wp, *c1_b, *c2_wp, *c2_b, *n1_g, *n1_b, *n2_g, *n2_b;
@@ -652,7 +657,9 @@ int ft_overlap_add(const float* frames, const float* inv_wss, float* ypad, int N
  *   or with u == NULL the counter-based draw u(seed, n, m) = (ft_hash32(seed, n*Fp + m) >> 8) * 2^-24 in [0, 1), where
  *   ft_hash32 is the library's 32-bit mixer of (seed, index) (csrc/ft_common.h; three multiply-xorshift rounds, the
  *   dropout generator): keyed on the frame n and bin m, NOT on b.  u_out (optional) [B*Tcap, Fp] receives the u used,
- *   0 at n >= N_b.
+ *   0 at n >= N_b.  seed: under ft_dropout's seed contract -- draws meant to be independent need seeds that differ in
+ *   the high word (not only in its top ten bits); seeds with equal high words, such as 1 and 2, give the SAME phases
+ *   permuted by an XOR of the index n*Fp + m.
  * gl_phase_ragged: gl_phase on rows n < N_b; proj = 0 and tprev = 0 on the others, whatever `rebuilt` holds there.
  * overlap_add_ragged: ypad_b[t] = (sum over the item's own frames n < N_b, ascending, of frames[b*Tcap + n][t - n*hop]) /
  *   wss_{N_b}[t] for t in [n_fft/2, n_fft/2 + hop*(N_b-1)), 0 in the rest of the item's stride and in the n_fft tail

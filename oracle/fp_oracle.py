@@ -7,7 +7,10 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 with torch.nn.MultiheadAttention written out (torch/nn/functional.py multi_head_attention_forward, the
 need_weights=True branch the reference takes: q scaled by 1/sqrt(hd), additive -inf key padding mask, softmax,
 P @ V, output projection).  Pinned by tests/golden/tiny_fastpitch.npz, produced by importing the reference
-(tests/golden/make_golden.py fastpitch).  All dropout = 0.
+(tests/golden/make_golden.py fastpitch).  All dropout = 0, unless the caller hands mha / fft_block / forward_transformer
+the dropout masks of a stack (`masks`, each tensor already holding keep * 1/(1-p)): F.dropout is a multiplication by
+such a tensor, whatever drew it.  masks = {'pe': [B,T,d] (PositionalEncoding's dropout), 'layers': [{'attn': [B,nh,T,T]
+(on the attention probabilities), 'res1': [B,T,d], 'res2': [B,T,d] (on the two residual branches)}, ...]}.
 """
 from __future__ import annotations
 
@@ -28,8 +31,10 @@ def layernorm(x: Tensor, g: Tensor, b: Tensor, eps: float = 1e-5) -> Tensor:
     return (x - mu) / torch.sqrt(var + eps) * g + b
 
 
-def mha(x: Tensor, key_pad: Optional[Tensor], P: Dict[str, Tensor], prefix: str, nheads: int) -> Tensor:
-    """self-attention on batch-major x [B,T,d]; key_pad bool [B,T] (True = ignore that key)."""
+def mha(x: Tensor, key_pad: Optional[Tensor], P: Dict[str, Tensor], prefix: str, nheads: int,
+        masks: Optional[Tensor] = None) -> Tensor:
+    """self-attention on batch-major x [B,T,d]; key_pad bool [B,T] (True = ignore that key); masks: the attention
+    dropout's [B,nh,T,T] factor on the probabilities"""
     B, T, d = x.shape
     hd = d // nheads
     qkv = linear(x, P[prefix + 'in_proj_weight'], P[prefix + 'in_proj_bias'])
@@ -43,12 +48,22 @@ def mha(x: Tensor, key_pad: Optional[Tensor], P: Dict[str, Tensor], prefix: str,
     if key_pad is not None:
         s = s.masked_fill(key_pad[:, None, None, :], float('-inf'))
     p = torch.softmax(s, dim=-1)
+    if masks is not None:
+        p = p * masks
     a = (p @ v).permute(0, 2, 1, 3).reshape(B, T, d)
     return linear(a, P[prefix + 'out_proj.weight'], P[prefix + 'out_proj.bias'])
 
 
-def fft_block(x: Tensor, key_pad: Optional[Tensor], P: Dict[str, Tensor], prefix: str, nheads: int) -> Tensor:
-    """common_layers.py:170-185"""
+def fft_block(x: Tensor, key_pad: Optional[Tensor], P: Dict[str, Tensor], prefix: str, nheads: int,
+              masks: Optional[Dict[str, Tensor]] = None) -> Tensor:
+    """common_layers.py:170-185; masks: {'attn', 'res1', 'res2'} of this layer"""
+    if masks is not None:
+        a = mha(x, key_pad, P, prefix + 'self_attn.', nheads, masks['attn'])
+        x = layernorm(x + masks['res1'] * a, P[prefix + 'norm1.weight'], P[prefix + 'norm1.bias'])
+        h = conv1d(x.transpose(1, 2), P[prefix + 'conv1.weight'], P[prefix + 'conv1.bias'])
+        h = torch.relu(h)
+        h = conv1d(h, P[prefix + 'conv2.weight'], P[prefix + 'conv2.bias']).transpose(1, 2)
+        return layernorm(x + masks['res2'] * h, P[prefix + 'norm2.weight'], P[prefix + 'norm2.bias'])
     x = layernorm(x + mha(x, key_pad, P, prefix + 'self_attn.', nheads), P[prefix + 'norm1.weight'],
                   P[prefix + 'norm1.bias'])
     h = conv1d(x.transpose(1, 2), P[prefix + 'conv1.weight'], P[prefix + 'conv1.bias'])
@@ -58,12 +73,14 @@ def fft_block(x: Tensor, key_pad: Optional[Tensor], P: Dict[str, Tensor], prefix
 
 
 def forward_transformer(x: Tensor, key_pad: Optional[Tensor], P: Dict[str, Tensor], prefix: str, nheads: int,
-                        layers: int) -> Tensor:
-    """common_layers.py:214-223 (batch-major throughout; pe [max_len,1,d])"""
+                        layers: int, masks: Optional[dict] = None) -> Tensor:
+    """common_layers.py:214-223 (batch-major throughout; pe [max_len,1,d]); masks: see the module docstring"""
     T = x.shape[1]
     x = x + P[prefix + 'pos_encoder.scale'] * P[prefix + 'pos_encoder.pe'][:T, 0, :].unsqueeze(0)
+    if masks is not None:
+        x = x * masks['pe']
     for i in range(layers):
-        x = fft_block(x, key_pad, P, f'{prefix}layers.{i}.', nheads)
+        x = fft_block(x, key_pad, P, f'{prefix}layers.{i}.', nheads, masks['layers'][i] if masks is not None else None)
     return layernorm(x, P[prefix + 'norm.weight'], P[prefix + 'norm.bias'])
 
 

@@ -250,11 +250,15 @@ def length_regulate(x: Tensor, dur: Tensor) -> Tensor:
 # modules
 # --------------------------------------------------------------------------- #
 def series_predictor(x_idx: Tensor, P: Dict[str, Tensor], prefix: str, training: bool,
-                     alpha: float = 1.0, new_buffers=None) -> Tensor:
-    """SeriesPredictor.forward (forward_tacotron.py:28-39), dropout treated as p=0."""
+                     alpha: float = 1.0, new_buffers=None, masks=None) -> Tensor:
+    """SeriesPredictor.forward (forward_tacotron.py:28-39), dropout treated as p=0 -- or, with `masks`, as the
+    multiplication by a given tensor that F.dropout is: three [B,C,T] tensors holding keep * 1/(1-p), one behind each
+    BatchNormConv (:34-36)."""
     x = embedding(x_idx, P[prefix + 'embedding.weight']).transpose(1, 2)
     for i in range(3):
         x = batchnorm_conv(x, P, f'{prefix}convs.{i}.', True, training, new_buffers)
+        if masks is not None:
+            x = x * masks[i]
     x = x.transpose(1, 2)
     x = bigru(x, P, prefix + 'rnn.')
     x = linear(x, P[prefix + 'lin.weight'], P[prefix + 'lin.bias'])
@@ -262,8 +266,9 @@ def series_predictor(x_idx: Tensor, P: Dict[str, Tensor], prefix: str, training:
 
 
 def cbhg(x: Tensor, P: Dict[str, Tensor], prefix: str, K: int, num_highways: int,
-         training: bool, new_buffers=None) -> Tensor:
-    """CBHG.forward (common_layers.py:91-124), dropout treated as p=0.  x [B,C,T] -> [B,T,2*channels]."""
+         training: bool, new_buffers=None, masks=None) -> Tensor:
+    """CBHG.forward (common_layers.py:91-124), dropout treated as p=0.  x [B,C,T] -> [B,T,2*channels].
+    masks: two [B,C,T] tensors holding keep * 1/(1-p): behind the max-pool (:106) and behind conv_project1 (:110)."""
     residual = x
     T = x.shape[-1]
     bank = []
@@ -272,7 +277,11 @@ def cbhg(x: Tensor, P: Dict[str, Tensor], prefix: str, K: int, num_highways: int
         bank.append(c[:, :, :T])
     y = torch.cat(bank, dim=1)
     y = maxpool_k2s1p1(y)
+    if masks is not None:
+        y = y * masks[0]
     y = batchnorm_conv(y, P, prefix + 'conv_project1.', True, training, new_buffers)
+    if masks is not None:
+        y = y * masks[1]
     y = batchnorm_conv(y, P, prefix + 'conv_project2.', False, training, new_buffers)
     y = y + residual
     y = y.transpose(1, 2)
@@ -291,11 +300,13 @@ def pad_to(x: Tensor, max_len: int, pad_value: float = PAD_VALUE) -> Tensor:
     return x
 
 
-def _trunk(x_idx, dur, pitch, energy, mel_lens, P, cfg, training, new_buffers, pad_frames_to=None):
+def _trunk(x_idx, dur, pitch, energy, mel_lens, P, cfg, training, new_buffers, pad_frames_to=None, masks=None):
     """pad_frames_to: zero-pad the LengthRegulator output to this many frames -- what pad_sequence does to an item that
-    sits in a batch beside a longer one (common_layers.py:23); lets one item of a large batch be checked alone."""
+    sits in a batch beside a longer one (common_layers.py:23); lets one item of a large batch be checked alone.
+    masks: {'prenet': ..., 'postnet': ...}, each as cbhg takes them."""
+    masks = masks or {}
     x = embedding(x_idx, P['embedding.weight']).transpose(1, 2)
-    x = cbhg(x, P, 'prenet.', cfg['prenet_k'], cfg['prenet_num_highways'], training, new_buffers)
+    x = cbhg(x, P, 'prenet.', cfg['prenet_k'], cfg['prenet_num_highways'], training, new_buffers, masks.get('prenet'))
     pp = conv1d(pitch, P['pitch_proj.weight'], P['pitch_proj.bias']).transpose(1, 2)
     x = x + pp * cfg['pitch_strength']
     ep = conv1d(energy, P['energy_proj.weight'], P['energy_proj.bias']).transpose(1, 2)
@@ -305,14 +316,17 @@ def _trunk(x_idx, dur, pitch, energy, mel_lens, P, cfg, training, new_buffers, p
         x = torch.cat([x, torch.zeros(x.shape[0], pad_frames_to - x.shape[1], x.shape[2], dtype=x.dtype)], dim=1)
     x = bilstm(x, mel_lens, P, 'lstm.', cfg.get('padding_value', PAD_VALUE))
     x = linear(x, P['lin.weight'], P['lin.bias']).transpose(1, 2)
-    xp = cbhg(x, P, 'postnet.', cfg['postnet_k'], cfg['postnet_num_highways'], training, new_buffers)
+    xp = cbhg(x, P, 'postnet.', cfg['postnet_k'], cfg['postnet_num_highways'], training, new_buffers,
+              masks.get('postnet'))
     xp = linear(xp, P['post_proj.weight']).transpose(1, 2)
     return x, xp
 
 
-def forward(P: Dict[str, Tensor], batch: Dict[str, Tensor], cfg: dict, training: bool
+def forward(P: Dict[str, Tensor], batch: Dict[str, Tensor], cfg: dict, training: bool, masks=None
             ) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
-    """ForwardTacotron.forward (forward_tacotron.py:118-165) with all dropout = 0.
+    """ForwardTacotron.forward (forward_tacotron.py:118-165) with all dropout = 0, or with the given dropout masks:
+    {'dur_pred', 'pitch_pred', 'energy_pred': as series_predictor takes them, 'prenet', 'postnet': as cbhg does}; a
+    missing key is a module without dropout.
 
     Returns (outputs, new_buffers).  new_buffers holds the BN running stats /
     num_batches_tracked / step values after the call (training mode only).
@@ -324,10 +338,13 @@ def forward(P: Dict[str, Tensor], batch: Dict[str, Tensor], cfg: dict, training:
     energy = batch['energy'].unsqueeze(1)
     if training:
         new_buffers['step'] = P['step'] + 1
-    dur_hat = series_predictor(x_idx, P, 'dur_pred.', training, 1.0, new_buffers).squeeze(-1)
-    pitch_hat = series_predictor(x_idx, P, 'pitch_pred.', training, 1.0, new_buffers).transpose(1, 2)
-    energy_hat = series_predictor(x_idx, P, 'energy_pred.', training, 1.0, new_buffers).transpose(1, 2)
-    x, xp = _trunk(x_idx, dur, pitch, energy, mel_lens, P, cfg, training, new_buffers)
+    masks = masks or {}
+    dur_hat = series_predictor(x_idx, P, 'dur_pred.', training, 1.0, new_buffers, masks.get('dur_pred')).squeeze(-1)
+    pitch_hat = series_predictor(x_idx, P, 'pitch_pred.', training, 1.0, new_buffers,
+                                 masks.get('pitch_pred')).transpose(1, 2)
+    energy_hat = series_predictor(x_idx, P, 'energy_pred.', training, 1.0, new_buffers,
+                                  masks.get('energy_pred')).transpose(1, 2)
+    x, xp = _trunk(x_idx, dur, pitch, energy, mel_lens, P, cfg, training, new_buffers, masks=masks)
     pv = cfg.get('padding_value', PAD_VALUE)
     out = {'mel': pad_to(x, mel.shape[2], pv), 'mel_post': pad_to(xp, mel.shape[2], pv),
            'dur': dur_hat, 'pitch': pitch_hat, 'energy': energy_hat}
@@ -414,8 +431,8 @@ def is_param(key: str) -> bool:
 
 
 def train_step(P: Dict[str, Tensor], opt_state: Dict[str, Dict[str, Tensor]], batch: Dict[str, Tensor],
-               cfg: dict, train_cfg: dict, lr: float, step_count: int):
-    """One full optimisation step (forward_trainer.py:73-99) with dropout/zoneout = 0.
+               cfg: dict, train_cfg: dict, lr: float, step_count: int, masks=None):
+    """One full optimisation step (forward_trainer.py:73-99) with dropout/zoneout = 0 (masks: see forward).
 
     Returns (new_P, new_opt_state, info) where info has losses, grads (pre-clip),
     grad_norm and the forward outputs.
@@ -424,7 +441,7 @@ def train_step(P: Dict[str, Tensor], opt_state: Dict[str, Dict[str, Tensor]], ba
     b = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
     pitch_target = b['pitch'].detach().clone()
     energy_target = b['energy'].detach().clone()
-    pred, new_buf = forward(leaf, b, cfg, training=True)
+    pred, new_buf = forward(leaf, b, cfg, training=True, masks=masks)
     L = losses(pred, b, pitch_target, energy_target, train_cfg)
     names = [k for k in leaf if is_param(k)]
     gl = torch.autograd.grad(L['loss'], [leaf[k] for k in names], allow_unused=True)

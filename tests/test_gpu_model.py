@@ -219,11 +219,9 @@ def test_tiny_model_golden_eval_and_train(ft):
     assert np.array_equal(b['dur'].cpu().numpy(), np.maximum(M['batch/dur'], 0))   # in-place clamp side effect
 
 
-@pytest.mark.parametrize('cfg_name', ['tiny', 'odd'])
-def test_model_vs_oracle_train(ft, cfg_name):
-    model, ops, hip = ft
+def _oracle_train_case(model, cfg):
+    """the model (on the CPU), its state dict and the awkward batch of test_model_vs_oracle_train"""
     from oracle import ft_oracle as O
-    cfg = TINY if cfg_name == 'tiny' else ODD
     torch.manual_seed(11)
     m = model.ForwardTacotron(**cfg)
     g = torch.Generator().manual_seed(5)
@@ -244,9 +242,11 @@ def test_model_vs_oracle_train(ft, cfg_name):
         n = int(batch['mel_len'][b])
         mel[b, :, :n] = torch.randn(cfg['n_mels'], n, generator=g) * 2 - 5
     batch['mel'] = mel
-    newP, _, info = O.train_step(P, {}, {k: v.clone() for k, v in batch.items()}, cfg, TRAIN_CFG, 1e-3, 1)
-    m = m.cuda()
-    pred, L, _ = _train_step_hip(model, ops, m, batch, TRAIN_CFG)
+    return m, P, batch
+
+
+def _assert_train_step_matches(m, pred, L, info, newP):
+    """the bars of test_model_vs_oracle_train: predictions 5e-5, loss 2e-5, gradients 1e-4, running statistics 1e-5"""
     for k in ('mel', 'mel_post', 'dur', 'pitch', 'energy'):
         assert maxdiff(pred[k].detach().cpu(), info['pred'][k]) < 5e-5, k
     assert abs(float(L['loss']) - float(info['losses']['loss'])) < 2e-5
@@ -260,6 +260,84 @@ def test_model_vs_oracle_train(ft, cfg_name):
     for k in sd:
         if 'running_' in k:
             assert maxdiff(sd[k].cpu(), newP[k]) < 1e-5, k
+    return worst, worst_k
+
+
+@pytest.mark.parametrize('cfg_name', ['tiny', 'odd'])
+def test_model_vs_oracle_train(ft, cfg_name):
+    model, ops, hip = ft
+    from oracle import ft_oracle as O
+    cfg = TINY if cfg_name == 'tiny' else ODD
+    m, P, batch = _oracle_train_case(model, cfg)
+    newP, _, info = O.train_step(P, {}, {k: v.clone() for k, v in batch.items()}, cfg, TRAIN_CFG, 1e-3, 1)
+    m = m.cuda()
+    pred, L, _ = _train_step_hip(model, ops, m, batch, TRAIN_CFG)
+    _assert_train_step_matches(m, pred, L, info, newP)
+
+
+DROPOUT_ON = dict(durpred_dropout=0.5, pitch_dropout=0.5, energy_dropout=0.5, prenet_dropout=0.5, postnet_dropout=0.1)
+
+
+def _forward_tacotron_masks(cfg, batch, torch_seed):
+    """The dropout masks of one training forward, for oracle.ft_oracle (its [B,C,T] layout), built on the CPU from the
+    restated mixer and seed stream (tests/dropout_cpu.py).  The draw order is read off model.py: forward() runs _predict
+    inside _fork_predictors, i.e. BEFORE the trunk is issued -- dur, pitch, energy, three sites each (conv_gru_predict:
+    one behind every BatchNormConv) -- then _trunk: prenet CBHG (behind the fused bank + max-pool, behind conv_project1),
+    then postnet CBHG likewise.  Every site is an ops.DropoutFn on a contiguous channels-last [B,T,C] tensor."""
+    import dropout_cpu as D
+    B, Tx = batch['x'].shape
+    Tm = int(batch['mel_len'].max())
+    sites = []
+    for name, key in (('dur_pred', 'durpred'), ('pitch_pred', 'pitch'), ('energy_pred', 'energy')):
+        sites += [(name, Tx, cfg[key + '_conv_dims'], cfg[key + '_dropout'])] * 3
+    sites += [('prenet', Tx, cfg['prenet_k'] * cfg['prenet_dims'], cfg['prenet_dropout']),
+              ('prenet', Tx, cfg['prenet_dims'], cfg['prenet_dropout']),
+              ('postnet', Tm, cfg['postnet_k'] * cfg['postnet_dims'], cfg['postnet_dropout']),
+              ('postnet', Tm, cfg['postnet_dims'], cfg['postnet_dropout'])]
+    masks = {}
+    for seed, (name, T, C, p) in zip(D.seed_stream(torch_seed, len(sites)), sites):
+        mk = torch.from_numpy(D.site_mask(seed, (B, T, C), p, np.float32))
+        masks.setdefault(name, []).append(mk.transpose(1, 2))
+    return masks
+
+
+def _replay_seed_stream(seed):
+    """base._seed() re-bases when it meets a torch seed other than the last one it saw: park it on another, install `seed`"""
+    from forwardtacotron_amd import base
+    torch.manual_seed(seed + 1)
+    base._seed()
+    torch.manual_seed(seed)
+
+
+@pytest.mark.parametrize('cfg_name', ['tiny', 'odd'])
+def test_model_vs_oracle_train_with_dropout(ft, cfg_name):
+    """test_model_vs_oracle_train with the production dropout on: 0.5 in the three predictors and the prenet CBHG, 0.1 in
+    the postnet CBHG, at the same bars.  The oracle multiplies by masks that are rebuilt on the CPU and owe nothing to the
+    code under test, so a wrong seed order (pitch and energy swapped), a wrong flat index, a keep scale other than
+    1/(1-p) or a backward that masks differently from its forward all show here."""
+    model, ops, hip = ft
+    from oracle import ft_oracle as O
+    cfg = dict(TINY if cfg_name == 'tiny' else ODD, **DROPOUT_ON)
+    m, P, batch = _oracle_train_case(model, cfg)
+    masks = _forward_tacotron_masks(cfg, batch, 4242)
+    assert [len(masks[k]) for k in ('dur_pred', 'pitch_pred', 'energy_pred', 'prenet', 'postnet')] == [3, 3, 3, 2, 2]
+    newP, _, info = O.train_step(P, {}, {k: v.clone() for k, v in batch.items()}, cfg, TRAIN_CFG, 1e-3, 1, masks=masks)
+    clean, _ = O.forward(P, {k: v.clone() for k, v in batch.items()}, cfg, training=True)
+    m = m.cuda()
+    _replay_seed_stream(4242)
+    pred, L, _ = _train_step_hip(model, ops, m, batch, TRAIN_CFG)
+    for k in ('mel', 'mel_post', 'dur', 'pitch', 'energy'):                  # the masks were really on
+        assert maxdiff(pred[k].detach().cpu(), clean[k].detach()) > 1e-2, k
+        print(f'{cfg_name} p on: {k} {maxdiff(pred[k].detach().cpu(), info["pred"][k]):.2e}')
+    worst = _assert_train_step_matches(m, pred, L, info, newP)
+    print(f'{cfg_name} p on: loss {abs(float(L["loss"]) - float(info["losses"]["loss"])):.2e}, worst gradient {worst}')
+    first = {k: pred[k].detach().clone() for k in ('mel', 'mel_post', 'dur', 'pitch', 'energy')}
+    _replay_seed_stream(4242)                                                 # same torch seed: the same masks, bit for bit
+    m.train()
+    with torch.no_grad():
+        again = m(cuda_batch({k: v.clone() for k, v in batch.items()}))
+    for k, v in first.items():
+        assert torch.equal(again[k], v), k
 
 
 def test_generate_golden(ft):

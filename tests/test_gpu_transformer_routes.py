@@ -12,7 +12,7 @@ ft_conv1d_bwd_data_relu).  This is what bench.py's variants.fastpitch_bf16_train
   composite  the bf16 default (composite_ok(d, heads) is asserted, so that loop is never compared with loop)
 
 Part 1: one ForwardTransformer alone (tests/transformer_cases.py), loss (y * w).sum() over all rows, against
-oracle.fp_oracle.forward_transformer in float64 and route against route.  Part 2: a small FastPitch whose five stacks all
+oracle.fp_oracle.forward_transformer in float64 and route against route, without dropout and with dropout 0.1.  Part 2: a small FastPitch whose five stacks all
 qualify for the composite, under TrainStep (gradient sink + weight-gradient side stream: the branch the benchmark runs) and
 under a plain backward.  Part 3: the pieces only this path uses, alone, in fp32 mode against float64.
 
@@ -40,6 +40,12 @@ of every case, so loop and composite show the layer route's figures and the wors
   hd128_T129_k3k3         6.0e-7             2.8e-3             9.1e-2     1.0e-1 (layers.0.conv1.weight)
   hd64_T7_nomask          6.9e-7             3.3e-3             5.7e-2     3.6e-1 (layers.0.conv1.weight)
   hd128_T841_wide_tiles   1.2e-6             4.0e-3             4.7e-2     6.6e-2 (pos_encoder.scale)
+
+With dropout 0.1 (training mode; the float64 reference gets the masks rebuilt on the CPU by tests/dropout_cpu.py, nothing of
+them comes from the code under test), same columns, loop = layer in fp32 and all three routes bit-identical in bf16:
+
+  hd64_T70_2layers        8.6e-7 (y)         4.8e-3             5.9e-2     1.3e-1 (layers.1.conv1.weight)
+  hd128_T129_k3k3         7.0e-7             2.6e-3             1.1e-1     1.4e-1 (layers.0.conv1.weight)
 
 The bf16 output sits at a few 1e-3, inside tol_mel.  The bf16 GRADIENTS of this loss are 5-10 % of their range away from
 float64 on every route alike, and two kinds of tensor more: pos_encoder.scale is ONE sum over all B * T * d products with
@@ -225,8 +231,9 @@ def test_wide_tile_gemms_ran_inside_the_composite(monkeypatch):
 @pytest.mark.parametrize('name', ['hd64_T70_2layers', 'hd128_T129_k3k3'])
 def test_bf16_routes_with_dropout_are_bit_identical_and_reproducible(monkeypatch, name):
     """(e), (f) dropout 0.1 in training mode: positional-encoding dropout, attention dropout inside the fused kernel and
-    the two residual dropouts fused into the LayerNorms, all from the library's counter-based mask.  No float64 reference;
-    the three routes draw the same seeds in the same order (replayed through base._seed()'s documented re-basing), so rule
+    the two residual dropouts fused into the LayerNorms, all from the library's counter-based mask.  This test compares
+    route with route; the float64 reference with the same masks, rebuilt on the CPU, is in the two dropout tests below.
+    The three routes draw the same seeds in the same order (replayed through base._seed()'s documented re-basing), so rule
     (d) applies: bit-equal.  The masks were really on (the output differs from the dropout-0 output), and a second
     composite run with the same seeds reproduces every gradient bit for bit (no atomics on the path)."""
     res = {r: _run(monkeypatch, name, 'bf16', r, p=0.1) for r in ROUTES}
@@ -237,6 +244,45 @@ def test_bf16_routes_with_dropout_are_bit_identical_and_reproducible(monkeypatch
     _assert_bitwise(res['loop'], res['layer'], 'dropout: loop vs layer')
     again = _run(monkeypatch, name, 'bf16', 'composite', p=0.1, cached=False)
     _assert_bitwise(again, res['composite'], 'composite, second run with the same seeds')
+
+
+DROPOUT_CASES = ['hd64_T70_2layers', 'hd128_T129_k3k3']
+
+
+@pytest.mark.parametrize('name', DROPOUT_CASES)
+def test_fp32_routes_with_dropout_vs_float64(monkeypatch, name):
+    """dropout 0.1, fp32 mode: loop and layer route against the float64 oracle run with THE SAME masks, rebuilt on the CPU
+    (tests/dropout_cpu.py: the restated mixer, the restated seed stream of torch.manual_seed(4242), the documented draw order
+    pe, then per layer attention, norm1, norm2, and each site's index layout) -- nothing of the mask comes from the code
+    under test.  The bars of test_fp32_loop_route_vs_float64: 1e-4 on y, 2e-4 on every gradient.  A wrong seed order, a
+    site indexing another layout, a backward that rebuilds another mask than its forward or a keep scale other than
+    1/(1-p) is an O(0.1) error here."""
+    ref = reference64(name, 0.1)
+    assert err(ref['y'], reference64(name)['y']) > 1e-2                     # the masks are on in the reference
+    res = {r: _run(monkeypatch, name, 'fp32', r, p=0.1) for r in ('loop', 'layer')}
+    for r, out in res.items():
+        worst = max(err(out[k], ref[k]) for k in _tensors(out))
+        print(f'fp32 p 0.1 {name} {r}: y {err(out["y"], ref["y"]):.3e}  worst {worst:.3e}')
+    for r, out in res.items():
+        for k in _tensors(out):
+            assert err(out[k], ref[k]) < (1e-4 if k == 'y' else 2e-4), (r, k, err(out[k], ref[k]))
+
+
+@pytest.mark.parametrize('name', DROPOUT_CASES)
+def test_bf16_routes_with_dropout_vs_float64_and_the_layer_yardstick(monkeypatch, name):
+    """dropout 0.1, bf16 mode, against the float64 oracle with the CPU-built masks: loop and composite within
+    2 * e_layer + 1e-6, e_layer the layer route's own error at p = 0.1, and 1e-5 < e_layer[y] < 8e-2 as at p = 0 -- a
+    mask that differed from the reference's anywhere would put e_layer[y] at O(0.1) or above."""
+    ref = reference64(name, 0.1)
+    res = {r: _run(monkeypatch, name, 'bf16', r, p=0.1) for r in ROUTES}
+    e_layer = {k: err(res['layer'][k], ref[k]) for k in _tensors(ref)}
+    print(f'bf16 p 0.1 {name} e_layer[y] {e_layer["y"]:.3e}  e_layer[dx] {e_layer["dx"]:.3e}  largest gradient e_layer '
+          f'{max(e_layer.values()):.3e} ({max(e_layer, key=e_layer.get)})')
+    assert 1e-5 < e_layer['y'] < 8e-2, e_layer['y']
+    for k in _tensors(ref):
+        for r in ('loop', 'composite'):
+            e = err(res[r][k], ref[k])
+            assert e <= 2 * e_layer[k] + 1e-6, (r, k, e, e_layer[k])
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -350,6 +396,40 @@ def test_trainstep_routes_bit_identical_and_vs_oracle(monkeypatch, small_fp):
         assert not bad, (a, b_, bad)
     bad = [(k, maxdiff(plain[k], res['composite'][k])) for k in plain if not torch.equal(plain[k], res['composite'][k])]
     assert not bad, ('plain backward vs TrainStep', bad)
+
+
+def test_composite_backward_keeps_every_side_stream_operand_alive(monkeypatch, small_fp):
+    """Under TrainStep the composite's weight gradients run on the sink's side stream, and TransformerFn.backward drops
+    the forward's state the moment blocks_bwd_composite returns.  Whatever those launches read must therefore sit in
+    GradSink.keep until the step joins the side stream -- also block 0's input `h`, the operand of the LAST weight gradient
+    issued (the in-projection's of block 0): a freed `h` is the main stream's to reuse while that GEMM still reads it, which
+    showed as one wrong in_proj_weight gradient (5.9e-3 from the oracle instead of 3.5e-5) in
+    test_trainstep_routes_bit_identical_and_vs_oracle, depending on what the allocator had cached from earlier tests.  Host-side and
+    deterministic: the addresses held by the sink right after each composite backward."""
+    from forwardtacotron_amd import fastpitch as F
+    from forwardtacotron_amd import ops
+    P, batch, _ = small_fp
+    real, seen = F.blocks_bwd_composite, []
+
+    def tensors(x):
+        if torch.is_tensor(x):
+            yield x
+        elif isinstance(x, (list, tuple)):
+            for y in x:
+                yield from tensors(y)
+
+    def spy(state, dy, params):
+        out = real(state, dy, params)
+        sink = ops._SINK
+        assert sink is not None and sink.stream is not None
+        held = {t.data_ptr() for t in tensors(sink.keep)}
+        seen.append(state['h'].data_ptr() in held and all(a.data_ptr() in held for a in state['arenas'])
+                    and dy.data_ptr() in held)
+        return out
+
+    monkeypatch.setattr(F, 'blocks_bwd_composite', spy)
+    _train_step(monkeypatch, P, batch, 'composite')
+    assert len(seen) == 5 and all(seen), seen               # dur, pitch, energy, prenet, postnet
 
 
 # ---------------------------------------------------------------------------------------------------

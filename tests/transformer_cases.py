@@ -5,10 +5,17 @@ A case is one ForwardTransformer (common_layers.py:188-223) alone: parameters pe
 reference starts as a deepcopy of ONE block; identical layers would hide a block mix-up), an input x [B,T,d], a ragged key
 padding mask and a fixed weight tensor w for the loss (y * w).sum() over ALL rows -- neither the reference nor this project
 masks the k > 1 convolutions in training, so padded query rows feed valid ones.
+
+With dropout p > 0 the reference gets the masks the GPU run will draw, built on the CPU (tests/dropout_cpu.py) from the
+seeds base._seed() hands out after torch.manual_seed(DROPOUT_TORCH_SEED), in the draw order every route documents
+(fastpitch.TransformerFn): the positional-encoding seed first, then per layer attention, norm1, norm2.
 """
 import functools
 
+import numpy as np
 import torch
+
+DROPOUT_TORCH_SEED = 4242      # the seed test_gpu_transformer_routes.py installs in front of every forward
 
 #        id                 d   heads d_fft k1 k2 layers B  T    lens
 CASES = {
@@ -51,15 +58,36 @@ def inputs(name: str):
     return P, x, pad, w
 
 
-def reference(name: str, dtype=torch.float64):
-    """oracle.fp_oracle.forward_transformer (dtype-agnostic) on `dtype` copies with requires_grad
+def dropout_masks(name: str, p: float, dtype=torch.float64, masked: bool = True):
+    """the masks argument of oracle.fp_oracle.forward_transformer for the case at dropout p (every site of a
+    ForwardTransformer has the same p); masked=False with p = 0 -> None, the unmasked call"""
+    import dropout_cpu as D
+    if p <= 0.0 and not masked:
+        return None
+    c = CASES[name]
+    B, T, d, nh = c['B'], c['T'], c['d'], c['nh']
+    seeds = iter(D.seed_stream(DROPOUT_TORCH_SEED, 1 + 3 * c['layers']))
+    npdt = np.float64 if dtype == torch.float64 else np.float32
+    site = lambda shape: torch.from_numpy(D.site_mask(next(seeds), shape, p, npdt)).to(dtype)
+    masks = {'pe': site((B, T, d)), 'layers': []}
+    for _ in range(c['layers']):
+        # both attention forms index [B,nh,T,T]; the LayerNorms index [rows, D] = [B * T, d], the same flat index as [B,T,d]
+        masks['layers'].append({'attn': site((B, nh, T, T)), 'res1': site((B, T, d)), 'res2': site((B, T, d))})
+    return masks
+
+
+def reference(name: str, dtype=torch.float64, p: float = 0.0, masked=None):
+    """oracle.fp_oracle.forward_transformer (dtype-agnostic) on `dtype` copies with requires_grad, with the dropout
+    masks of the case at p (masked=True forces the masked code path at p = 0 too, with masks of ones)
     -> {'y', 'dx', <parameter name>: gradient}, pos_encoder.scale included"""
     from oracle import fp_oracle as FP
     c = CASES[name]
     P, x, pad, w = inputs(name)
-    Pd = {k: v.to(dtype).requires_grad_(FP.is_param(k)) for k, v in P.items()}
-    xd = x.to(dtype).requires_grad_(True)
-    y = FP.forward_transformer(xd, pad, Pd, '', c['nh'], c['layers'])
+    # copies: .to(float32) of the cached fp32 inputs would hand back the cached tensors themselves
+    Pd = {k: v.detach().to(dtype, copy=True).requires_grad_(FP.is_param(k)) for k, v in P.items()}
+    xd = x.detach().to(dtype, copy=True).requires_grad_(True)
+    masks = dropout_masks(name, p, dtype, masked=p > 0 if masked is None else masked)
+    y = FP.forward_transformer(xd, pad, Pd, '', c['nh'], c['layers'], masks=masks)
     (y * w.to(dtype)).sum().backward()
     out = {'y': y.detach(), 'dx': xd.grad}
     out.update({k: v.grad for k, v in Pd.items() if FP.is_param(k)})
@@ -68,5 +96,5 @@ def reference(name: str, dtype=torch.float64):
 
 
 @functools.lru_cache(maxsize=None)
-def reference64(name: str):
-    return reference(name, torch.float64)
+def reference64(name: str, p: float = 0.0):
+    return reference(name, torch.float64, p)
