@@ -7,6 +7,8 @@ of preprocess.py:78-89 `Preprocessor._convert_file` (trim_silence, peak normalis
     mel = dsp.wav_to_mel(y)                          # [n_mels, 1 + len(y) // hop]; numpy in -> numpy out, device in -> device out
     out = dsp.preprocess_batch([y0, y1, ...])        # ragged batch, one pass, no host synchronisation inside
     items = split_items(out)                         # per-item numpy arrays for np.save (this is the one sync)
+    out = dsp.preprocess_batch(wavs48k, source_sr=48000)     # load_wav's resampling first, then the same five launches
+    rs = dsp.resample_batch(wavs, 48000)             # {'wav' [B, ld], 'wav_len' [B]} at dsp.sample_rate; one launch
     wav = dsp.griffinlim(mel)                        # vocoder.GriffinLim, which shares the bases
     wavs = split_wavs(dsp.griffinlim_batch(mel, mel_len))    # a ragged batch of mels (generate_batch's) -> wavs
 
@@ -23,12 +25,24 @@ librosa's published algorithm: stft(center=True) with ZERO padding of n_fft // 2
 gives the older default), periodic Hann window, magnitude, Slaney area-normalised mel basis; effects.trim(top_db,
 frame_length=2048, hop_length=512) with ref = the maximum frame power.
 
+Resampling (the reference's load_wav is librosa.load(path, sr=sample_rate), which resamples every file on the way in)
+is provided for audio that is already in memory: resample / resample_batch, and the `source_sr` argument of preprocess /
+preprocess_batch.  One launch, ft_resample_poly_ragged (csrc/ft_resample.hip), for a ragged batch: the polyphase design
+of scipy.signal.resample_poly -- a Kaiser(5.0)-windowed sinc of 20 max(up, down) + 1 taps, zero phase, zero padding --
+which is librosa's res_type='polyphase'.  The filter (resample_filter), the ratio and the output length are host
+functions of this module, importable without a device; the float64 restatement the tests compare against is
+tests/resample_cpu.py, itself held to scipy.  PARITY UNPINNED here too: librosa.load defaults to res_type='soxr_hq', and
+neither librosa nor soxr is installed here; what is pinned is the published Kaiser polyphase design, to scipy.
+
 Not provided: trim_long_silences (webrtcvad; the reference's own code for it fails on current numpy) raises FtError at
-construction; load_wav / save_wav (wav I/O is out of scope).  normalize / denormalize are the two element-wise
-conveniences of the reference's interface; the hot path has them fused into ft_mel_project / ft_exp_transpose.
+construction; the file I/O of load_wav / save_wav (reading and writing wav files is out of scope).  normalize /
+denormalize are the two element-wise conveniences of the reference's interface; the hot path has them fused into
+ft_mel_project / ft_exp_transpose.
 """
 import ctypes
-from typing import Any, Dict, List, Sequence, Union
+import math
+import operator
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -51,6 +65,67 @@ def _empty(*shape, dtype=torch.float32, device=None) -> torch.Tensor:
 
 def _alloc(*shape, **kw) -> torch.Tensor:
     return _empty(*shape, **kw)               # looked up at call time, so a replaced _empty takes effect
+
+
+# ----------------------------------------------------------------------------------------------------
+# sample-rate conversion: host side (no device needed)
+# ----------------------------------------------------------------------------------------------------
+RESAMPLE_MAX_RATE = 1024          # max(up, down) after the gcd: every pair of standard rates is far below; table < 100 KB
+
+
+def _rate(sr, what: str) -> int:
+    if isinstance(sr, (bool, float)) or not hasattr(sr, '__index__'):
+        raise _lib.FtError(f'resample: {what} must be a positive integer, got {sr!r}')
+    sr = operator.index(sr)
+    if sr <= 0:
+        raise _lib.FtError(f'resample: {what} must be a positive integer, got {sr!r}')
+    return sr
+
+
+def resample_ratio(source_sr: int, target_sr: int) -> Tuple[int, int]:
+    """(up, down) = (target_sr, source_sr) / gcd; FtError for rates that are no positive integers or a ratio with
+    max(up, down) > 1024"""
+    source_sr, target_sr = _rate(source_sr, 'source_sr'), _rate(target_sr, 'target_sr')
+    g = math.gcd(source_sr, target_sr)
+    up, down = target_sr // g, source_sr // g
+    if max(up, down) > RESAMPLE_MAX_RATE:
+        raise _lib.FtError(f'resample: {source_sr} -> {target_sr} Hz reduces to {up}/{down}; max(up, down) must be <= '
+                           f'{RESAMPLE_MAX_RATE}')
+    return up, down
+
+
+def resample_len(n: int, source_sr: int, target_sr: int) -> int:
+    """the number of samples n samples at source_sr become: ceil(n * up / down)"""
+    up, down = resample_ratio(source_sr, target_sr)
+    n = operator.index(n)
+    if n < 0:
+        raise _lib.FtError(f'resample: a negative length ({n})')
+    return -((-n * up) // down)
+
+
+def resample_filter(source_sr: int, target_sr: int) -> Tuple[np.ndarray, int]:
+    """(h float64 [2 half + 1], half): scipy.signal.resample_poly's default filter -- firwin(2 half + 1, 1 / R, window=
+    ('kaiser', 5.0)) * up with R = max(up, down), half = 10 R -- whose centre tap h[half] sits on output n's position
+    n * down / up"""
+    up, down = resample_ratio(source_sr, target_sr)
+    R = max(up, down)
+    half = 10 * R
+    i = np.arange(2 * half + 1, dtype=np.float64)
+    h = (1.0 / R) * np.sinc((i - half) / R) * np.kaiser(2 * half + 1, 5.0)
+    h /= h.sum()
+    h *= up
+    return h, half
+
+
+def resample_table(h: np.ndarray, half: int, up: int) -> np.ndarray:
+    """h -> the kernel's phase-major table, fp32 [up, Tp]: tab[p, t] = h[p + t * up], zero past the last tap; T =
+    ceil((2 half + 1) / up) taps per phase, row stride Tp = T | 1 (include/fwdtaco_hip.h: ft_resample_poly_ragged)"""
+    T = (2 * half + up) // up
+    Tp = T | 1
+    idx = np.arange(up)[:, None] + np.arange(T)[None, :] * up
+    tab = np.zeros((up, Tp), dtype=np.float32)
+    tab[:, :T] = np.where(idx <= 2 * half, np.asarray(h, dtype=np.float64)[np.minimum(idx, 2 * half)], 0.0)
+    return tab
 
 
 class DSP:
@@ -86,13 +161,19 @@ class DSP:
         self._w_ptr = H._ptr_array([self.gl.w_fwd])
         self._col0 = (ctypes.c_int * 1)(0)
         self._outf = (ctypes.c_int * 1)(2 * self.Fp)
+        self._rs_tabs: Dict[Tuple[int, int], Any] = {}          # resampling coefficient tables per (up, down)
+        self._rs_bad: Optional[torch.Tensor] = None             # the pinned word a device-side length check reports through
 
     @classmethod
     def from_config(cls, config: Dict[str, Any], **kw) -> 'DSP':
         return cls(**config['dsp'], **kw)
 
     # ------------------------------------------------------------------------------------------------
-    def _gather(self, wavs: Sequence[Wav]):
+    def _check_reflect(self, min_len: int) -> None:
+        if self.pad_mode == 'reflect' and min_len <= self.n_fft // 2:
+            raise _lib.FtError(f"DSP: pad_mode='reflect' needs more than n_fft // 2 = {self.n_fft // 2} samples per wav")
+
+    def _gather(self, wavs: Sequence[Wav], for_stft: bool = True):
         """list of 1-D wavs -> (wav [B, ld] zero-padded device tensor, lens [B] int64 device tensor, Lmax)"""
         if len(wavs) == 0:
             raise _lib.FtError('DSP: an empty batch')
@@ -104,8 +185,8 @@ class DSP:
         Lmax = max(lens)
         if Lmax == 0:
             raise _lib.FtError('DSP: every wav of the batch is empty')
-        if self.pad_mode == 'reflect' and min(lens) <= self.n_fft // 2:
-            raise _lib.FtError(f"DSP: pad_mode='reflect' needs more than n_fft // 2 = {self.n_fft // 2} samples per wav")
+        if for_stft:
+            self._check_reflect(min(lens))
         ld = (Lmax + 3) // 4 * 4
         if all(isinstance(y, np.ndarray) for y in wavs):
             host = np.zeros((len(wavs), ld), dtype=np.float32)
@@ -138,18 +219,124 @@ class DSP:
                 'peak': tp['peak'], 'wav': wav_out[:, :Lmax], 'wav_len': tp['wav_len']}
 
     # ------------------------------------------------------------------------------------------------
-    def preprocess_batch(self, wavs: Sequence[Wav]) -> Dict[str, torch.Tensor]:
+    # ---- sample-rate conversion ----------------------------------------------------------------------
+    def _rs_table(self, up: int, down: int):
+        """-> (the phase-major coefficient table on the device, half), built once per (up, down)"""
+        ent = self._rs_tabs.get((up, down))
+        if ent is None:
+            h, half = resample_filter(down, up)                      # (up, down) is in lowest terms already
+            host = torch.zeros(_lib.query('ft_resample_table_floats', up, down, half), dtype=torch.float32).pin_memory()
+            flat = torch.from_numpy(resample_table(h, half, up).reshape(-1))
+            host[:flat.numel()] = flat
+            tab = _alloc(host.numel(), device=self.device)
+            tab.copy_(host, non_blocking=True)
+            ent = self._rs_tabs[(up, down)] = (tab, half, host)      # the pinned source stays alive with the copy
+        return ent[0], ent[1]
+
+    def _rs_input(self, wavs, wav_len):
+        """-> (wav [B, ld] on the device with 16-byte aligned rows, lens [B] int64 on the device, Lmax, error flag or
+        None).  A host-side wav_len is checked here; a device-side one gets a zeroed device flag that the kernel raises."""
+        if wav_len is None:
+            if isinstance(wavs, (np.ndarray, torch.Tensor)):
+                raise _lib.FtError('resample_batch: a padded [B, L] batch needs wav_len; without it pass a list of 1-D wavs')
+            return self._gather(wavs, for_stft=False) + (None,)
+        if isinstance(wavs, np.ndarray):
+            wavs = torch.from_numpy(np.ascontiguousarray(wavs, dtype=np.float32))
+        if not isinstance(wavs, torch.Tensor) or wavs.dim() != 2 or wavs.dtype != torch.float32:
+            raise _lib.FtError('resample_batch: with wav_len, wavs must be a float32 [B, L] tensor')
+        B, L = wavs.shape
+        if B < 1 or L < 1:
+            raise _lib.FtError('resample_batch: an empty batch')
+        if not isinstance(wav_len, torch.Tensor):
+            wav_len = torch.as_tensor(np.asarray(wav_len))
+        if wav_len.dim() != 1 or wav_len.numel() != B or wav_len.dtype != torch.int64:
+            raise _lib.FtError(f'resample_batch: wav_len must be int64 [B = {B}]')
+        wav = wavs.to(self.device)
+        if L % 4 or not wav.is_contiguous() or wav.data_ptr() % 16:
+            buf = _alloc(B, (L + 3) // 4 * 4, device=self.device)     # columns >= L are never read: every len <= L
+            buf[:, :L].copy_(wav)
+            wav = buf
+        if not wav_len.is_cuda:
+            if int(wav_len.min()) < 0 or int(wav_len.max()) > L:
+                raise _lib.FtError(f'resample_batch: every wav_len must be in [0, L = {L}] (got {wav_len.tolist()})')
+            return wav, wav_len.pin_memory().to(self.device, non_blocking=True), L, None
+        return wav, wav_len.contiguous(), L, torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _resample(self, wav: torch.Tensor, lens: torch.Tensor, Lmax: int, up: int, down: int,
+                  err: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        ldy = max(4, (-((-Lmax * up) // down) + 3) // 4 * 4)         # from the host's bound: no sync to allocate
+        tab, half = (None, 0) if up == down else self._rs_table(up, down)
+        y, out_len = H.resample_poly_ragged(wav, lens, Lmax, tab, up, down, half, ldy, err, alloc=_alloc)
+        return {'wav': y, 'wav_len': out_len}
+
+    def resample_batch(self, wavs, source_sr: int, target_sr: Optional[int] = None,
+                       wav_len: Optional[Wav] = None) -> Dict[str, torch.Tensor]:
+        """The resampling of DSP.load_wav (librosa.load(path, sr=...)) for a ragged batch, in one launch: source_sr ->
+        target_sr (default: self.sample_rate) by scipy.signal.resample_poly's Kaiser polyphase filter (resample_filter).
+
+        wavs: a list of 1-D numpy arrays or tensors of different lengths (gathered as preprocess_batch does), or a padded
+        float32 tensor [B, L] with wav_len int64 [B] on the host or the device -- griffinlim_batch's 'wav' and 'wav_len'.
+        -> {'wav': float32 [B, ld] on the device, zero at j >= wav_len[b]; 'wav_len': int64 [B] = ceil(len * up / down)},
+        ld = ceil(L * up / down) rounded up to a multiple of 4.
+
+        Exact: item b's samples are bit-identical whether it is passed alone or inside any batch, at any position, and
+        whatever sits beyond the lengths (NaN, Inf) or in other items.  source_sr == target_sr returns the input bits.
+
+        Nothing is sized from device values and, with the lengths on the host, nothing synchronises.  A wav_len that
+        lives on the device is range-checked on the device (lengths are clamped inside the kernel, so nothing indexes out
+        of bounds): the FtError is raised at the end of the call, after one synchronisation, and the flag travels through
+        ONE pinned host word kept on this object -- so one DSP must not run resample_batch with a device-side wav_len
+        from two threads or on two streams at once (host-side lengths are checked up front and have no such limit)."""
+        up, down = resample_ratio(source_sr, self.sample_rate if target_sr is None else target_sr)
+        wav, lens, Lmax, err = self._rs_input(wavs, wav_len)
+        out = self._resample(wav, lens, Lmax, up, down, err)
+        if err is not None:
+            if self._rs_bad is None:
+                self._rs_bad = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._rs_bad.copy_(err, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            if int(self._rs_bad[0]) != 0:
+                raise _lib.FtError(f'resample_batch: every wav_len must be in [0, L = {Lmax}]')
+        return out
+
+    def resample(self, y: Wav, source_sr: int, target_sr: Optional[int] = None) -> Wav:
+        """one 1-D wav at source_sr -> ceil(len(y) * up / down) samples at target_sr (default: self.sample_rate); numpy
+        in -> numpy out, device tensor in -> device tensor out"""
+        if getattr(y, 'ndim', None) != 1:
+            raise _lib.FtError('DSP: every wav must be a 1-D array or tensor')
+        target_sr = self.sample_rate if target_sr is None else target_sr
+        n = resample_len(int(y.shape[0]), source_sr, target_sr)
+        if n == 0:
+            return np.zeros(0, dtype=np.float32) if isinstance(y, np.ndarray) else \
+                torch.zeros(0, dtype=torch.float32, device=self.device)
+        wav = self.resample_batch([y], source_sr, target_sr)['wav'][0, :n]
+        return wav.cpu().numpy() if isinstance(y, np.ndarray) else wav
+
+    # ------------------------------------------------------------------------------------------------
+    def preprocess_batch(self, wavs: Sequence[Wav], source_sr: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """The audio part of Preprocessor._convert_file for a list of wavs of different lengths, in one pass.  Returns
         device tensors: mel [B, n_mels, Tmax] (-11.5129 at frames >= mel_len[b]), mel_len, trim_start, trim_end (int64
         sample indices into the input), peak (max |y| of the trimmed wav), wav [B, Lmax] (trimmed, scaled, zero-padded:
         what a pitch extractor is handed) and wav_len.  As in the reference, an all-zero item under peak_norm=True is
-        divided by its peak of 0: its wav and mel are NaN."""
-        wav, lens, Lmax = self._gather(wavs)
-        return self._run(wav, lens, Lmax, self.should_trim_start_end_silence, 1 if self.should_peak_norm else 0, True,
-                         MEL_PAD_VALUE)
+        divided by its peak of 0: its wav and mel are NaN.
 
-    def preprocess(self, wav: Wav) -> Dict[str, torch.Tensor]:
-        return self.preprocess_batch([wav])
+        source_sr: the rate of `wavs` if it is not self.sample_rate.  The wavs are then resampled first (the reference's
+        load_wav, then _convert_file: one more launch, resample_batch's, and no synchronisation), everything above is
+        computed from the resampled signals, and trim_start / trim_end are sample indices into the RESAMPLED signal,
+        not into the input.  With source_sr None or equal to self.sample_rate the call issues exactly the launches, and
+        returns exactly the bits, of the call without it."""
+        trim, peak = self.should_trim_start_end_silence, 1 if self.should_peak_norm else 0
+        if source_sr is None or _rate(source_sr, 'source_sr') == self.sample_rate:
+            wav, lens, Lmax = self._gather(wavs)
+            return self._run(wav, lens, Lmax, trim, peak, True, MEL_PAD_VALUE)
+        up, down = resample_ratio(source_sr, self.sample_rate)
+        wav, lens, Lmax = self._gather(wavs, for_stft=False)
+        self._check_reflect(-((-min(int(y.shape[0]) for y in wavs) * up) // down))
+        rs = self._resample(wav, lens, Lmax, up, down, None)
+        return self._run(rs['wav'], rs['wav_len'], -((-Lmax * up) // down), trim, peak, True, MEL_PAD_VALUE)
+
+    def preprocess(self, wav: Wav, source_sr: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        return self.preprocess_batch([wav], source_sr)
 
     def wav_to_mel(self, y: Wav, normalize: bool = True) -> Wav:
         """DSP.wav_to_mel: 1-D wav -> [n_mels, 1 + len(y) // hop] (log-mel, or the linear mel with normalize=False)"""
@@ -223,4 +410,5 @@ def split_wavs(out: Dict[str, Wav]) -> List[np.ndarray]:
     return [np.ascontiguousarray(wav[b, :int(wav_len[b])]) for b in range(wav.shape[0])]
 
 
-__all__ = ['DSP', 'MEL_PAD_VALUE', 'sparse_mel_basis', 'split_items', 'split_wavs']
+__all__ = ['DSP', 'MEL_PAD_VALUE', 'resample_filter', 'resample_len', 'resample_ratio', 'resample_table',
+           'sparse_mel_basis', 'split_items', 'split_wavs']

@@ -1377,6 +1377,21 @@ def mel_project(spec: torch.Tensor, Fp: int, rows_per_item: int, mel_len: torch.
     return mel
 
 
+def resample_poly_ragged(x: torch.Tensor, lens: torch.Tensor, Lmax: int, tab: Optional[torch.Tensor], up: int, down: int,
+                         half: int, ldy: int, err: Optional[torch.Tensor] = None, alloc=torch.empty):
+    """csrc/ft_resample.hip: x [B, ldx] fp32, lens [B] int64 (device), tab = the phase-major coefficient table (None for
+    up == down) -> (y [B, ldy] fp32, zero at j >= out_len[b]; out_len [B] int64 = ceil(lens * up / down))"""
+    _chk(x, 'wav'); _chk(lens, 'wav_len', torch.int64)
+    if tab is not None:
+        _chk(tab, 'tab')
+    B, ldx = x.shape
+    y = alloc(B, ldy, dtype=torch.float32, device=x.device)
+    out_len = alloc(B, dtype=torch.int64, device=x.device)
+    _lib.call('ft_resample_poly_ragged', _p(x), ldx, _p(lens), B, Lmax, _p(tab), up, down, half, _p(y), ldy, _p(out_len),
+              _p(err), _stream())
+    return y, out_len
+
+
 # ---------------------------------------------------------------------------------------------------
 # Griffin-Lim on a ragged batch (csrc/ft_dsp.hip, the *_ragged entries; the public interface is
 # vocoder.GriffinLim.griffinlim_batch).  Item b owns rows [b * Tcap, (b + 1) * Tcap); mel_len int64 [B] on the device.

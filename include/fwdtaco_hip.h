@@ -711,6 +711,36 @@ int ft_mel_project(const float* spec, long ld_spec, int Fp, long rows_per_item, 
                    const int* meta, int nnz, int n_mels, int B, int Tmax, int log_clip, float pad_value, float* mel,
                    void* stream);
 
+/* ---- sample-rate conversion in front of the audio front end (utils/dsp.py:40-42 DSP.load_wav = librosa.load(path,
+ *      sr=sample_rate), which resamples every file on the way in) -------------------------------------------------- */
+/* The polyphase design of scipy.signal.resample_poly (librosa res_type='polyphase'), for a ragged batch in the layout of
+ * the front end above: x [B, ldx] fp32, len [B] int64 on the device, Lmax the host's bound.  For source_sr -> target_sr:
+ * g = gcd, up = target_sr / g, down = source_sr / g, R = max(up, down) <= 1024, half = 10 R; in fp64
+ * h[i] = (1/R) sinc((i - half) / R) kaiser(2 half + 1, 5.0)[i], h /= sum(h), h *= up, rounded to fp32 once.  For item b,
+ * out_len[b] = ceil(len[b] * up / down) and, for n < out_len[b],
+ *   y[b, n] = sum over k in [0, len[b]) with 0 <= half + n*down - k*up <= 2 half, ascending k, of
+ *             h[half + n*down - k*up] * x[b, k]
+ * as ONE fp32 fma chain (n*down in 64 bits); y[b, j] = 0 exactly for out_len[b] <= j < ldy.  Zero phase, zero padding on
+ * both sides.  A term is left out by a select, never multiplied by zero, and nothing at k >= len[b] is loaded: NaN or
+ * Inf in the padding of x or in another item changes no bit of an item, and an output's bits depend on its item and its
+ * index alone -- not on B, Lmax, ldx, ldy or the item's position.
+ * tab: the coefficients phase-major, [up][Tp] fp32 with T = ceil((2 half + 1) / up) taps per phase and the odd row
+ * stride Tp = T | 1: tab[p * Tp + t] = h[p + t * up], 0 where p + t * up > 2 half, zero-filled up to
+ * ft_resample_table_floats(up, down, half) floats (a multiple of 4; 0 = bad arguments), 16-byte aligned.
+ * up == down is the identity (tab may be NULL): y[b, :len[b]] = x[b, :len[b]], out_len = len.
+ * A len[b] outside [0, Lmax] is clamped into it (nothing indexes out of bounds) and sets *err_flag = 1 (int32 on the
+ * device, zeroed by the caller; NULL = no report).  ldx % 4 == 0, ldy % 4 == 0, 1 <= Lmax <= ldx,
+ * ldy >= ceil(Lmax * up / down), x and y 16-byte aligned.  One launch: a workgroup owns a tile of
+ * ft_resample_tile(up, down, half) = 1024 consecutive outputs of one item (0 = bad arguments), grid (ceil(ldy / 1024), B).
+ * ft_resample_route: which kernel the ratio takes -- 1: the table, the tile's input window and its outputs staged in LDS
+ * (they fit 64 KiB: the pairs of standard rates down to about 4:1), 0: operands read through the cache (the same fma
+ * chain, the same bits), 2: the identity copy, -1: bad arguments. */
+int ft_resample_table_floats(int up, int down, int half);
+int ft_resample_tile(int up, int down, int half);
+int ft_resample_route(int up, int down, int half);
+int ft_resample_poly_ragged(const float* x, long ldx, const long* len, int B, long Lmax, const float* tab, int up,
+                            int down, int half, float* y, long ldy, long* out_len, int* err_flag, void* stream);
+
 /* ---- durations from a Tacotron attention (duration_extraction/duration_extractor.py:23-84 DurationExtractor ;
  *      duration_extraction_pipe.py:56-62,173-183 ; utils/metrics.py:4-31 attention_score, r = 1) ---------------- */
 /* One workgroup per item b; every length is read on the device.  Inputs: attn [B,Tm,Tx] fp32 (rows = mel frames),
