@@ -1393,6 +1393,60 @@ def resample_poly_ragged(x: torch.Tensor, lens: torch.Tensor, Lmax: int, tab: Op
 
 
 # ---------------------------------------------------------------------------------------------------
+# pYIN on a ragged batch (csrc/ft_pitch.hip; the public interface is pitch.LibrosaPitchExtractor).  `tb` is
+# pitch.pyin_tables(...), `dev` its float32 tables on the device.
+# ---------------------------------------------------------------------------------------------------
+def pyin_cmnd(wav: torch.Tensor, lens: torch.Tensor, Lmax: int, frame_length: int, hop: int, pmin: int, pmax: int,
+              Tmax: int, alloc=torch.empty):
+    """wav [B, ld] fp32, lens [B] int64 (device) -> (dn [B, Tmax, P] fp32, frames [B] int64 = 1 + lens // hop)"""
+    _chk(wav, 'wav'); _chk(lens, 'wav_len', torch.int64)
+    B, ld = wav.shape
+    dn = alloc(B, Tmax, pmax - pmin + 1, dtype=torch.float32, device=wav.device)
+    frames = alloc(B, dtype=torch.int64, device=wav.device)
+    _lib.call('ft_pyin_cmnd', _p(wav), ld, _p(lens), B, Lmax, frame_length, hop, pmin, pmax, Tmax, _p(dn), _p(frames),
+              _stream())
+    return dn, frames
+
+
+def pyin_observe(dn: torch.Tensor, frames: torch.Tensor, tb, dev, debug: bool = False, alloc=torch.empty):
+    """dn [B, Tmax, P], frames [B] int64 -> {'lo_v' [B, Tmax, N], 'lo_u', 'vp' [B, Tmax]}; debug adds 'prob' [B, Tmax, P],
+    'info' [B, Tmax, 102] int32 and 'pos' [B, Tmax, P, 100] int16 (include/fwdtaco_hip.h: ft_pyin_observe)"""
+    _chk(dn, 'dn'); _chk(frames, 'frames', torch.int64)
+    B, Tmax, P = dn.shape
+    if P != tb['P']:
+        raise _lib.FtError(f'pyin_observe: dn holds {P} periods, the tables {tb["P"]}')
+    N = tb['N']
+    out = {'lo_v': alloc(B, Tmax, N, dtype=torch.float32, device=dn.device),
+           'lo_u': alloc(B, Tmax, dtype=torch.float32, device=dn.device),
+           'vp': alloc(B, Tmax, dtype=torch.float32, device=dn.device)}
+    if debug:
+        out['prob'] = alloc(B, Tmax, P, dtype=torch.float32, device=dn.device)
+        out['info'] = alloc(B, Tmax, 102, dtype=torch.int32, device=dn.device)
+        out['pos'] = alloc(B, Tmax, P, 100, dtype=torch.int16, device=dn.device)
+    _lib.call('ft_pyin_observe', _p(dn), _p(frames), B, Tmax, P, tb['pmin'], N, float(tb['sr']), float(tb['fmin']),
+              _p(dev['thr']), _p(dev['bp']), _p(dev['bpc']), _p(dev['E']), _p(dev['C']), tb['nE'], tb['LZ'],
+              _p(out['lo_v']), _p(out['lo_u']), _p(out['vp']), _p(out.get('prob')), _p(out.get('info')), _p(out.get('pos')), _stream())
+    return out
+
+
+def pyin_viterbi(lo_v: torch.Tensor, lo_u: torch.Tensor, frames: torch.Tensor, tb, dev, alloc=torch.empty):
+    """lo_v [B, Tmax, N], lo_u [B, Tmax], frames [B] int64 -> {'state' [B, Tmax] int32, 'score' [B], 'pitch' [B, Tmax]}"""
+    _chk(lo_v, 'lo_v'); _chk(lo_u, 'lo_u'); _chk(frames, 'frames', torch.int64)
+    B, Tmax, N = lo_v.shape
+    if N != tb['N'] or lo_u.shape != (B, Tmax):
+        raise _lib.FtError('pyin_viterbi: lo_v must be [B, Tmax, N] of the tables and lo_u [B, Tmax]')
+    out = {'state': alloc(B, Tmax, dtype=torch.int32, device=lo_v.device),
+           'score': alloc(B, dtype=torch.float32, device=lo_v.device),
+           'pitch': alloc(B, Tmax, dtype=torch.float32, device=lo_v.device)}
+    nbytes = _lib.query('ft_pyin_viterbi_workspace', B, Tmax, N)
+    ws = alloc(max(nbytes, 2), dtype=torch.uint8, device=lo_v.device)
+    _lib.call('ft_pyin_viterbi', _p(lo_v), _p(lo_u), _p(frames), B, Tmax, N, tb['half'], _p(dev['logtri']),
+              _p(dev['lognorm']), _p(dev['freqs']), tb['ls'], tb['lw'], tb['LZ'], tb['lN'], _p(out['state']),
+              _p(out['score']), _p(out['pitch']), _p(ws), nbytes, _stream())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # Griffin-Lim on a ragged batch (csrc/ft_dsp.hip, the *_ragged entries; the public interface is
 # vocoder.GriffinLim.griffinlim_batch).  Item b owns rows [b * Tcap, (b + 1) * Tcap); mel_len int64 [B] on the device.
 # ---------------------------------------------------------------------------------------------------

@@ -858,6 +858,66 @@ int ft_taco_gen_batch_steps(const float* enc_proj, const float* enc_pq, const fl
                             int Tx, int lstm_dims, int r, int S, int s0, int n, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* ---- raw pitch of a ragged batch: pYIN (pitch_extraction/pitch_extractor.py:24-47 LibrosaPitchExtractor) --------- */
+/* Probabilistic YIN (Mauch & Dixon 2014) with librosa.pyin's documented defaults, in three launches (csrc/ft_pitch.hip);
+ * the full definition is DESIGN.md section 7, the numpy restatement tests/pyin_cpu.py, the host tables
+ * forwardtacotron_amd/pitch.py pyin_tables.  With W = frame_length / 2: pmin = max(floor(sr / fmax), 1), pmax =
+ * min(ceil(sr / fmin), frame_length - W - 1), P = pmax - pmin + 1 periods; N = floor(120 log2(fmax / fmin)) + 1 pitch
+ * bins; half = 5 round(35.92 * 12 * hop / sr), a transition band of 2 half + 1 bins.  Item b has T_b = 1 + len_b / hop
+ * frames (wav_to_mel's mel_len); frame t is frame_length samples from t * hop of the wav zero-padded by
+ * frame_length / 2 on both sides.  Every entry reads its lengths on the device and clamps them (wav_len into [0, Lmax],
+ * frames into [0, Tmax]; the Viterbi into [1, Tmax]); nothing past a length is loaded; nothing is sized from device
+ * values and nothing synchronises.  Limits: frame_length even and >= 4; the samples of four frames and their difference
+ * functions sit in LDS, ft_pyin_cmnd_lds(...) bytes <= 65536 (0: bad arguments); P <= 1024; N <= 1024, i.e. at most
+ * 2N = 2048 HMM states (two per thread of the Viterbi's 1024), half <= 2048, and the Viterbi's LDS plan -- (4N + 6 half +
+ * 33) floats, 2N flag bytes and at least one row of 2N 16-bit back-pointers -- within 65536 bytes: ft_pyin_viterbi_rows(N,
+ * half) is the number of back-pointer rows it holds (at most 32), 0 where N or half is out of range or no row fits (N =
+ * 1024 fits up to half = 1786).
+ *
+ * ft_pyin_cmnd: wav [B, ld] fp32, wav_len [B] int64 -> dn [B, Tmax, P] fp32, Tmax = 1 + Lmax / hop, and frames [B]
+ * int64 = T_b.  d(tau) = sum_{j < W} (x_j - x_{j+tau})^2 for tau = 0 .. pmax, formed directly in fp32 (one ascending fma
+ * chain per tau, the same whatever the batch); c(tau) = (sum_{u = 1 .. tau} d(u)) / tau; dn[tau - pmin] = d(tau) /
+ * max(c(tau), FLT_MIN).  A frame of zeros and every frame t >= T_b give exactly 0.
+ *
+ * ft_pyin_observe: dn, frames -> lo_v [B, Tmax, N], lo_u [B, Tmax], vp [B, Tmax].  Host tables, float64 rounded once:
+ * thr[k] = (k + 1) / 100, bp[k] = F((k + 1) / 100) - F(k / 100) of the Beta(2, 18) cdf F, k = 0 .. 99; bpc[m] = sum of
+ * bp[0 .. m - 1], m = 0 .. 100; E[pos] = exp(-2 pos), C[n] = (1 - exp(-2)) / (1 - exp(-2 n)) (C[0] = 0), nE >= (P + 1) /
+ * 2 + 1 entries each; LZ = log(FLT_MIN).  Trough i: dn[i] < dn[i-1] and dn[i] <= dn[i+1] (ends: strictly below the one
+ * neighbour).  p_i = sum over k ascending of [h_i < thr[k]] (E[pos(i,k)] * C[n(k)]) * bp[k] in fp32, pos / n = troughs
+ * below thr[k] before i / in all; the lowest trough g of minimal height gets p_g += 0.01f * bpc[m], m = the number of k
+ * with h_g >= thr[k].  A trough with p_i > 0 is a candidate at period pmin + i + shift (parabolic shift -b / a if |b| <
+ * |a| else 0, 0 at both ends) and bin floor(120 log2(f0 / fmin) + 0.5), both formed in fp64 from the fp32 dn; bin < 0
+ * becomes 0, bin > N - 1 drops the candidate, the larger i wins a shared bin.  vp = clamp(sum of the bins' p, 0, 1);
+ * lo_v = log(max(p, FLT_MIN)) (LZ itself where p is 0), lo_u = log(max((1 - vp) / N, FLT_MIN)).  A frame t >= frames[b]
+ * is treated as dn = 0: lo_v = LZ, vp = 0.  Optional outputs for tests (NULL to skip): prob [B, Tmax, P] = p_i, -1 where
+ * i is no trough; info [B, Tmax, 102] int32 = (g or -1, m, n(0) .. n(99)); pos [B, Tmax, P, 100] int16 = pos(i, k) where
+ * trough i is below thr[k], -1 where it is not or i is no trough (so pos >= 0 is `below`).
+ *
+ * ft_pyin_viterbi: lo_v, lo_u, frames -> state [B, Tmax] int32, score [B], pitch [B, Tmax].  States: voiced bins
+ * 0 .. N-1, then unvoiced N .. 2N-1.  Host tables: logtri [2 half + 1] = log of the triangle window, lognorm [N] = log of
+ * its sum over the targets inside [0, N), freqs [N] = fmin 2^(s / 120); ls = log .99, lw = log .01, LZ, lN = -log N.  Every
+ * operation is one fp32 add, subtract or maximum: t = 0: delta_v[s] = LZ + lo_v[0, s], delta_u[s] = lN + lo_u[0]; t >= 1:
+ * a[k] = max(delta_v[k] + ls, delta_u[k] + lw) - lognorm[k], delta'_v[s] = max over |s - k| <= half of (a[k] + logtri[s -
+ * k + half]) + lo_v[t, s]; the unvoiced targets take max(delta_v[k] + lw, delta_u[k] + ls) and add lo_u[t]; after every
+ * step, t = 0 included, the maximum over all 2N states is subtracted.  score = the fp32 running sum of the subtracted
+ * maxima in step order (the final maximum is 0 after the normalisation, so this is the path's log score).  Ties inside a
+ * step go to the lowest source state; the path is traced back from the lowest maximal final state.  pitch[t] =
+ * freqs[state] for a voiced state, 0 for an unvoiced one; at t >= T_b state is -1 and pitch 0.  An item with NaN in its
+ * observations finishes like any other (every loop is bounded by Tmax and N); its path is a valid state sequence of no
+ * meaning and its score NaN.  ws: ft_pyin_viterbi_workspace(B, Tmax, N) bytes (16-bit back-pointers [B, Tmax, 2N]; 0:
+ * bad dims). */
+size_t ft_pyin_cmnd_lds(int frame_length, int hop, int pmin, int pmax);
+int ft_pyin_cmnd(const float* wav, long ld, const long* wav_len, int B, long Lmax, int frame_length, int hop, int pmin,
+                 int pmax, int Tmax, float* dn, long* frames, void* stream);
+int ft_pyin_observe(const float* dn, const long* frames, int B, int Tmax, int P, int pmin, int N, double sr, double fmin,
+                    const float* thr, const float* bp, const float* bpc, const float* E, const float* C, int nE, float LZ,
+                    float* lo_v, float* lo_u, float* vp, float* prob, int* info, short* pos, void* stream);
+int ft_pyin_viterbi_rows(int N, int half);
+size_t ft_pyin_viterbi_workspace(int B, int Tmax, int N);
+int ft_pyin_viterbi(const float* lo_v, const float* lo_u, const long* frames, int B, int Tmax, int N, int half,
+                    const float* logtri, const float* lognorm, const float* freqs, float ls, float lw, float LZ, float lN,
+                    int* state, float* score, float* pitch, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
