@@ -13,12 +13,12 @@ of preprocess.py:78-89 `Preprocessor._convert_file` (trim_silence, peak normalis
     wavs = split_wavs(dsp.griffinlim_batch(mel, mel_len))    # a ragged batch of mels (generate_batch's) -> wavs
 
 HIP device only, like vocoder.GriffinLim: without a device the constructor raises FtError.  The wavs are first gathered
-into one zero-padded [B, ld] device buffer (numpy inputs: one host-to-device copy; device tensors: a fill and one copy
-per item, B + 1 small launches, still without a host synchronisation).  After that one call is five launches:
-ft_wav_trim_peak (two), ft_wav_pack, the DFT of every frame of every item as ONE GEMM over the packed buffer read with
-a row stride of hop (ft_linear_multi_fwd_as with a fixed `as_rows`, so the GEMM kernel -- and with it the rounding --
-does not depend on the batch: an item alone gives the bits it gives inside a batch), and ft_mel_project.  Semantics are
-in include/fwdtaco_hip.h; the float64 restatement the tests compare against is tests/mel_cpu.py.
+into one zero-padded [B, ld] device buffer and lengths are taken from the host or the device: the intake of a ragged
+batch and its contract are ragged.py's.  After that one call is five launches: ft_wav_trim_peak (two), ft_wav_pack, the
+DFT of every frame of every item as ONE GEMM over the packed buffer read with a row stride of hop (hip.linear_fwd_as,
+whose kernel -- and with it the rounding -- does not depend on the batch: an item alone gives the bits it gives inside
+a batch), and ft_mel_project.  Semantics are in include/fwdtaco_hip.h; the float64 restatement the tests compare
+against is tests/mel_cpu.py.
 
 PARITY UNPINNED against the reference, as for the vocoder: librosa is not installed here.  What is restated is
 librosa's published algorithm: stft(center=True) with ZERO padding of n_fft // 2 (librosa >= 0.10; `pad_mode='reflect'`
@@ -39,7 +39,6 @@ construction; the file I/O of load_wav / save_wav (reading and writing wav files
 denormalize are the two element-wise conveniences of the reference's interface; the hot path has them fused into
 ft_mel_project / ft_exp_transpose.
 """
-import ctypes
 import math
 import operator
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
@@ -49,11 +48,10 @@ import torch
 
 from . import _lib
 from . import hip as H
+from . import ragged
 from .vocoder import GriffinLim, slaney_mel_basis
 
 MEL_PAD_VALUE = -11.5129          # datapath.MEL_PAD_VALUE: what the collators pad mels with
-# the DFT GEMM is always rounded like a launch over this many rows (the 128 x 128 tile), whatever the batch holds
-_AS_ROWS = 1 << 20
 
 Wav = Union[np.ndarray, torch.Tensor]
 
@@ -158,46 +156,21 @@ class DSP:
         w, meta = sparse_mel_basis(slaney_mel_basis(sample_rate, n_fft, num_mels, fmin, fmax))
         self.mel_w = torch.from_numpy(w).to(self.device)
         self.mel_meta = torch.from_numpy(meta).to(self.device)
-        self._w_ptr = H._ptr_array([self.gl.w_fwd])
-        self._col0 = (ctypes.c_int * 1)(0)
-        self._outf = (ctypes.c_int * 1)(2 * self.Fp)
         self._rs_tabs: Dict[Tuple[int, int], Any] = {}          # resampling coefficient tables per (up, down)
-        self._rs_bad: Optional[torch.Tensor] = None             # the pinned word a device-side length check reports through
+        self._len_flag = ragged.LenFlag()                       # the pinned word a device-side length check reports through
 
     @classmethod
     def from_config(cls, config: Dict[str, Any], **kw) -> 'DSP':
         return cls(**config['dsp'], **kw)
 
     # ------------------------------------------------------------------------------------------------
-    def _check_reflect(self, min_len: int) -> None:
-        if self.pad_mode == 'reflect' and min_len <= self.n_fft // 2:
+    def _wavs(self, wavs: Sequence[Wav], up: int = 1, down: int = 1):
+        """the wavs of an STFT: ragged.gather_wavs with rows of a multiple of 4 floats, an all-empty batch refused; under
+        pad_mode='reflect' the shortest wav, after a resampling by up / down, must be longer than the padding"""
+        out = ragged.gather_wavs(wavs, self.device, 'DSP', row_multiple=4, allow_all_empty=False, alloc=_alloc)
+        if self.pad_mode == 'reflect' and -((-min(int(y.shape[0]) for y in wavs) * up) // down) <= self.n_fft // 2:
             raise _lib.FtError(f"DSP: pad_mode='reflect' needs more than n_fft // 2 = {self.n_fft // 2} samples per wav")
-
-    def _gather(self, wavs: Sequence[Wav], for_stft: bool = True):
-        """list of 1-D wavs -> (wav [B, ld] zero-padded device tensor, lens [B] int64 device tensor, Lmax)"""
-        if len(wavs) == 0:
-            raise _lib.FtError('DSP: an empty batch')
-        lens = []
-        for y in wavs:
-            if getattr(y, 'ndim', None) != 1:
-                raise _lib.FtError('DSP: every wav must be a 1-D array or tensor')
-            lens.append(int(y.shape[0]))
-        Lmax = max(lens)
-        if Lmax == 0:
-            raise _lib.FtError('DSP: every wav of the batch is empty')
-        if for_stft:
-            self._check_reflect(min(lens))
-        ld = (Lmax + 3) // 4 * 4
-        if all(isinstance(y, np.ndarray) for y in wavs):
-            host = np.zeros((len(wavs), ld), dtype=np.float32)
-            for b, y in enumerate(wavs):
-                host[b, :lens[b]] = y
-            wav = torch.from_numpy(host).to(self.device)
-        else:
-            wav = torch.zeros(len(wavs), ld, dtype=torch.float32, device=self.device)
-            for b, y in enumerate(wavs):
-                wav[b, :lens[b]] = torch.as_tensor(y).to(self.device, torch.float32)
-        return wav, torch.tensor(lens, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True), Lmax
+        return out
 
     def _run(self, wav: torch.Tensor, lens: torch.Tensor, Lmax: int, do_trim: bool, peak_mode: int, log_clip: bool,
              pad_value: float) -> Dict[str, torch.Tensor]:
@@ -207,12 +180,7 @@ class DSP:
         Tcap = (ld + n_fft + hop - 1) // hop                    # rows per item; its padded signal fits in Tcap * hop
         tp = H.wav_trim_peak(wav, lens, Lmax, do_trim, self.trim_silence_top_db, peak_mode, hop, alloc=_alloc)
         packed, wav_out = H.wav_pack(wav, tp, Tcap * hop, n_fft, self.pad_mode == 'reflect', alloc=_alloc)
-        rows = B * Tcap
-        spec = _alloc(rows, 2 * Fp, device=self.device)
-        c_void_p = ctypes.c_void_p
-        _lib.call('ft_linear_multi_fwd_as', packed.data_ptr(), hop, 1, ctypes.cast(self._w_ptr, c_void_p), None,
-                  spec.data_ptr(), 2 * Fp, ctypes.cast(self._col0, c_void_p), ctypes.cast(self._outf, c_void_p), rows,
-                  n_fft, _AS_ROWS, H._stream())
+        spec = H.linear_fwd_as(packed, hop, self.gl.w_fwd, B * Tcap, n_fft, alloc=_alloc)     # frames read in place
         mel = H.mel_project(spec, Fp, Tcap, tp['mel_len'], self.mel_w, self.mel_meta, self.n_mels, B, Tmax, log_clip,
                             pad_value, alloc=_alloc)
         return {'mel': mel, 'mel_len': tp['mel_len'], 'trim_start': tp['trim_start'], 'trim_end': tp['trim_end'],
@@ -235,32 +203,14 @@ class DSP:
 
     def _rs_input(self, wavs, wav_len):
         """-> (wav [B, ld] on the device with 16-byte aligned rows, lens [B] int64 on the device, Lmax, error flag or
-        None).  A host-side wav_len is checked here; a device-side one gets a zeroed device flag that the kernel raises."""
-        if wav_len is None:
-            if isinstance(wavs, (np.ndarray, torch.Tensor)):
-                raise _lib.FtError('resample_batch: a padded [B, L] batch needs wav_len; without it pass a list of 1-D wavs')
-            return self._gather(wavs, for_stft=False) + (None,)
-        if isinstance(wavs, np.ndarray):
-            wavs = torch.from_numpy(np.ascontiguousarray(wavs, dtype=np.float32))
-        if not isinstance(wavs, torch.Tensor) or wavs.dim() != 2 or wavs.dtype != torch.float32:
-            raise _lib.FtError('resample_batch: with wav_len, wavs must be a float32 [B, L] tensor')
-        B, L = wavs.shape
-        if B < 1 or L < 1:
-            raise _lib.FtError('resample_batch: an empty batch')
-        if not isinstance(wav_len, torch.Tensor):
-            wav_len = torch.as_tensor(np.asarray(wav_len))
-        if wav_len.dim() != 1 or wav_len.numel() != B or wav_len.dtype != torch.int64:
-            raise _lib.FtError(f'resample_batch: wav_len must be int64 [B = {B}]')
-        wav = wavs.to(self.device)
-        if L % 4 or not wav.is_contiguous() or wav.data_ptr() % 16:
-            buf = _alloc(B, (L + 3) // 4 * 4, device=self.device)     # columns >= L are never read: every len <= L
+        None): the intake of ragged.py, then the rows of a padded batch re-laid where they are not aligned"""
+        wav, lens, L, err = ragged.intake(wavs, wav_len, self.device, 'resample_batch', row_multiple=4,
+                                          allow_all_empty=False, alloc=_alloc)
+        if wav.shape[1] % 4 or not wav.is_contiguous() or wav.data_ptr() % 16:
+            buf = _alloc(len(wav), (L + 3) // 4 * 4, device=self.device)      # columns >= L are never read: every len <= L
             buf[:, :L].copy_(wav)
             wav = buf
-        if not wav_len.is_cuda:
-            if int(wav_len.min()) < 0 or int(wav_len.max()) > L:
-                raise _lib.FtError(f'resample_batch: every wav_len must be in [0, L = {L}] (got {wav_len.tolist()})')
-            return wav, wav_len.pin_memory().to(self.device, non_blocking=True), L, None
-        return wav, wav_len.contiguous(), L, torch.zeros(1, dtype=torch.int32, device=self.device)
+        return wav, lens, L, err
 
     def _resample(self, wav: torch.Tensor, lens: torch.Tensor, Lmax: int, up: int, down: int,
                   err: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -282,21 +232,14 @@ class DSP:
         Exact: item b's samples are bit-identical whether it is passed alone or inside any batch, at any position, and
         whatever sits beyond the lengths (NaN, Inf) or in other items.  source_sr == target_sr returns the input bits.
 
-        Nothing is sized from device values and, with the lengths on the host, nothing synchronises.  A wav_len that
-        lives on the device is range-checked on the device (lengths are clamped inside the kernel, so nothing indexes out
-        of bounds): the FtError is raised at the end of the call, after one synchronisation, and the flag travels through
-        ONE pinned host word kept on this object -- so one DSP must not run resample_batch with a device-side wav_len
-        from two threads or on two streams at once (host-side lengths are checked up front and have no such limit)."""
+        The lengths follow the contract of ragged.py: a host-side wav_len is checked up front and nothing synchronises;
+        a device-side one is clamped inside the kernel and its FtError is raised at the end of the call, after one
+        synchronisation, through ONE pinned host word kept on this object -- so one DSP must not run resample_batch
+        with a device-side wav_len from two threads or on two streams at once."""
         up, down = resample_ratio(source_sr, self.sample_rate if target_sr is None else target_sr)
         wav, lens, Lmax, err = self._rs_input(wavs, wav_len)
         out = self._resample(wav, lens, Lmax, up, down, err)
-        if err is not None:
-            if self._rs_bad is None:
-                self._rs_bad = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._rs_bad.copy_(err, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            if int(self._rs_bad[0]) != 0:
-                raise _lib.FtError(f'resample_batch: every wav_len must be in [0, L = {Lmax}]')
+        self._len_flag.check(err, ragged.range_message('resample_batch', 'wav_len', 0, Lmax, 'L'))
         return out
 
     def resample(self, y: Wav, source_sr: int, target_sr: Optional[int] = None) -> Wav:
@@ -327,11 +270,10 @@ class DSP:
         returns exactly the bits, of the call without it."""
         trim, peak = self.should_trim_start_end_silence, 1 if self.should_peak_norm else 0
         if source_sr is None or _rate(source_sr, 'source_sr') == self.sample_rate:
-            wav, lens, Lmax = self._gather(wavs)
+            wav, lens, Lmax = self._wavs(wavs)
             return self._run(wav, lens, Lmax, trim, peak, True, MEL_PAD_VALUE)
         up, down = resample_ratio(source_sr, self.sample_rate)
-        wav, lens, Lmax = self._gather(wavs, for_stft=False)
-        self._check_reflect(-((-min(int(y.shape[0]) for y in wavs) * up) // down))
+        wav, lens, Lmax = self._wavs(wavs, up, down)
         rs = self._resample(wav, lens, Lmax, up, down, None)
         return self._run(rs['wav'], rs['wav_len'], -((-Lmax * up) // down), trim, peak, True, MEL_PAD_VALUE)
 
@@ -340,13 +282,13 @@ class DSP:
 
     def wav_to_mel(self, y: Wav, normalize: bool = True) -> Wav:
         """DSP.wav_to_mel: 1-D wav -> [n_mels, 1 + len(y) // hop] (log-mel, or the linear mel with normalize=False)"""
-        wav, lens, Lmax = self._gather([y])
+        wav, lens, Lmax = self._wavs([y])
         mel = self._run(wav, lens, Lmax, False, -1, bool(normalize), MEL_PAD_VALUE if normalize else 0.0)['mel'][0]
         return mel.cpu().numpy() if isinstance(y, np.ndarray) else mel
 
     def trim_silence(self, wav: Wav) -> Wav:
         """librosa.effects.trim(wav, top_db, frame_length=2048, hop_length=512)[0]"""
-        dev, lens, Lmax = self._gather([wav])
+        dev, lens, Lmax = self._wavs([wav])
         tp = H.wav_trim_peak(dev, lens, Lmax, True, self.trim_silence_top_db, -1, self.hop_length, alloc=_alloc)
         s, e = int(tp['trim_start'][0]), int(tp['trim_end'][0])
         return wav[s:e]

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void ft_wav_block_stats_kernel(const float* __
                                                                  const long* __restrict__ len, float* __restrict__ sq,
                                                                  float* __restrict__ mx, int nblk) {
   const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long L = clampl(len[b], 0, Lmax);
+  const long L = ft_item_len(len, b, 0, Lmax, nullptr);
   const float* y = wav + (long)b * ld;
   const int k0 = (blockIdx.x * 4 + w) * 4;
   f32x4 v[4][2];
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void ft_wav_trim_kernel(const float* __restric
   __shared__ int redlo[256], redhi[256];
   __shared__ long bounds[2];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const long L = clampl(len[b], 0, ld);
+  const long L = ft_item_len(len, b, 0, ld, nullptr);
   const float* s = sq + (long)b * nblk;
   if (do_trim) {
     const int nfr = 1 + (int)(L / kTrimHop);
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void ft_mel_project_kernel(const float* __rest
   float* mag = lds;
   float* wl = lds + TT * ldm;
   const int b = blockIdx.y, t0 = blockIdx.x * TT, tid = threadIdx.x;
-  const long ml = clampl(mel_len[b], 0, rows_per_item < Tmax ? rows_per_item : (long)Tmax);
+  const long ml = ft_item_len(mel_len, b, 0, rows_per_item < Tmax ? rows_per_item : (long)Tmax, nullptr);
   const int nt = ml - t0 < TT ? (int)(ml - t0) : TT;
   if (nt > 0) {
     for (int i = tid; i < nnz; i += 256) wl[i] = w[i];

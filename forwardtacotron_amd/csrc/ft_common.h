@@ -51,6 +51,18 @@ __device__ __forceinline__ double ft_wave_sum_d(double v) {
   return v;
 }
 
+// Item b's length of a ragged batch, clamped into [lo, hi] so that nothing indexes out of bounds.  A length outside the
+// range sets *err where err is non-null: the callers pass it from exactly one thread of the item and nullptr from the
+// rest (and everywhere, where the clamp is silent).  Plain load, plain store, no synchronisation.
+__device__ __forceinline__ long ft_item_len(const long* __restrict__ len, int b, long lo, long hi, int* err) {
+  long L = len[b];
+  if (L < lo || L > hi) {
+    if (err) *err = 1;
+    L = L < lo ? lo : hi;
+  }
+  return L;
+}
+
 // counter-based dropout mask (ft_dropout and the kernels that fuse it): element i of a tensor is kept iff u(seed, i) >= p;
 // the backward re-derives the same mask from the seed, so no mask tensor is stored.  32-bit mixing (three multiplies:
 // the attention kernels draw one decision per score element, forward and twice in the backward -- the 64-bit finalizer

@@ -104,16 +104,7 @@ __global__ __launch_bounds__(256) void ft_overlap_add_kernel(const float* __rest
 }
 
 // ---- ragged batch ------------------------------------------------------------------------------------------------
-// an item's frame count, clamped into [1, Tmax] so that nothing indexes out of bounds; err (one thread passes it) is raised
-__device__ __forceinline__ int gl_item_len(const long* __restrict__ mel_len, int b, int Tmax, int* err) {
-  long N = mel_len[b];
-  if (N < 1 || N > Tmax) {
-    if (err) *err = 1;
-    N = N < 1 ? 1 : Tmax;
-  }
-  return (int)N;
-}
-
+// an item's frame count is ft_item_len(mel_len, b, 1, Tmax, err): clamped into [1, Tmax]
 __global__ __launch_bounds__(256) void ft_gl_exp_transpose_ragged_kernel(const float* __restrict__ in,
                                                                          const long* __restrict__ mel_len,
                                                                          float* __restrict__ out, int C, int Tmax,
@@ -121,7 +112,7 @@ __global__ __launch_bounds__(256) void ft_gl_exp_transpose_ragged_kernel(const f
   __shared__ float tile[32][33];
   const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const bool first = (blockIdx.x | blockIdx.y | threadIdx.x | threadIdx.y) == 0;
-  const int N = gl_item_len(mel_len, b, Tmax, first ? err : nullptr);
+  const int N = (int)ft_item_len(mel_len, b, 1, Tmax, first ? err : nullptr);
   const float* src = in + (long)b * C * Tmax;
   for (int i = threadIdx.y; i < 32; i += 8) {
     const int c = c0 + i, t = t0 + threadIdx.x;
@@ -163,7 +154,7 @@ __global__ __launch_bounds__(256) void ft_gl_init_ragged_kernel(const float* __r
   const long row = i / q;
   const int m = (int)(i - row * q) * 4;
   const int b = (int)(row / Tcap), n = (int)(row - (long)b * Tcap);
-  const int N = gl_item_len(mel_len, b, Tmax, (n == 0 && m == 0) ? err : nullptr);
+  const int N = (int)ft_item_len(mel_len, b, 1, Tmax, (n == 0 && m == 0) ? err : nullptr);
   float4 re = make_float4(0.f, 0.f, 0.f, 0.f), im = re, uu = re;
   if (n < N) {
     const float4 s = *reinterpret_cast<const float4*>(S + row * Fp + m);
@@ -204,7 +195,7 @@ __global__ __launch_bounds__(256) void ft_gl_phase_ragged_kernel(const float* __
   const long row = i / q;
   const int m = (int)(i - row * q) * 4;
   const int b = (int)(row / Tcap), n = (int)(row - (long)b * Tcap);
-  const int N = gl_item_len(mel_len, b, Tmax, nullptr);
+  const int N = (int)ft_item_len(mel_len, b, 1, Tmax, nullptr);
   const long ire = row * 2 * Fp + m, iim = ire + Fp;
   float4 pr = make_float4(0.f, 0.f, 0.f, 0.f), pi = pr, tr = pr, ti = pr;
   if (n < N) {                                  // rows past the item: `rebuilt` holds its neighbour's samples, not read
@@ -254,7 +245,7 @@ __global__ __launch_bounds__(256) void ft_overlap_add_ragged_kernel(const float*
                                                                     float* __restrict__ ypad, float* __restrict__ wav,
                                                                     int B, int Tcap, int Tmax, int n_fft, int hop) {
   const int b = blockIdx.y;
-  const int N = gl_item_len(mel_len, b, Tmax, nullptr);
+  const int N = (int)ft_item_len(mel_len, b, 1, Tmax, nullptr);
   const long pad = n_fft / 2, sig = (long)hop * (N - 1);        // the item's signal is ypad_b[pad, pad + sig)
   const float* fr = frames + (long)b * Tcap * n_fft;
   const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;

@@ -31,7 +31,6 @@ constexpr int kMaxN = 1024;                 // viterbi: 2N <= 2048 states, at mo
 constexpr int kMaxHalf = 2048;
 constexpr size_t kLdsBudget = 65536;
 
-__device__ __forceinline__ int py_clampi(long v, long lo, long hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // stage 1.  A workgroup owns kFrames consecutive frames of one item and stages their samples once (consecutive frames
@@ -55,8 +54,7 @@ __global__ __launch_bounds__(kCmndThreads) void py_cmnd_kernel(const float* __re
                                                                long* __restrict__ frames) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int b = blockIdx.y, tid = threadIdx.x;
-  long L = len[b];
-  L = L < 0 ? 0 : (L > Lmax ? Lmax : L);
+  const long L = ft_item_len(len, b, 0, Lmax, nullptr);
   const int T = (int)(1 + L / hop);                                     // <= Tmax = 1 + Lmax / hop
   if (blockIdx.x == 0 && tid == 0) frames[b] = T;
   const int t0 = blockIdx.x * kFrames;
@@ -195,7 +193,7 @@ __global__ __launch_bounds__(kObsThreads) void py_observe_kernel(
   __shared__ int wminq[kObsThreads / 64];
   __shared__ float wsum[kObsThreads / 64];
   const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = py_clampi(frames[b], 0, Tmax);
+  const int T = (int)ft_item_len(frames, b, 0, Tmax, nullptr);
   const bool live = t < T;
   const long row = (long)b * Tmax + t;
   if (!live) {                                                          // past the item: what a frame of dn = 0 gives
@@ -402,7 +400,7 @@ __global__ __launch_bounds__(kVitThreads) void py_viterbi_kernel(
   unsigned char* fuv = reinterpret_cast<unsigned char*>(lds) + g.flag_off;
   unsigned char* fuu = fuv + N;
   unsigned short* rows = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(lds) + g.rows_off);
-  const int T = py_clampi(frames[b], 1, Tmax);
+  const int T = (int)ft_item_len(frames, b, 1, Tmax, nullptr);
   const float* lv = lo_v + (long)b * Tmax * N;
   const float* lu = lo_u + (long)b * Tmax;
   unsigned short* bk = back + (long)b * Tmax * S;

@@ -28,16 +28,6 @@ constexpr int kTile = 1024;                 // outputs per workgroup: 256 thread
 constexpr int kMaxRate = 1024;              // max(up, down) after the gcd
 constexpr size_t kLdsBudget = 65536;
 
-// the length of item b clamped into [0, Lmax]; one thread of the item raises err
-__device__ __forceinline__ long rs_item_len(const long* __restrict__ len, int b, long Lmax, int* err, bool first) {
-  long L = len[b];
-  if (L < 0 || L > Lmax) {
-    if (err && first) *err = 1;
-    L = L < 0 ? 0 : Lmax;
-  }
-  return L;
-}
-
 // taps per phase, the table's (odd) row stride, and the input window of one tile in samples (a multiple of 4)
 struct RsGeom { int T, Tp, W, tabN; };
 __host__ __device__ inline RsGeom rs_geom(int up, int down, int half) {
@@ -58,7 +48,7 @@ __global__ __launch_bounds__(256) void ft_resample_kernel(const float* __restric
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int b = blockIdx.y, tid = threadIdx.x;
   const bool first = blockIdx.x == 0 && tid == 0;
-  const long L = rs_item_len(len, b, Lmax, err, first);
+  const long L = ft_item_len(len, b, 0, Lmax, first ? err : nullptr);
   const long nout = (L * up + down - 1) / down;
   if (first) out_len[b] = nout;
   const long n0 = (long)blockIdx.x * kTile, j0 = n0 + tid * 4;
@@ -140,7 +130,7 @@ __global__ __launch_bounds__(256) void ft_resample_copy_kernel(const float* __re
                                                                long* __restrict__ out_len, int* err) {
   const int b = blockIdx.y;
   const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-  const long L = rs_item_len(len, b, Lmax, err, first);
+  const long L = ft_item_len(len, b, 0, Lmax, first ? err : nullptr);
   if (first) out_len[b] = L;
   const long j = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (j >= ldy) return;

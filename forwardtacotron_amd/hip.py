@@ -206,6 +206,27 @@ def linear_multi_fwd(x: torch.Tensor, ws: List[torch.Tensor], biases: Optional[L
     return y
 
 
+# every batch-independent GEMM is rounded like a launch over this many rows (the 128 x 128 tile), whatever the batch holds
+AS_ROWS = 1 << 20
+_as_operands = {}
+
+
+def linear_fwd_as(x: torch.Tensor, ldx: int, w: torch.Tensor, rows: int, in_f: int, alloc=torch.empty) -> torch.Tensor:
+    """y [rows, out_f] = x (read with a row stride of ldx floats, so rows may overlap) * w^T, w [out_f, in_f], on the
+    kernel a launch over AS_ROWS rows takes (ft_linear_multi_fwd_as with one weight): the kernel, and with it the
+    rounding, does not depend on `rows`, so a row alone gives the bits it gives inside any batch.  The operand arrays
+    are a pure function of (w.data_ptr(), out_f) and are kept per such pair."""
+    out_f = int(w.shape[0])
+    ops = _as_operands.get((w.data_ptr(), out_f))
+    if ops is None:
+        arrs = (_ptr_array([w]), (ctypes.c_int * 1)(0), (ctypes.c_int * 1)(out_f))
+        ops = _as_operands[(w.data_ptr(), out_f)] = tuple(ctypes.cast(a, c_void_p) for a in arrs) + (arrs,)
+    y = alloc(rows, out_f, dtype=torch.float32, device=x.device)
+    _lib.call('ft_linear_multi_fwd_as', x.data_ptr(), ldx, 1, ops[0], None, y.data_ptr(), out_f, ops[1], ops[2], rows, in_f,
+              AS_ROWS, _stream())
+    return y
+
+
 # Data gradients contract over the OUTPUT features, which are the slow index of torch's [out,in] weights.  The
 # bf16-split MFMA kernel wants the contraction index contiguous in both operands, so the (small) weight is transposed
 # first and the product runs in the NT form; NT_GRADS = False keeps the [K][N] form on the f32 MFMA kernel.

@@ -10,13 +10,13 @@ preprocess.py:90, where `self.pitch_extractor(y)` follows `wav_to_mel(y)` and it
     write_raw_pitch(res, item_ids, paths.raw_pitch)      # the files pitch_energy.extract_pitch_energy reads
 
 HIP device only: without a device the constructor raises FtError.  extract_batch is three launches -- ft_pyin_cmnd,
-ft_pyin_observe, ft_pyin_viterbi (csrc/ft_pitch.hip) -- behind the gathering of the wavs; nothing is sized from device
-values and, with the lengths on the device or on the host, nothing synchronises.  The algorithm is probabilistic YIN
-(Mauch & Dixon 2014) with librosa.pyin's documented defaults: n_thresholds=100, beta_parameters=(2, 18),
-boltzmann_parameter=2, resolution=0.1, max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01, win_length =
-frame_length // 2, center=True with zero padding.  Semantics are in include/fwdtaco_hip.h and DESIGN.md section 7; the
-float64 and fp32 restatements the tests compare against are tests/pyin_cpu.py.  pyin_tables (the host tables and the
-derived sizes) needs no device.
+ft_pyin_observe, ft_pyin_viterbi (csrc/ft_pitch.hip) -- behind the intake of the ragged batch (ragged.py, which states
+the contract; here a device-side length is clamped silently, so lengths on the device or on the host never
+synchronise).  The algorithm is probabilistic YIN (Mauch & Dixon 2014) with librosa.pyin's documented defaults:
+n_thresholds=100, beta_parameters=(2, 18), boltzmann_parameter=2, resolution=0.1, max_transition_rate=35.92,
+switch_prob=0.01, no_trough_prob=0.01, win_length = frame_length // 2, center=True with zero padding.  Semantics are
+in include/fwdtaco_hip.h and DESIGN.md section 7; the float64 and fp32 restatements the tests compare against are
+tests/pyin_cpu.py.  pyin_tables (the host tables and the derived sizes) needs no device.
 
 PARITY UNPINNED against the reference, as for the rest of the audio front end: librosa is not installed here.  What is
 pinned is the written definition, and it differs from librosa.pyin on purpose in three places: the difference function
@@ -37,6 +37,7 @@ import torch
 
 from . import _lib
 from . import hip as H
+from . import ragged
 
 Wav = Union[np.ndarray, torch.Tensor]
 
@@ -179,54 +180,19 @@ class LibrosaPitchExtractor:
 
     # ------------------------------------------------------------------------------------------------
     def _gather(self, wavs: Sequence[Wav]):
-        """list of 1-D wavs -> (wav [B, ld] zero-padded device tensor, lens [B] int64 device tensor, Lmax)"""
-        if len(wavs) == 0:
-            raise _lib.FtError('extract_batch: an empty batch')
-        lens = []
-        for y in wavs:
-            if getattr(y, 'ndim', None) != 1:
-                raise _lib.FtError('extract_batch: every wav must be a 1-D array or tensor')
-            lens.append(int(y.shape[0]))
-        Lmax = max(lens)
-        ld = max(1, Lmax)
-        if all(isinstance(y, np.ndarray) for y in wavs):
-            host = np.zeros((len(wavs), ld), dtype=np.float32)
-            for b, y in enumerate(wavs):
-                host[b, :lens[b]] = y
-            wav = torch.from_numpy(host).to(self.device)
-        else:
-            wav = torch.zeros(len(wavs), ld, dtype=torch.float32, device=self.device)
-            for b, y in enumerate(wavs):
-                wav[b, :lens[b]] = torch.as_tensor(y).to(self.device, torch.float32)
-        return wav, torch.tensor(lens, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True), Lmax
+        """ragged.gather_wavs with this extractor's parameters (the stage tests and tools/bench_pitch.py start here)"""
+        return ragged.gather_wavs(wavs, self.device, 'extract_batch', alloc=_alloc)
 
     def _input(self, wav, wav_len):
-        if wav_len is None:
-            if isinstance(wav, (np.ndarray, torch.Tensor)):
-                raise _lib.FtError('extract_batch: a padded [B, L] batch needs wav_len; without it pass a list of 1-D wavs')
-            return self._gather(wav)
-        if isinstance(wav, np.ndarray):
-            wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
-        if not isinstance(wav, torch.Tensor) or wav.dim() != 2 or wav.dtype != torch.float32:
-            raise _lib.FtError('extract_batch: with wav_len, wav must be a float32 [B, L] tensor')
-        B, L = wav.shape
-        if B < 1:
-            raise _lib.FtError('extract_batch: an empty batch')
-        if not isinstance(wav_len, torch.Tensor):
-            wav_len = torch.as_tensor(np.asarray(wav_len))
-        if wav_len.dim() != 1 or wav_len.numel() != B or wav_len.dtype != torch.int64:
-            raise _lib.FtError(f'extract_batch: wav_len must be int64 [B = {B}]')
-        wav = wav.to(self.device)
-        if L == 0 or not wav.is_contiguous():
-            buf = _alloc(B, max(1, L), device=self.device)           # columns >= L are never read: every len <= L
+        """the intake of ragged.py (a device-side wav_len gets no flag: the kernels clamp it silently), with a one-column
+        buffer for a padded batch of L == 0"""
+        wav, lens, L, _ = ragged.intake(wav, wav_len, self.device, 'extract_batch', flag=False, alloc=_alloc)
+        if wav.shape[1] == 0 or not wav.is_contiguous():
+            buf = _alloc(len(wav), max(1, L), device=self.device)    # columns >= L are never read: every len <= L
             if L:
                 buf.copy_(wav)
             wav = buf
-        if not wav_len.is_cuda:
-            if int(wav_len.min()) < 0 or int(wav_len.max()) > L:
-                raise _lib.FtError(f'extract_batch: every wav_len must be in [0, L = {L}] (got {wav_len.tolist()})')
-            wav_len = wav_len.pin_memory().to(self.device, non_blocking=True)
-        return wav, wav_len.contiguous(), L
+        return wav, lens, L
 
     def stages(self, wav: torch.Tensor, lens: torch.Tensor, Lmax: int, debug: bool = False) -> Dict[str, torch.Tensor]:
         """the three launches on a gathered batch; returns every intermediate (dn, frames, lo_v, lo_u, vp, state, score,

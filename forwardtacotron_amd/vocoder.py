@@ -16,8 +16,9 @@ phase update and the mel pseudo-inverse steps are small element-wise kernels (cs
 A RAGGED BATCH goes through `griffinlim_batch(mel, mel_len)` (generate_batch's 'mel_post' and 'mel_len'): every item
 sits at a fixed stride of Tcap rows in one packed buffer (`gl_batch_geometry`), so each transform of every iteration is
 ONE GEMM for the whole batch and each element-wise step ONE launch (the *_ragged kernels of csrc/ft_dsp.hip, lengths
-read on the device).  Every GEMM of that path is `ft_linear_multi_fwd_as` with the fixed `_AS_ROWS`, so the kernel --
-and the rounding -- never depends on the batch: an item's samples are bit-identical alone and inside any batch.
+read on the device).  Every GEMM of that path is `hip.linear_fwd_as`, whose kernel -- and the rounding -- never depends
+on the batch: an item's samples are bit-identical alone and inside any batch.  How mel_len is taken from the host or
+the device is the contract of ragged.py.
 
 PARITY UNPINNED against the reference: librosa is not installed in this image and the reference ships no audio
 fixture.  The oracle is oracle/gl_oracle.py (numpy, FFT-based -- an independent route to the same published algorithm);
@@ -26,7 +27,6 @@ tests/test_gpu_vocoder.py compares step by step.  Differences from librosa that 
     followed by `nnls_iter` projected-gradient steps (GEMMs), see the oracle's header;
   * the random initial phases come from numpy's default_rng(seed) on the host (librosa: default_rng(random_state)).
 """
-import ctypes
 import os
 from typing import Any, Dict, Optional, Union
 
@@ -35,6 +35,7 @@ import torch
 
 from . import _lib
 from . import hip as H
+from . import ragged
 
 
 def _hz_to_mel(f):
@@ -58,10 +59,6 @@ def slaney_mel_basis(sr: int, n_fft: int, n_mels: int, fmin: float, fmax: float)
     down = (pts[2:, None] - freqs[None, :]) / (pts[2:] - pts[1:-1])[:, None]
     w = np.clip(np.minimum(up, down), 0, None)
     return w * (2.0 / (pts[2:] - pts[:-2]))[:, None]
-
-
-# every GEMM of the batched path is rounded like a launch over this many rows (the 128 x 128 tile), whatever the batch holds
-_AS_ROWS = 1 << 20
 
 
 def _empty(*shape, dtype=torch.float32, device=None) -> torch.Tensor:
@@ -134,9 +131,11 @@ class GriffinLim:
         pinv[:F] = np.linalg.pinv(B)
         f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
         self.w_fwd, self.w_inv = f32(fwd), f32(inv)
+        self.w2 = f32(self.window ** 2)                                     # the batched overlap-add's fp32 squared window
         self.mel_basis, self.mel_basis_t, self.mel_pinv = f32(Bp), f32(Bp.T), f32(pinv)
         self.inv_lip = float(1.0 / np.linalg.norm(B, 2) ** 2)
         self._inv_wss: Dict[int, torch.Tensor] = {}
+        self._len_flag = ragged.LenFlag()                   # the pinned word a device-side mel_len check reports through
 
     @classmethod
     def from_config(cls, config: Dict[str, Any], **kw) -> 'GriffinLim':
@@ -233,61 +232,28 @@ class GriffinLim:
         return self.griffinlim_from_stft(self.mel_to_stft(mel), n_iter, init_u, seed)
 
     # ---- ragged batch --------------------------------------------------------------------------------
-    def _batch_ctx(self):
-        """operands of the forced-tile GEMMs (host arrays of device pointers) and the fp32 squared window"""
-        ctx = getattr(self, '_bctx', None)
-        if ctx is None:
-            if self.n_fft % 8:
-                raise _lib.FtError('griffinlim_batch: n_fft must be a multiple of 8')
-            mk = lambda w: (H._ptr_array([w]), (ctypes.c_int * 1)(0), (ctypes.c_int * 1)(int(w.shape[0])), w)
-            ctx = {k: mk(w) for k, w in (('pinv', self.mel_pinv), ('basis', self.mel_basis), ('basis_t', self.mel_basis_t),
-                                         ('fwd', self.w_fwd), ('inv', self.w_inv))}
-            ctx['w2'] = torch.from_numpy((self.window ** 2).astype(np.float32)).to(self.device)
-            ctx['bad_host'] = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._bctx = ctx
-        return ctx
-
-    def _gemm_as(self, x: torch.Tensor, ldx: int, key: str, rows: int, in_f: int) -> torch.Tensor:
-        """y [rows, out_f] = x (row stride ldx) * w^T on the kernel a launch over _AS_ROWS rows takes"""
-        wp, col0, outf, w = self._batch_ctx()[key]
-        y = _alloc(rows, int(w.shape[0]), device=self.device)
-        c = ctypes.c_void_p
-        _lib.call('ft_linear_multi_fwd_as', x.data_ptr(), ldx, 1, ctypes.cast(wp, c), None, y.data_ptr(), int(w.shape[0]),
-                  ctypes.cast(col0, c), ctypes.cast(outf, c), rows, in_f, _AS_ROWS, H._stream())
-        return y
-
     def _batch_lens(self, what: str, mel_len: torch.Tensor, B: int, Tmax: int):
-        """-> (mel_len on the device, error flag or None).  A host-side mel_len is checked here, before any launch; a
-        device-side one gets a zeroed device flag that the kernels raise."""
-        if not isinstance(mel_len, torch.Tensor) or mel_len.dim() != 1 or mel_len.numel() != B \
-                or mel_len.dtype != torch.int64:
-            raise _lib.FtError(f'{what}: mel_len must be an int64 tensor [B = {B}]')
+        """-> (mel_len on the device, error flag or None, the message of a raised flag): ragged.device_lens for
+        1 <= mel_len[b] <= Tmax"""
+        if self.n_fft % 8:
+            raise _lib.FtError('griffinlim_batch: n_fft must be a multiple of 8')
+        if not isinstance(mel_len, torch.Tensor):
+            raise _lib.FtError(f'{what}: mel_len must be an int64 tensor')
         if B < 1 or Tmax < 1:
             raise _lib.FtError(f'{what}: an empty batch')
-        if not mel_len.is_cuda:
-            if int(mel_len.min()) < 1 or int(mel_len.max()) > Tmax:
-                raise _lib.FtError(f'{what}: every mel_len must be in [1, Tmax = {Tmax}] (got {mel_len.tolist()})')
-            return mel_len.pin_memory().to(self.device, non_blocking=True), None
-        return mel_len.contiguous(), torch.zeros(1, dtype=torch.int32, device=self.device)
-
-    def _batch_raise(self, what: str, err: Optional[torch.Tensor], Tmax: int) -> None:
-        if err is not None:
-            bad = self._batch_ctx()['bad_host']
-            bad.copy_(err, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            if int(bad[0]) != 0:
-                raise _lib.FtError(f'{what}: every mel_len must be in [1, Tmax = {Tmax}]')
+        return ragged.device_lens(mel_len, B, 1, Tmax, what, 'mel_len', 'Tmax', self.device) \
+            + (ragged.range_message(what, 'mel_len', 1, Tmax, 'Tmax'),)
 
     def _mel_to_stft_batch(self, mel: torch.Tensor, ml: torch.Tensor, err: Optional[torch.Tensor]) -> torch.Tensor:
         B, C, Tmax = mel.shape
         g = gl_batch_geometry(B, Tmax, self.n_fft, self.hop)
         rows, st = g['rows'], H._stream()
         M = H.gl_exp_transpose_ragged(mel, ml, g['Tcap'], err, alloc=_alloc)          # [rows, C], zero rows at n >= N_b
-        X = H.gl_relu(self._gemm_as(M, C, 'pinv', rows, C))                           # clipped least squares [rows, Fp]
+        X = H.gl_relu(H.linear_fwd_as(M, C, self.mel_pinv, rows, C, _alloc))         # clipped least squares [rows, Fp]
         for _ in range(self.nnls_iter):                                              # row-local: zero rows stay zero
-            R = self._gemm_as(X, self.Fp, 'basis', rows, self.Fp)                     # [rows, n_mels]
+            R = H.linear_fwd_as(X, self.Fp, self.mel_basis, rows, self.Fp, _alloc)        # [rows, n_mels]
             _lib.call('ft_sub', R.data_ptr(), M.data_ptr(), R.data_ptr(), R.numel(), st)
-            G = self._gemm_as(R, C, 'basis_t', rows, C)                               # [rows, Fp]
+            G = H.linear_fwd_as(R, C, self.mel_basis_t, rows, C, _alloc)                  # [rows, Fp]
             _lib.call('ft_nnls_step', X.data_ptr(), G.data_ptr(), self.inv_lip, X.numel(), st)
         return X
 
@@ -304,9 +270,9 @@ class GriffinLim:
         """log-mel [B, n_mels, Tmax], mel_len int64 [B] -> magnitudes packed [B * Tcap, Fp] (item b's frame n at row
         b * Tcap + n, Tcap from gl_batch_geometry); the rows n >= mel_len[b] of an item are all zero"""
         mel = self._check_mel_batch('mel_to_stft_batch', mel)
-        ml, err = self._batch_lens('mel_to_stft_batch', mel_len, mel.shape[0], mel.shape[2])
+        ml, err, msg = self._batch_lens('mel_to_stft_batch', mel_len, mel.shape[0], mel.shape[2])
         X = self._mel_to_stft_batch(mel, ml, err)
-        self._batch_raise('mel_to_stft_batch', err, mel.shape[2])
+        self._len_flag.check(err, msg)
         return X
 
     def _gl_from_stft_batch(self, S, ml, B, Tmax, n_iter, init_u, seed, err) -> Dict[str, torch.Tensor]:
@@ -317,17 +283,16 @@ class GriffinLim:
             raise _lib.FtError(f'griffinlim_from_stft_batch: expected S [B * Tcap = {rows}, Fp = {Fp}], got {tuple(S.shape)}')
         if init_u is None and seed is None:
             seed = int.from_bytes(os.urandom(8), 'little')
-        w2 = self._batch_ctx()['w2']
         proj = H.gl_init_ragged(S, ml, B, Tcap, Tmax, u=init_u, seed=seed or 0, err=err, alloc=_alloc)
         tprev = _alloc(rows, 2 * Fp, device=self.device)
         alpha = self.momentum / (1.0 + self.momentum)
-        ola = lambda fr, as_wav: H.overlap_add_ragged(fr, w2, ml, B, Tcap, Tmax, self.n_fft, self.hop, as_wav, alloc=_alloc)
+        ola = lambda fr, as_wav: H.overlap_add_ragged(fr, self.w2, ml, B, Tcap, Tmax, self.n_fft, self.hop, as_wav, alloc=_alloc)
         for it in range(n_iter):
-            frames = self._gemm_as(proj, 2 * Fp, 'inv', rows, 2 * Fp)                 # inverse STFT of every item
+            frames = H.linear_fwd_as(proj, 2 * Fp, self.w_inv, rows, 2 * Fp, _alloc)        # inverse STFT of every item
             ypad = ola(frames, False)
-            rebuilt = self._gemm_as(ypad, self.hop, 'fwd', rows, self.n_fft)          # frames read in place, ldx = hop
+            rebuilt = H.linear_fwd_as(ypad, self.hop, self.w_fwd, rows, self.n_fft, _alloc)     # in place, ldx = hop
             H.gl_phase_ragged(rebuilt, tprev, S, ml, proj, B, Tcap, Tmax, alpha, it > 0)
-        wav = ola(self._gemm_as(proj, 2 * Fp, 'inv', rows, 2 * Fp), True)
+        wav = ola(H.linear_fwd_as(proj, 2 * Fp, self.w_inv, rows, 2 * Fp, _alloc), True)
         return {'wav': wav, 'wav_len': (ml - 1) * self.hop}
 
     def griffinlim_from_stft_batch(self, S: torch.Tensor, mel_len: torch.Tensor, Tmax: int, n_iter: int = 32,
@@ -338,9 +303,9 @@ class GriffinLim:
         / (2 pi) in the same layout (rows n >= mel_len[b] are ignored); without it they are drawn on the device from
         (seed, frame, bin) -- see griffinlim_batch."""
         B = int(mel_len.numel()) if isinstance(mel_len, torch.Tensor) else 0
-        ml, err = self._batch_lens('griffinlim_from_stft_batch', mel_len, B, int(Tmax))
+        ml, err, msg = self._batch_lens('griffinlim_from_stft_batch', mel_len, B, int(Tmax))
         out = self._gl_from_stft_batch(S, ml, B, int(Tmax), n_iter, init_u, seed, err)
-        self._batch_raise('griffinlim_from_stft_batch', err, int(Tmax))
+        self._len_flag.check(err, msg)
         return out
 
     def griffinlim_batch(self, mel: torch.Tensor, mel_len: torch.Tensor, n_iter: int = 32, seed: Optional[int] = None,
@@ -362,18 +327,16 @@ class GriffinLim:
         seeds with equal high words -- seed=1 and seed=2 -- give the same phases permuted by an XOR of the index
         (csrc/ft_common.h: the seed contract of ft_hash32).
 
-        Nothing is sized from device values and, with mel_len on the host, nothing synchronises.  A mel_len that lives
-        on the device is range-checked on the device (lengths are clamped inside the kernels, so nothing indexes out of
-        bounds): the FtError is raised at the end of the call, after one synchronisation, and the flag travels through
-        ONE pinned host word kept on this object -- so one GriffinLim must not run the batched calls with a device-side
-        mel_len from two threads or on two streams at once (a host-side mel_len is checked up front and has no such
-        limit)."""
+        The lengths follow the contract of ragged.py: a host-side mel_len is checked up front and nothing synchronises;
+        a device-side one is clamped inside the kernels and its FtError is raised at the end of the call, after one
+        synchronisation, through ONE pinned host word kept on this object -- so one GriffinLim must not run the batched
+        calls with a device-side mel_len from two threads or on two streams at once."""
         mel = self._check_mel_batch('griffinlim_batch', mel)
         B, _, Tmax = mel.shape
-        ml, err = self._batch_lens('griffinlim_batch', mel_len, B, Tmax)
+        ml, err, msg = self._batch_lens('griffinlim_batch', mel_len, B, Tmax)
         S = self._mel_to_stft_batch(mel, ml, err)
         out = self._gl_from_stft_batch(S, ml, B, Tmax, n_iter, init_u, seed, err)
-        self._batch_raise('griffinlim_batch', err, Tmax)
+        self._len_flag.check(err, msg)
         return out
 
 

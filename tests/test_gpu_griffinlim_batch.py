@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from poison import poison as _poison
+
 pytestmark = pytest.mark.gpu
 
 LENS = [5, 64, 1, 37, 2, 3]
@@ -92,11 +94,6 @@ def project():
 
 def _item(out, b):
     return out['wav'][b, :int(out['wav_len'][b])]
-
-
-def _poison(*shape, dtype=torch.float32, device=None):
-    t = torch.empty(*shape, dtype=dtype, device=device)
-    return t.fill_(float('nan')) if dtype.is_floating_point else t.fill_(-123456789)
 
 
 # ---- 1. oracle -------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import mel_cpu as R
+from poison import poison as _poison
 
 pytestmark = pytest.mark.gpu
 
@@ -128,11 +129,6 @@ def test_all_zero_item_under_peak_norm_is_nan_like_numpy(items):
     quiet = _host(_dsp().preprocess_batch([z]))                     # peak_norm off: nothing is divided
     assert not quiet['wav'].any()                                   # every mel value is the clip's log, to the two logs' rounding
     assert np.abs(quiet['mel'][0] - np.log(1e-5)).max() <= 5 * float(np.spacing(np.float32(8)))
-
-
-def _poison(*shape, dtype=torch.float32, device=None):
-    t = torch.empty(*shape, dtype=dtype, device=device)
-    return t.fill_(float('nan')) if dtype.is_floating_point else t.fill_(-123456789)
 
 
 def test_item_alone_equals_item_in_batch_and_padding_is_exact(items, monkeypatch):

@@ -33,6 +33,7 @@ import pytest
 import torch
 
 import pyin_cpu as R
+from poison import poison as _poison
 
 pytestmark = pytest.mark.gpu
 
@@ -72,13 +73,6 @@ def run(name, j):
 @pytest.fixture(scope='module', params=['A', 'B'])
 def name(request):
     return request.param
-
-
-def _poison(*shape, dtype=torch.float32, device=None):
-    t = torch.empty(*shape, dtype=dtype, device=device)
-    if dtype.is_floating_point:
-        return t.fill_(float('nan'))
-    return t.fill_(255) if dtype == torch.uint8 else t.fill_(-123456789)
 
 
 # ---- stage 1 ----------------------------------------------------------------------------------------------------------

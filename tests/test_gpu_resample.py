@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import resample_cpu as R
+from poison import poison as _poison
 
 pytestmark = pytest.mark.gpu
 
@@ -86,11 +87,6 @@ def worst_ratio(y, y64, S, T_n):
     err, bnd = np.abs(y.astype(np.float64) - y64), R.bound(S, T_n)
     assert (err[bnd == 0] == 0).all()
     return float((err[bnd > 0] / bnd[bnd > 0]).max()) if (bnd > 0).any() else 0.0
-
-
-def _poison(*shape, dtype=torch.float32, device=None):
-    t = torch.empty(*shape, dtype=dtype, device=device)
-    return t.fill_(float('nan')) if dtype.is_floating_point else t.fill_(-123456789)
 
 
 # ---- 1. the float64 restatement, lengths, padding ----------------------------------------------------------------

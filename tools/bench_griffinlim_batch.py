@@ -138,26 +138,26 @@ def main():
     M = hip.gl_exp_transpose_ragged(mel, ml_dev, Tcap)
     proj = hip.gl_init_ragged(S, ml_dev, B, Tcap, Tmax, seed=a.seed)
     tprev = torch.zeros_like(proj)
-    frames = gl._gemm_as(proj, 2 * Fp, 'inv', rows, 2 * Fp)
-    w2 = gl._batch_ctx()['w2']
+    frames = hip.linear_fwd_as(proj, 2 * Fp, gl.w_inv, rows, 2 * Fp)
+    w2 = gl.w2
     ypad = hip.overlap_add_ragged(frames, w2, ml_dev, B, Tcap, Tmax, gl.n_fft, gl.hop)
-    rebuilt = gl._gemm_as(ypad, gl.hop, 'fwd', rows, gl.n_fft)
-    R = gl._gemm_as(S, Fp, 'basis', rows, Fp)
-    G = gl._gemm_as(R, gl.n_mels, 'basis_t', rows, gl.n_mels)
+    rebuilt = hip.linear_fwd_as(ypad, gl.hop, gl.w_fwd, rows, gl.n_fft)
+    R = hip.linear_fwd_as(S, Fp, gl.mel_basis, rows, Fp)
+    G = hip.linear_fwd_as(R, gl.n_mels, gl.mel_basis_t, rows, gl.n_mels)
     X = S.clone()
     st = hip._stream()
 
     def gemms_dft():
         for _ in range(a.n_iter):
-            gl._gemm_as(proj, 2 * Fp, 'inv', rows, 2 * Fp)
-            gl._gemm_as(ypad, gl.hop, 'fwd', rows, gl.n_fft)
-        gl._gemm_as(proj, 2 * Fp, 'inv', rows, 2 * Fp)
+            hip.linear_fwd_as(proj, 2 * Fp, gl.w_inv, rows, 2 * Fp)
+            hip.linear_fwd_as(ypad, gl.hop, gl.w_fwd, rows, gl.n_fft)
+        hip.linear_fwd_as(proj, 2 * Fp, gl.w_inv, rows, 2 * Fp)
 
     def gemms_nnls():
-        gl._gemm_as(M, gl.n_mels, 'pinv', rows, gl.n_mels)
+        hip.linear_fwd_as(M, gl.n_mels, gl.mel_pinv, rows, gl.n_mels)
         for _ in range(gl.nnls_iter):
-            gl._gemm_as(S, Fp, 'basis', rows, Fp)
-            gl._gemm_as(R, gl.n_mels, 'basis_t', rows, gl.n_mels)
+            hip.linear_fwd_as(S, Fp, gl.mel_basis, rows, Fp)
+            hip.linear_fwd_as(R, gl.n_mels, gl.mel_basis_t, rows, gl.n_mels)
 
     def elementwise():
         hip.gl_exp_transpose_ragged(mel, ml_dev, Tcap)

@@ -79,23 +79,17 @@ def main():
     res['preprocess_batch_ms'] = timed(lambda: dsp.preprocess_batch(wavs), a.iters, a.warmup)
 
     # the stages alone, on the buffers of one call
-    wav, lens, Lmax = dsp._gather(wavs)
+    wav, lens, Lmax = dsp._wavs(wavs)
     ld = wav.shape[1]
     Tmax, Tcap = 1 + Lmax // hop, (ld + n_fft + hop - 1) // hop
     rows = B * Tcap
     tp = H.wav_trim_peak(wav, lens, Lmax, True, dsp.trim_silence_top_db, 0, hop)
     packed, _ = H.wav_pack(wav, tp, Tcap * hop, n_fft, False)
-    spec = torch.empty(rows, 2 * Fp, device='cuda')
-    import ctypes
-    from forwardtacotron_amd import _lib
-    from forwardtacotron_amd.audio import _AS_ROWS
-    cv = ctypes.c_void_p
 
     def gemm():
-        _lib.call('ft_linear_multi_fwd_as', packed.data_ptr(), hop, 1, ctypes.cast(dsp._w_ptr, cv), None, spec.data_ptr(),
-                  2 * Fp, ctypes.cast(dsp._col0, cv), ctypes.cast(dsp._outf, cv), rows, n_fft, _AS_ROWS, H._stream())
+        return H.linear_fwd_as(packed, hop, dsp.gl.w_fwd, rows, n_fft)
 
-    gemm()
+    spec = gemm()
     res['trim_peak_ms'] = timed(lambda: H.wav_trim_peak(wav, lens, Lmax, True, dsp.trim_silence_top_db, 0, hop),
                                 a.iters, a.warmup)
     res['pack_ms'] = timed(lambda: H.wav_pack(wav, tp, Tcap * hop, n_fft, False), a.iters, a.warmup)

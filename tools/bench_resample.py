@@ -81,7 +81,7 @@ def main():
         res = {'source_sr': src, 'up': up, 'down': down, 'batch': len(wavs)}
         res['resample_batch_ms'] = timed(lambda: dsp.resample_batch(wavs, src), a.iters, a.warmup)
 
-        wav, lens, Lmax = dsp._gather(wavs, for_stft=False)
+        wav, lens, Lmax = dsp._rs_input(wavs, None)[:3]
         tab, half = dsp._rs_table(up, down)
         ldy = (-((-Lmax * up) // down) + 3) // 4 * 4
         res['kernel_ms'] = timed(lambda: H.resample_poly_ragged(wav, lens, Lmax, tab, up, down, half, ldy), a.iters, a.warmup)
