@@ -2,6 +2,8 @@
 // ft_rnn_persist.hip: one-launch persistent forms).
 #pragma once
 #include "ft_common.h"
+#include "ft_rnn_plan.h"
+#include "fwdtaco_hip.h"
 
 constexpr int RLD = 20;     // LDS row stride of the 16x16 partial tiles
 constexpr int GCH = 8;      // K groups (16 k each) a wave keeps in registers
@@ -67,7 +69,7 @@ __device__ __forceinline__ int clamp_len(const long* lens, int b, int T) {
 // One-launch persistent recurrences (ft_rnn_persist.hip).  Return FT_OK if launched, -1 if the persistent form does
 // not apply (the caller then issues the per-step kernels).
 int ft_rnn_fwd_persistent(int G, RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream);
-// share of one XCD's CUs the persistent forward of this shape would hold (-1: it would not run persistent)
-double ft_rnn_fwd_xcd_fill(int G, int B, int T, int H, void* ws, size_t ws_bytes);
-double ft_rnn_bwd_xcd_fill(int G, int B, int T, int H, void* ws, size_t ws_bytes);
+// share of one XCD's CUs the persistent forward (backward != 0: BPTT) of this shape would hold (-1: it would not run
+// persistent)
+double ft_rnn_xcd_fill(int G, int backward, int B, int T, int H, void* ws, size_t ws_bytes);
 int ft_rnn_bwd_persistent(int G, RnnBwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream);

@@ -486,8 +486,8 @@ int rnn_layer_fwd(const float* x, int In, const float* const* wih, const float* 
   const int nc = T > 0 ? (T + cs - 1) / cs : 1;
   hipEvent_t ev0 = layer_event(0), ev1 = layer_event(1);
   // a recurrence that fills whole XCDs (the 512-wide LSTM) stops the dispatch of every other kernel while it is resident:
-  // chunks launched beside it would only run after it -- and it would wait for them (ft_rnn_fwd_xcd_fill)
-  const double fill = (nc >= 2 && side && gate) ? ft_rnn_fwd_xcd_fill(G, B, T, H, ws, ws_bytes) : -1.0;
+  // chunks launched beside it would only run after it -- and it would wait for them (ft_rnn_xcd_fill)
+  const double fill = (nc >= 2 && side && gate) ? ft_rnn_xcd_fill(G, 0, B, T, H, ws, ws_bytes) : -1.0;
   if (nc < 2 || !side || side == stream || !gate || !ev0 || !ev1 || fill < 0.0 || fill > 0.75) {
     int rc = project(0, 0, T, stream);
     if (rc == FT_OK) rc = project(1, 0, T, stream);

@@ -1311,10 +1311,13 @@ bool persistent_enabled() {
   return g_persistent == 1;
 }
 
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+// Everything a launch decides -- form, workspace carve, layout, demand, admission -- is ft_rnn_plan.h's, in plain C++;
+// here are the HIP calls around it.  The FT_RNN_* switches are read per launch (Switches: each at most once).
+using rnn_plan::Form;
+using rnn_plan::Switches;
+static_assert(rnn_plan::NSH == NSH && rnn_plan::CSTRIDE == CSTRIDE && rnn_plan::NFLAG == NFLAG && rnn_plan::NXCC == NXCC &&
+                  rnn_plan::MB16 == MB16 && rnn_plan::GCH == GCH, "ft_rnn_plan.h plans with the kernels' constants");
+const char* env_lookup(const char* name) { return getenv(name); }
 
 int device_cus() {
   static int cus = 0;
@@ -1327,52 +1330,10 @@ int device_cus() {
   return cus;
 }
 
-struct PersistWs {
-  float* xb;
-  unsigned* cnt;
-  size_t sync_bytes, xb_bytes, total_bytes;
-};
-// workspace = [arrival counters | flag words | XCC ids | exchange buffer (fp32 parities, granule parities)]; the sync region (and, for the all-gather
-// forms, the exchange buffer) is zeroed per call from the allocation's start (the fault word is NOT in here: it is the
-// device-global g_rnn_fault, which launches never touch)
-size_t sync_region_bytes(int ngrp) { return (size_t)ngrp * (NSH * CSTRIDE + NFLAG + NXCC) * sizeof(unsigned); }
-PersistWs carve_ws(void* ws, int ngrp, int K, int mb) {
-  PersistWs p;
-  p.sync_bytes = sync_region_bytes(ngrp);
-  p.cnt = (unsigned*)ws;
-  // two fp32 parities, then the granule area of the XCD-local split kernels (two parities of 8-byte granules)
-  p.xb_bytes = (size_t)3 * 2 * ngrp * (K / 4) * mb * 4 * sizeof(float);
-  p.xb = (float*)((char*)ws + p.sync_bytes);
-  p.total_bytes = p.sync_bytes + p.xb_bytes;
-  return p;
-}
-
-// reduce-scatter backward: xb[parity][group][consumer][producer][16 * mb]
-PersistWs carve_ws_rs(void* ws, int ngrp, int nchunks, int mb) {
-  PersistWs p;
-  p.sync_bytes = sync_region_bytes(ngrp);
-  p.cnt = (unsigned*)ws;
-  p.xb_bytes = (size_t)2 * ngrp * nchunks * nchunks * 16 * mb * sizeof(float);
-  p.xb = (float*)((char*)ws + p.sync_bytes);
-  p.total_bytes = p.sync_bytes + p.xb_bytes;
-  return p;
-}
-
-// Batch rows per workgroup of the forms that come in an 8-row variant (the 512-wide LSTM's forward and reduce-scatter
-// BPTT, the 256-wide GRU's forward and all-gather BPTT), for nd * ceil(B / 16) (direction, batch group) groups.  Every group runs on one XCD slot of its own, so with
-// fewer than 8 groups the 16-row form leaves slots idle (B = 32: 4 of 8); 8 rows give the same batch twice the groups,
-// each CU half the rows to load, multiply and update per step, with the same results bit for bit.  Only where the
-// 8-row groups still fit one per slot and are more of them.  The narrower GRUs (the predictors, H <= 128) stay on 16
-// rows: not measured.  FT_RNN_MB=16 (read per launch): always 16 rows.
-int rows_per_wg(int nd, int B) {
-  if (env_int("FT_RNN_MB", 8) == 16) return 16;
-  const int g16 = nd * ft_cdiv(B, 16), g8 = nd * ft_cdiv(B, 8);
-  return g16 < 8 && g8 <= 8 && g8 > g16 ? 8 : 16;
-}
-
 constexpr int MAX_DEV = 16;
 unsigned g_max_spins = MAX_SPINS_DEFAULT;
 long g_n_persistent = 0, g_n_refused = 0, g_n_waited = 0;
+int g_rotor = 0;            // groups the aligned layouts have placed so far: successive launches start on different slots
 
 int current_device() {
   int dev = 0;
@@ -1409,13 +1370,12 @@ std::vector<hipEvent_t> g_ev_pool[MAX_DEV];
 template <typename KernelT>
 double xcd_demand(KernelT kernel, int block, int wgs_per_slot) {
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) return -1.0;
-  if (per_cu > 2) per_cu = 2;      // stay well inside what the dispatcher really admits
-  return (double)wgs_per_slot / (per_cu * (device_cus() / 8.0));
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess) per_cu = 0;
+  return rnn_plan::demand(wgs_per_slot, per_cu, device_cus());
 }
 
 // true: admitted (call admitted_launch_done after the launch); false: does not fit beside what other streams may run
-bool admit(double d, hipStream_t stream) {
+bool admit(double d, hipStream_t stream, Switches& sw) {
   if (d < 0.0 || !ft_rnn_fault_word()) return false;
   const int dev = current_device();
   std::lock_guard<std::mutex> lk(g_adm_mu);
@@ -1430,40 +1390,18 @@ bool admit(double d, hipStream_t stream) {
     }
   }
   (void)hipGetLastError();         // hipErrorNotReady of a pending event is not an error
-  auto counts = [&](const Flight& f) {
-    if (f.stream == stream) return false;
-    for (hipStream_t j : f.joined_by)
-      if (j == stream) return false;
-    return true;
-  };
-  double others = 0.0;             // sum over other streams of their largest unfinished demand
-  for (size_t i = 0; i < fl.size(); ++i) {
-    if (!counts(fl[i])) continue;
-    bool first = true;
-    double mx = 0.0;
-    for (size_t j = 0; j < fl.size(); ++j)
-      if (fl[j].stream == fl[i].stream && counts(fl[j])) {
-        if (j < i) first = false;
-        if (fl[j].d > mx) mx = fl[j].d;
-      }
-    if (first) others += mx;
+  const rnn_plan::Admission a = rnn_plan::admission(fl, stream, d, sw[Switches::ADMIT_PCT] / 100.0);
+  if (a.verdict == rnn_plan::REFUSE) return false;      // does not fit the chip even alone: per-step kernels
+  // Not beside what the other streams may still be running: make THIS stream wait for those launches (device-side
+  // wait on their events; the host does not block) and launch afterwards.  Always the same kernel, whatever the
+  // timing -- a fallback to the per-step kernels here would make results depend on when the host happened to look
+  // (they round differently: f32 MFMA against the exact bf16 split) -- and waits only follow enqueue order, so they
+  // cannot form a cycle.
+  for (size_t i : a.wait_for) {
+    (void)hipStreamWaitEvent(stream, fl[i].ev, 0);
+    fl[i].joined_by.push_back(stream);
   }
-  const double scale = env_int("FT_RNN_ADMIT_PCT", 100) / 100.0;
-  if (d > 1.0 * scale) return false;             // does not fit the chip even alone: per-step kernels
-  const bool fits = others == 0.0 || d + others <= 0.75 * scale;
-  if (!fits) {
-    // Not beside what the other streams may still be running: make THIS stream wait for those launches (device-side
-    // wait on their events; the host does not block) and launch afterwards.  Always the same kernel, whatever the
-    // timing -- a fallback to the per-step kernels here would make results depend on when the host happened to look
-    // (they round differently: f32 MFMA against the exact bf16 split) -- and waits only follow enqueue order, so they
-    // cannot form a cycle.
-    for (Flight& f : fl)
-      if (counts(f)) {
-        (void)hipStreamWaitEvent(stream, f.ev, 0);
-        f.joined_by.push_back(stream);
-      }
-    ++g_n_waited;
-  }
+  if (a.verdict == rnn_plan::ADMIT_AFTER_WAIT) ++g_n_waited;
   return true;
 }
 
@@ -1482,274 +1420,78 @@ void admitted_launch_done(double d, hipStream_t stream) {
   ++g_n_persistent;
 }
 
-// Grid layout of a persistent launch.  The 1-D grid is 8 x per: the decode hands XCD slot x the work items
-// [x*per, (x+1)*per).  ALIGNED: per = whole (direction, batch group) groups, so that a group's hand-off stays inside
-// one XCD (the XCD-local protocol then applies; surplus workgroups of the larger grid exit at once); successive
-// launches start on different slots.  SPREAD: per = ceil(total / 8), groups straddle XCDs, agent-scope protocol only.
-// The aligned layout is tried first; the spread one only runs when the aligned per-XCD demand exceeds a whole XCD (admit()
-// makes a launch WAIT for conflicting ones rather than refuse it, so a demand <= 1 is always taken as aligned).
-struct Layout {
-  int grid, per, xcd_off, aligned;
-};
-Layout layout_aligned(const Geom& geo) {
-  static int rotor = 0;
-  Layout l = {0, 0, 0, 0};
-  if (!geo.xcd_aware || !geo.sig_per_wave || !env_int("FT_RNN_XCDALIGN", 1) || geo.nchunks > NXCC) return l;
-  const int ngroups = geo.total / geo.nchunks;
-  l.per = geo.nchunks * ft_cdiv(ngroups, 8);
-  l.grid = 8 * l.per;
-  l.xcd_off = rotor & 7;
-  l.aligned = 1;
-  rotor += ngroups < 8 ? ngroups : 8;
-  return l;
-}
-Layout layout_spread(const Geom& geo) {
-  Layout l = {0, 0, 0, 0};
-  l.per = ft_cdiv(geo.total, 8);
-  l.grid = 8 * l.per;
-  return l;
-}
-
-// the kernel a launch picked, for the FT_RNN_DEBUG line: kind "fwd" <G, NW, B3, UB, BC, MB>, "bwd" (all-gather)
-// <G, NW, GW, B3, MB>, "bwd_rs" (reduce-scatter) <G, NW, NT, MB> with the unused slots -1; gran: the kernel has the
-// granule form of the XCD-local hand-off (the others hand over through flag words there)
-struct FormTag {
-  const char* kind;
-  int v[6];
-  int gran;
-};
-
-// picks the layout, checks admission, fills geo; -1.0 = not admitted in any layout
-template <typename KernelT>
-double plan_launch(KernelT kernel, int block, Geom& geo, int& grid, hipStream_t stream, const FormTag& form) {
-  const Layout cand[2] = {layout_aligned(geo), layout_spread(geo)};
-  for (int i = 0; i < 2; ++i) {
-    if (cand[i].grid == 0) continue;
-    const double d = xcd_demand(kernel, block, cand[i].per);
-    const bool ok = d <= 1.0 && admit(d, stream);
-    const int local_ok = cand[i].aligned && env_int("FT_RNN_LOCAL", 1);
-    const int gran = env_int("FT_RNN_GRANULES", 1), fast = env_int("FT_RNN_FAST_CELL", 1);
+// The one launcher: picks the layout (aligned first), checks admission, fills the kernel's Geom, zeroes the workspace's
+// start and launches; -1 = not admitted in any layout (the caller issues the per-step kernels).
+template <typename KernelT, typename ArgsT>
+int launch_persist(KernelT kernel, const char* what, const ArgsT& a, const Form& f, Switches& sw, void* ws,
+                   hipStream_t stream) {
+  const rnn_plan::Layout cand[2] = {rnn_plan::layout_aligned(f, sw, g_rotor), rnn_plan::layout_spread(f)};
+  for (const rnn_plan::Layout& l : cand) {
+    if (l.grid == 0) continue;
+    const double d = xcd_demand(kernel, f.threads, l.per);
+    const bool ok = d <= 1.0 && admit(d, stream, sw);
+    const int local_ok = l.aligned && sw[Switches::LOCAL];
+    const int gran = sw[Switches::GRANULES], fast = sw[Switches::FAST_CELL];
     // (the hand-off named here is the one the groups take from step 2 on IF their workgroups landed in one XCD;
     //  ft_rnn_mode_counts tells how many did)
-    if (env_int("FT_RNN_DEBUG", 0))
+    if (sw[Switches::DEBUG])
       fprintf(stderr,
               "[ft_rnn] %s<%d,%d,%d,%d,%d,%d> block %d total %d nchunks %d: %s layout, %d workgroups per XCD slot, demand %.3f -> %s; "
               "hand-off %s, cell %s\n",
-              form.kind, form.v[0], form.v[1], form.v[2], form.v[3], form.v[4], form.v[5], block, geo.total, geo.nchunks,
-              cand[i].aligned ? "aligned" : "spread", cand[i].per, d, ok ? "admitted" : "refused",
-              !local_ok ? "agent" : (form.gran && gran ? "local-granules" : "local-flags"), fast ? "fast" : "exact");
+              rnn_plan::kind_name(f.kind), f.v[0], f.v[1], f.v[2], f.v[3], f.v[4], f.v[5], f.threads, f.total, f.nchunks,
+              l.aligned ? "aligned" : "spread", l.per, d, ok ? "admitted" : "refused",
+              !local_ok ? "agent" : (f.gran && gran ? "local-granules" : "local-flags"), fast ? "fast" : "exact");
     if (!ok) continue;
-    grid = cand[i].grid;
-    geo.xcd_off = cand[i].xcd_off;
-    geo.local_ok = local_ok;
-    geo.gran = gran;
-    geo.fast = fast;
-    return d;
+    Geom geo = {f.nchunks, f.nbg, f.total, f.xcd_aware, f.sig_per_wave, l.xcd_off, g_max_spins, local_ok, gran, fast};
+    // (no effect today: a kernel with BC > 2 is compiled without the granule hand-off -- GRAN in the kernel -- and never
+    //  reads geo.gran; kept so that the switch holds if the 4-block form gets granules)
+    if (f.kind == rnn_plan::FWD && f.v[4] > 2 && !sw[Switches::GRAN4]) geo.gran = 0;
+    unsigned* const cnt = (unsigned*)ws;
+    (void)hipMemsetAsync(cnt, 0, f.zero_bytes, stream);
+    hipLaunchKernelGGL(kernel, dim3(l.grid), dim3(f.threads), 0, stream, a, geo, (float*)((char*)ws + f.ws.sync_bytes), cnt,
+                       ft_rnn_fault_word(), (unsigned)f.ws.xb_bytes);
+    admitted_launch_done(d, stream);
+    return ft_check_launch(what);
   }
   ++g_n_refused;
-  return -1.0;
+  return -1;
 }
 
-// fill_probe (ft_rnn_fwd_xcd_fill): no launch -- report the share of an XCD's CUs the aligned layout of this kernel holds
-double* g_fill_probe = nullptr;
-
-template <int G, int NW, bool B3, int UB, int BC, int MB = MB16>
-int launch_fwd_persist(const RnnFwdArgs& a, Geom geo, const PersistWs& p, hipStream_t stream) {
-  if (g_fill_probe) {
-    const int ngroups = geo.total / geo.nchunks;
-    *g_fill_probe = xcd_demand(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>, NW * 64, geo.nchunks * ft_cdiv(ngroups, 8));
-    return FT_OK;
-  }
-  int grid = 0;
-  const double cus = plan_launch(ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>, NW * 64, geo, grid, stream,
-                                 FormTag{"fwd", {G, NW, B3, UB, BC, MB}, B3 && BC <= 2});
-  if (cus < 0.0) return -1;
-  // (no effect today: a kernel with BC > 2 is compiled without the granule hand-off -- GRAN in the kernel -- and never
-  //  reads geo.gran; kept so that the switch holds if the 4-block form gets granules)
-  if (BC > 2 && !env_int("FT_RNN_GRAN4", 1)) geo.gran = 0;
-  (void)hipMemsetAsync(p.cnt, 0, p.total_bytes, stream);
-  hipLaunchKernelGGL((ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb,
-                     p.cnt, ft_rnn_fault_word(), (unsigned)p.xb_bytes);
-  admitted_launch_done(cus, stream);
-  return ft_check_launch("rnn_fwd_persistent");
-}
-
-template <int G>
-int fwd_persistent(RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) {
-  if (!persistent_enabled() || !ws || a.T < 2) return -1;
-  const int H = a.H, B = a.B;
-  if (!a.vec || H % 16 != 0) return -1;
-  const int ngroups = H / 16;
-  int NW = ngroups > 16 ? 8 : 4;
-  // The 512-wide LSTM: a (direction, batch group) group must fit ONE XCD to hand over through its L2, i.e. at most 32
-  // workgroup-CUs.  Two forms do: (a) 16 units per 8-wave workgroup (32 workgroups, one per CU; 2 resident k-blocks per
-  // wave, granule hand-off) -- every CU then pulls the group's h once per step instead of twice (two 8-unit workgroups
-  // per CU: 64 KB per CU and step through one 64 B/clk path) -- and (b) 8 units per 4-wave workgroup (64 workgroups, two
-  // per CU; 4 resident blocks per wave, flag words).  Round 2 measured (a) at 5.65 us per step against 3.77: it spilled
-  // 57 registers.  With ONE MFMA site per (block, tile) for all hand-off protocols (round 3) it spills 4 and runs 3.51
-  // against 3.88 in isolation, 22.8 -> 22.3 ms per train step (profiles/r03_rnn_ab.txt).  FT_RNN_FWD_UB16=0: form (b).
-  const bool wide = NW == 8 && G == 4 && H / 8 > 32 && H % 32 == 0 && ft_cdiv(H / 32, 8) <= 2 && env_int("FT_RNN_B3", 1) &&
-                    env_int("FT_RNN_FWD_UB16", 1);
-  if (!wide && NW == 8 && G == 4 && H % 32 == 0 && ft_cdiv(H / 32, 4) <= 4 && env_int("FT_RNN_FWD_NW4", 1)) NW = 4;
-  if (ft_cdiv(ngroups, NW) > GCH) return -1;
-  const int bpw = H % 32 == 0 ? ft_cdiv(H / 32, NW) : 99;                 // 32-k blocks per wave in the split form
-  // matmul on the bf16 pipe (exact split): the 8-wave kernels keep at most 2 resident k-blocks per wave (BC), the 4-wave
-  // ones 4 -- a width beyond that (8 waves: H = 544 .. 1024) takes the f32 form, whose 8 k-groups per wave cover it
-  const bool b3 = bpw <= (NW == 8 ? 2 : 4) && env_int("FT_RNN_B3", 1);
-  // GRU, H = 256 (the trunk's two GRUs; the postnet's runs 841 steps): 8 waves with ONE resident k-block each and 16
-  // hidden units per workgroup -- 16 producers per group instead of 32, half the operand bytes per wave.  Same box,
-  // us per step at T = 841 (lab/gru256_ab.py): 4 waves x 2 blocks x 8 units 2.03 | 8 x 1 x 8: 2.03-2.07 | 4 x 2 x 16:
-  // 2.04 | 8 x 1 x 16: 1.78-1.81 | 8 x 1 x 32: 2.30.  FT_RNN_GRU_WIDE=0: the 4-wave 8-unit form.
-  const bool gru_wide = G == 3 && H == 256 && b3 && NW == 4 && env_int("FT_RNN_GRU_WIDE", 1);
-  const int mb = (wide && G == 4) || gru_wide ? rows_per_wg(a.ND, B) : MB16;
-  Geom geo;
-  geo.nchunks = H / ((wide || gru_wide) ? 16 : 8);
-  geo.nbg = ft_cdiv(B, mb);
-  geo.total = a.ND * geo.nbg * geo.nchunks;      // ND = 1: the forward direction's groups only (the workspace keeps two)
-  geo.xcd_aware = env_int("FT_RNN_XCDMAP", 1);
-  geo.sig_per_wave = env_int("FT_RNN_SIG", 1);
-  geo.max_spins = g_max_spins;
-  PersistWs p = carve_ws(ws, 2 * geo.nbg, H, mb);
-  if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
-  geo.xcd_off = 0;
-  geo.local_ok = 0;
-  geo.gran = 0;
-  geo.fast = 0;
-  a.s = 0;
-  if constexpr (G == 4) {
-    if (wide && mb == 8) return launch_fwd_persist<G, 8, true, 16, 2, 8>(a, geo, p, stream);
-  }
-  if (wide) return launch_fwd_persist<G, 8, true, 16, 2>(a, geo, p, stream);
-  if constexpr (G == 3) {
-    if (gru_wide && mb == 8) return launch_fwd_persist<G, 8, true, 16, 1, 8>(a, geo, p, stream);
-    if (gru_wide) return launch_fwd_persist<G, 8, true, 16, 1>(a, geo, p, stream);
-  }
-  if (b3) {
-    if (NW == 8) return bpw <= 1 ? launch_fwd_persist<G, 8, true, 8, 1>(a, geo, p, stream)
-                                 : launch_fwd_persist<G, 8, true, 8, 2>(a, geo, p, stream);     // (NW = 8: bpw <= 2)
-    if (bpw <= 1) return launch_fwd_persist<G, 4, true, 8, 1>(a, geo, p, stream);
-    if (bpw <= 2) return launch_fwd_persist<G, 4, true, 8, 2>(a, geo, p, stream);
-    return launch_fwd_persist<G, 4, true, 8, 4>(a, geo, p, stream);
-  }
-  return NW == 8 ? launch_fwd_persist<G, 8, false, 8, 1>(a, geo, p, stream)
-                 : launch_fwd_persist<G, 4, false, 8, 1>(a, geo, p, stream);
-}
-
-template <int G, int NW, int GW, bool B3, int MB = MB16>
-int launch_bwd_persist(const RnnBwdArgs& a, Geom geo, const PersistWs& p, hipStream_t stream) {
-  if (g_fill_probe) {
-    *g_fill_probe = xcd_demand(ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>, NW * 64,
-                               geo.nchunks * ft_cdiv(geo.total / geo.nchunks, 8));
-    return FT_OK;
-  }
-  int grid = 0;
-  const double cus = plan_launch(ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>, NW * 64, geo, grid, stream,
-                                 FormTag{"bwd", {G, NW, GW, B3, MB, -1}, B3 && GW / 2 <= 4});
-  if (cus < 0.0) return -1;
-  (void)hipMemsetAsync(p.cnt, 0, p.total_bytes, stream);
-  hipLaunchKernelGGL((ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb,
-                     p.cnt, ft_rnn_fault_word(), (unsigned)p.xb_bytes);
-  admitted_launch_done(cus, stream);
-  return ft_check_launch("rnn_bwd_persistent");
-}
-
-template <int G, int NW, int NT, int MB = MB16>
-int launch_bwd_rs(const RnnBwdArgs& a, Geom geo, const PersistWs& p, hipStream_t stream) {
-  if (g_fill_probe) {
-    *g_fill_probe =
-        xcd_demand(ft_rnn_bwd_rs_kernel<G, NW, NT, MB>, NW * 64, geo.nchunks * ft_cdiv(geo.total / geo.nchunks, 8));
-    return FT_OK;
-  }
-  int grid = 0;
-  const double cus = plan_launch(ft_rnn_bwd_rs_kernel<G, NW, NT, MB>, NW * 64, geo, grid, stream,
-                                 FormTag{"bwd_rs", {G, NW, NT, MB, -1, -1}, 0});
-  if (cus < 0.0) return -1;
-  // only the sync region (counters, flags, XCC ids) needs zeroing: every exchange block is written before it is read
-  (void)hipMemsetAsync(p.cnt, 0, p.sync_bytes, stream);
-  hipLaunchKernelGGL((ft_rnn_bwd_rs_kernel<G, NW, NT, MB>), dim3(grid), dim3(NW * 64), 0, stream, a, geo, p.xb, p.cnt,
-                     ft_rnn_fault_word(), (unsigned)p.xb_bytes);
-  admitted_launch_done(cus, stream);
-  return ft_check_launch("rnn_bwd_persistent_rs");
-}
-
-// reduce-scatter form: H/16 output tiles over NW waves, NT tiles each; -1 if it does not apply.  The LSTM-512 form
-// (G = 4, 32 tiles) comes in 8 rows per workgroup too (rows_per_wg), which regroups geo's batch.
-template <int G>
-int bwd_persistent_rs(RnnBwdArgs a, Geom geo, void* ws, size_t ws_bytes, hipStream_t stream) {
-  const int tiles = a.H / 16;
-  if (!env_int("FT_RNN_BWD_RS", 1) || !env_int("FT_RNN_B3", 1) || !geo.sig_per_wave) return -1;
-  const int mb = G == 4 && tiles == 32 ? rows_per_wg(2, a.B) : MB16;
-  geo.nbg = ft_cdiv(a.B, mb);
-  geo.total = 2 * geo.nbg * geo.nchunks;
-  PersistWs p = carve_ws_rs(ws, 2 * geo.nbg, geo.nchunks, mb);
-  if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
-  // measured (lab/rnn_step_us.py, B = 32, us/step, all-gather -> reduce-scatter): LSTM H=512 5.26 -> 4.67;
-  // GRU H=256 3.15 -> 3.60, H=128 2.87 -> 2.95, H=64 2.70 -> 2.73: the form pays once the gathered operand is large
-  // (G*H >= 1024 values per row); FT_RNN_BWD_RS=2 forces it wherever it applies
-  const bool force = env_int("FT_RNN_BWD_RS", 1) == 2;
-  if (!force && G * a.H < 1024) return -1;
-  switch (tiles) {
-    case 4: return launch_bwd_rs<G, 4, 1>(a, geo, p, stream);
-    case 8: return launch_bwd_rs<G, 8, 1>(a, geo, p, stream);
-    case 16: return launch_bwd_rs<G, 8, 2>(a, geo, p, stream);
-    case 32:
-      if constexpr (G == 4) {
-        if (mb == 8) return launch_bwd_rs<G, 8, 4, 8>(a, geo, p, stream);
-      }
-      return launch_bwd_rs<G, 8, 4>(a, geo, p, stream);
-    default: return -1;
-  }
-}
-
-template <int G>
-int bwd_persistent(RnnBwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) {
-  if (!persistent_enabled() || !ws || a.T < 2) return -1;
-  const int H = a.H, B = a.B, K = G * H;
-  if (!a.vec || H % 16 != 0) return -1;
-  const int ngroups = K / 16;
-  // waves x resident K groups per wave: 8 waves keep up to 16 groups each (256 registers per lane at 2 waves per
-  // SIMD); 16 waves would cap a lane at 128 registers and spill the LSTM-512 working set
-  const int NW = ngroups > 128 ? 16 : (ngroups > 16 ? 8 : 4);
-  const int GW = ngroups > 64 ? 16 : 8;
-  if (ft_cdiv(ngroups, NW) > GW) return -1;
-  Geom geo;
-  geo.nchunks = H / 16;
-  geo.nbg = ft_cdiv(B, MB16);
-  geo.total = 2 * geo.nbg * geo.nchunks;
-  geo.xcd_aware = env_int("FT_RNN_XCDMAP", 1);
-  geo.sig_per_wave = env_int("FT_RNN_SIG", 1);
-  geo.max_spins = g_max_spins;
-  geo.xcd_off = 0;
-  geo.local_ok = 0;
-  geo.gran = 0;
-  geo.fast = 0;
-  a.s = 0;
-  {
-    const int rc = bwd_persistent_rs<G>(a, geo, ws, ws_bytes, stream);
-    if (rc != -1) return rc;
-  }
-  // (GRU H = 256, K = 768 on 16 waves with 2 of the 24 k-blocks each instead of 8 x 3: 11.9 us per step against 2.45 --
-  //  a 1024-thread workgroup caps a lane at 128 registers; 12 waves x 2 blocks: 5.1 us; lab/gru256_ab.py)
-  const bool b3 = K % 32 == 0 && ft_cdiv(K / 32, NW) <= GW / 2 && env_int("FT_RNN_B3", 1);
-  // the GRU-256 form (8 waves x 3 resident k-blocks) comes in 8 rows per workgroup too (rows_per_wg): regroup the batch
-  const int mb = G == 3 && H == 256 && b3 && NW == 8 && GW == 8 ? rows_per_wg(2, B) : MB16;
-  geo.nbg = ft_cdiv(B, mb);
-  geo.total = 2 * geo.nbg * geo.nchunks;
-  PersistWs p = carve_ws(ws, 2 * geo.nbg, K, mb);
-  if (ws_bytes < p.total_bytes || p.xb_bytes >= (1ull << 31)) return -1;
-  if (b3) {
-    if constexpr (G == 3) {
-      if (mb == 8) return launch_bwd_persist<G, 8, 8, true, 8>(a, geo, p, stream);
-    }
-    if (NW == 16) return launch_bwd_persist<G, 16, 16, true>(a, geo, p, stream);
-    if (NW == 8) return GW == 16 ? launch_bwd_persist<G, 8, 16, true>(a, geo, p, stream)
-                                 : launch_bwd_persist<G, 8, 8, true>(a, geo, p, stream);
-    return launch_bwd_persist<G, 4, 8, true>(a, geo, p, stream);
-  }
-  if (NW == 16) return launch_bwd_persist<G, 16, 16, false>(a, geo, p, stream);
-  if (NW == 8) return GW == 16 ? launch_bwd_persist<G, 8, 16, false>(a, geo, p, stream)
-                               : launch_bwd_persist<G, 8, 8, false>(a, geo, p, stream);
-  return launch_bwd_persist<G, 4, 8, false>(a, geo, p, stream);
+// Every instantiation the library carries, by the form that names it (no (G, H, switch) reaches fwd<G,8,1,8,1,16>,
+// fwd<3,4,1,8,4,16> and fwd<3,8,1,16,2,16>: tests/rnn_forms_table.py).  A planned form without a row is an error.
+using FwdKernel = void (*)(RnnFwdArgs, Geom, float*, unsigned*, unsigned*, unsigned);
+using BwdKernel = void (*)(RnnBwdArgs, Geom, float*, unsigned*, unsigned*, unsigned);
+struct Instance {
+  rnn_plan::Kind kind;
+  int v[6];
+  FwdKernel fwd;
+  BwdKernel bwd;
+};
+#define FWD(G, NW, B3, UB, BC, MB) {rnn_plan::FWD, {G, NW, B3, UB, BC, MB}, ft_rnn_fwd_persist_kernel<G, NW, B3, UB, BC, MB>, nullptr}
+#define BWD(G, NW, GW, B3, MB) {rnn_plan::BWD, {G, NW, GW, B3, MB, -1}, nullptr, ft_rnn_bwd_persist_kernel<G, NW, GW, B3, MB>}
+#define RS(G, NW, NT, MB) {rnn_plan::BWD_RS, {G, NW, NT, MB, -1, -1}, nullptr, ft_rnn_bwd_rs_kernel<G, NW, NT, MB>}
+#define BOTH(M, ...) M(3, __VA_ARGS__), M(4, __VA_ARGS__)
+const Instance g_instances[] = {
+    BOTH(FWD, 4, 0, 8, 1, 16), BOTH(FWD, 8, 0, 8, 1, 16),                                  // f32 MFMA
+    BOTH(FWD, 4, 1, 8, 1, 16), BOTH(FWD, 4, 1, 8, 2, 16), BOTH(FWD, 4, 1, 8, 4, 16),      // bf16 split, 8 units
+    BOTH(FWD, 8, 1, 8, 1, 16), BOTH(FWD, 8, 1, 8, 2, 16),
+    BOTH(FWD, 8, 1, 16, 2, 16), FWD(4, 8, 1, 16, 2, 8),                                    // the 512-wide LSTM's
+    FWD(3, 8, 1, 16, 1, 16), FWD(3, 8, 1, 16, 1, 8),                                       // the 256-wide GRU's
+    BOTH(BWD, 4, 8, 0, 16), BOTH(BWD, 8, 8, 0, 16), BOTH(BWD, 8, 16, 0, 16), BOTH(BWD, 16, 16, 0, 16),
+    BOTH(BWD, 4, 8, 1, 16), BOTH(BWD, 8, 8, 1, 16), BOTH(BWD, 8, 16, 1, 16), BOTH(BWD, 16, 16, 1, 16),
+    BWD(3, 8, 8, 1, 8),                                                                    // the 256-wide GRU's
+    BOTH(RS, 4, 1, 16), BOTH(RS, 8, 1, 16), BOTH(RS, 8, 2, 16), BOTH(RS, 8, 4, 16), RS(4, 8, 4, 8),
+};
+#undef FWD
+#undef BWD
+#undef RS
+#undef BOTH
+const Instance* instance_of(const Form& f) {
+  for (const Instance& k : g_instances)
+    if (k.kind == f.kind && !memcmp(k.v, f.v, sizeof(k.v))) return &k;
+  ft_set_error("rnn: no kernel for the planned form %s<%d,%d,%d,%d,%d,%d>", rnn_plan::kind_name(f.kind), f.v[0], f.v[1],
+               f.v[2], f.v[3], f.v[4], f.v[5]);
+  return nullptr;
 }
 
 }  // namespace
@@ -1766,73 +1508,83 @@ unsigned* ft_rnn_fault_word() {
   return cache[dev];
 }
 
-// Share of ONE XCD's CUs that the persistent forward of this shape occupies (aligned layout), or -1 if it would not run
-// persistent.  A launch that fills whole XCDs (the 512-wide LSTM: 1.0) stops EVERY other kernel from being dispatched
-// while it is resident -- workgroups are dealt to the XCDs round-robin and the dispatcher waits at the first one whose
-// XCD has no room (profiles/r03_xcd_dispatch_probe.txt) -- so nothing it waits for may be launched beside it.
-double ft_rnn_fwd_xcd_fill(int G, int B, int T, int H, void* ws, size_t ws_bytes) {
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  RnnFwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.B = B; a.T = T; a.H = H; a.ND = 2; a.Bld = B; a.vec = H % 4 == 0;
-  double fill = -1.0;
-  g_fill_probe = &fill;
-  const int rc = G == 3 ? fwd_persistent<3>(a, ws, ws_bytes, nullptr) : fwd_persistent<4>(a, ws, ws_bytes, nullptr);
-  g_fill_probe = nullptr;
-  return rc == FT_OK ? fill : -1.0;
-}
-
-// the same for the persistent backward of this shape (what trainer.TrainStep._predictors_first budgets with)
-double ft_rnn_bwd_xcd_fill(int G, int B, int T, int H, void* ws, size_t ws_bytes) {
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  RnnBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.B = B; a.T = T; a.H = H; a.ND = 2; a.vec = H % 4 == 0;
-  double fill = -1.0;
-  g_fill_probe = &fill;
-  const int rc = G == 3 ? bwd_persistent<3>(a, ws, ws_bytes, nullptr) : bwd_persistent<4>(a, ws, ws_bytes, nullptr);
-  g_fill_probe = nullptr;
-  return rc == FT_OK ? fill : -1.0;
+// Share of ONE XCD's CUs that the persistent forward (backward != 0: BPTT) of this shape occupies (aligned layout), or
+// -1 if it would not run persistent.  A launch that fills whole XCDs (the 512-wide LSTM: 1.0) stops EVERY other kernel
+// from being dispatched while it is resident -- workgroups are dealt to the XCDs round-robin and the dispatcher waits at
+// the first one whose XCD has no room (profiles/r03_xcd_dispatch_probe.txt) -- so nothing it waits for may be launched
+// beside it.  Plans as a launch would and asks the occupancy of the kernel it would take; nothing is launched.
+double ft_rnn_xcd_fill(int G, int backward, int B, int T, int H, void* ws, size_t ws_bytes) {
+  if (!persistent_enabled() || !ws) return -1.0;
+  Switches sw(env_lookup);
+  const Form f = backward ? rnn_plan::plan_bwd(G, H, B, T, H % 4 == 0, ws_bytes, sw)
+                          : rnn_plan::plan_fwd(G, H, B, 2, T, H % 4 == 0, ws_bytes, sw);
+  const Instance* k = f.kind == rnn_plan::PER_STEP ? nullptr : instance_of(f);
+  if (!k) return -1.0;
+  const int per = rnn_plan::aligned_per(f);
+  return k->fwd ? xcd_demand(k->fwd, f.threads, per) : xcd_demand(k->bwd, f.threads, per);
 }
 
 int ft_rnn_fwd_persistent(int G, RnnFwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) {
-  return G == 3 ? fwd_persistent<3>(a, ws, ws_bytes, stream) : fwd_persistent<4>(a, ws, ws_bytes, stream);
+  if (!persistent_enabled() || !ws) return -1;
+  Switches sw(env_lookup);
+  const Form f = rnn_plan::plan_fwd(G, a.H, a.B, a.ND, a.T, a.vec, ws_bytes, sw);
+  if (f.kind == rnn_plan::PER_STEP) return -1;
+  const Instance* k = instance_of(f);
+  if (!k) return FT_ERR_ARG;
+  a.s = 0;
+  return launch_persist(k->fwd, "rnn_fwd_persistent", a, f, sw, ws, stream);
 }
+
+// the reduce-scatter form where it applies; if that grid is refused admission, the all-gather form is tried in its place
 int ft_rnn_bwd_persistent(int G, RnnBwdArgs a, void* ws, size_t ws_bytes, hipStream_t stream) {
-  return G == 3 ? bwd_persistent<3>(a, ws, ws_bytes, stream) : bwd_persistent<4>(a, ws, ws_bytes, stream);
+  if (!persistent_enabled() || !ws) return -1;
+  Switches sw(env_lookup);
+  a.s = 0;
+  for (const bool rs : {true, false}) {
+    const Form f = rnn_plan::plan_bwd(G, a.H, a.B, a.T, a.vec, ws_bytes, sw, rs);
+    if (f.kind == rnn_plan::PER_STEP) return -1;
+    const Instance* k = instance_of(f);
+    if (!k) return FT_ERR_ARG;
+    const bool is_rs = f.kind == rnn_plan::BWD_RS;
+    const int rc = launch_persist(k->bwd, is_rs ? "rnn_bwd_persistent_rs" : "rnn_bwd_persistent", a, f, sw, ws, stream);
+    if (rc != -1 || !is_rs) return rc;
+  }
+  return -1;
 }
 
 extern "C" {
 
 size_t ft_rnn_workspace(int gates, int B, int H) {
   if (gates < 3 || gates > 4 || B <= 0 || H <= 0 || H % 16 != 0) return 0;
-  // the largest of every form's workspace, in 16 and 8 rows per workgroup (8 rows: as many or fewer padded rows, but
-  // up to twice the groups' sync words)
-  size_t m = 0;
-  for (int mb : {MB16, 8}) {
-    const int ngrp = 2 * ft_cdiv(B, mb);
-    const size_t f = carve_ws(nullptr, ngrp, H, mb).total_bytes;
-    const size_t b = carve_ws(nullptr, ngrp, gates * H, mb).total_bytes;
-    const size_t r = carve_ws_rs(nullptr, ngrp, H / 16, mb).total_bytes;
-    m = f > m ? f : m;
-    m = b > m ? b : m;
-    m = r > m ? r : m;
-  }
-  return m;
+  return rnn_plan::workspace_bound(gates, B, H);
+}
+
+int ft_rnn_plan(int gates, int backward, int B, int T, int H, int nd, long* form) {
+  FT_REQUIRE((gates == 3 || gates == 4) && B > 0 && H > 0 && (nd == 1 || nd == 2) && form, "rnn_plan: bad arguments");
+  Switches sw(env_lookup);
+  Form f = {};
+  if (persistent_enabled())
+    f = backward ? rnn_plan::plan_bwd(gates, H, B, T, H % 4 == 0, (size_t)-1, sw)
+                 : rnn_plan::plan_fwd(gates, H, B, nd, T, H % 4 == 0, (size_t)-1, sw);
+  memset(form, 0, FT_RNN_PLAN_FIELDS * sizeof(long));
+  if (f.kind == rnn_plan::PER_STEP) return FT_OK;
+  int rotor = 0;                   // a query places nothing: the launches' rotor stays where it is
+  const long out[FT_RNN_PLAN_FIELDS] = {f.kind, f.v[0], f.v[1], f.v[2], f.v[3], f.v[4], f.v[5], f.threads, f.rows, f.nchunks,
+                                        f.total / f.nchunks, f.total, rnn_plan::layout_aligned(f, sw, rotor).per,
+                                        rnn_plan::layout_spread(f).per, f.gran, (long)f.ws.total_bytes};
+  memcpy(form, out, sizeof(out));
+  return FT_OK;
 }
 
 /* share of ONE XCD's CUs the persistent recurrence of this shape holds while it runs (gates 3 | 4; backward != 0: the
  * BPTT kernel), in percent; -1: it would not run persistent.  100 = whole XCDs: no other kernel is dispatched beside it */
 int ft_rnn_xcd_fill_pct(int gates, int backward, int B, int T, int H) {
   if ((gates != 3 && gates != 4) || B <= 0 || H <= 0) return -1;
-  void* const ws = (void*)(uintptr_t)256;            // never dereferenced by the probe
-  const double f = backward ? ft_rnn_bwd_xcd_fill(gates, B, T, H, ws, (size_t)-1)
-                            : ft_rnn_fwd_xcd_fill(gates, B, T, H, ws, (size_t)-1);
+  void* const ws = (void*)(uintptr_t)256;            // never dereferenced: nothing is launched
+  const double f = ft_rnn_xcd_fill(gates, backward, B, T, H, ws, (size_t)-1);
   return f < 0.0 ? -1 : (int)(f * 100.0 + 0.5);
 }
-int ft_rnn_admit_budget_pct(void) { return (int)(0.75 * env_int("FT_RNN_ADMIT_PCT", 100) + 0.5); }
+int ft_rnn_admit_budget_pct(void) { return (int)(0.75 * Switches(env_lookup)[Switches::ADMIT_PCT] + 0.5); }
 
 int ft_rnn_set_persistent(int enabled) {
   int old = persistent_enabled() ? 1 : 0;

@@ -1196,6 +1196,21 @@ def rnn_waited_launches() -> int:
     return int(_lib.query('ft_rnn_waited_launches'))
 
 
+RNN_PLAN_KINDS = ('per-step', 'fwd', 'bwd', 'bwd_rs')
+
+
+def rnn_plan(gates: int, backward: bool, B: int, T: int, H: int, nd: int = 2):
+    """ft_rnn_plan (include/fwdtaco_hip.h): the persistent form this recurrence would take under the current FT_RNN_*
+    environment, decided on the host alone; None where the per-step kernels would run.  tag is the kernel as the
+    FT_RNN_DEBUG line names it; aligned / spread: workgroups per XCD slot in that layout, 0 where it does not apply."""
+    f = (ctypes.c_long * 16)()
+    _lib.call('ft_rnn_plan', gates, int(backward), B, T, H, nd, f)
+    if f[0] == 0:
+        return None
+    keys = ('threads', 'rows', 'nchunks', 'groups', 'total', 'aligned', 'spread', 'granules', 'workspace')
+    return dict(zip(keys, f[7:]), kind=RNN_PLAN_KINDS[f[0]], tag=f'{RNN_PLAN_KINDS[f[0]]}<{",".join(map(str, f[1:7]))}>')
+
+
 def gru_fwd(xp, whh_f, whh_r, bhh_f, bhh_r, H: int, save_gates: bool):
     _chk(xp, 'xp')
     T, B, _ = xp.shape

@@ -21,7 +21,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#define FWDTACO_ABI_VERSION 7
+#define FWDTACO_ABI_VERSION 8
 
 #ifdef __cplusplus
 extern "C" {
@@ -447,6 +447,18 @@ int ft_rnn_counters(long* persistent_launches, long* refused_launches);
  * waits at the first full one). */
 int ft_rnn_xcd_fill_pct(int gates, int backward, int B, int T, int H);
 int ft_rnn_admit_budget_pct(void);
+/* The persistent form a recurrence of this shape would take under the current FT_RNN_* environment (gates 3 = GRU,
+ * 4 = LSTM; backward != 0: the BPTT, always both directions; nd = 1 | 2 directions of the forward), decided on the host
+ * alone: no device is touched, nothing is launched, aligned buffers and a workspace of ft_rnn_workspace bytes are
+ * assumed.  form[FT_RNN_PLAN_FIELDS] receives, in this order:
+ *   kind (0 = per-step kernels, and every other field 0; 1 = forward, 2 = all-gather BPTT, 3 = reduce-scatter BPTT),
+ *   the six template arguments of the kernel as the FT_RNN_DEBUG line prints them (unused ones -1),
+ *   threads per workgroup, batch rows per workgroup, workgroups per (direction, batch group) group (nchunks), groups,
+ *   workgroups in all, workgroups per XCD slot in the aligned layout and in the spread one (0: the layout does not
+ *   apply), 1 if the kernel hands over by granules inside an XCD, workspace bytes the form needs.
+ * Whether a launch is then admitted depends on the kernel's occupancy and on what is in flight (ft_rnn_xcd_fill_pct). */
+#define FT_RNN_PLAN_FIELDS 16
+int ft_rnn_plan(int gates, int backward, int B, int T, int H, int nd, long* form);
 int ft_rnn_waited_launches(void);
 int ft_gru_fwd(const float* xp, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
                float* out, float* gates, int B, int T, int H, void* workspace, size_t workspace_bytes,

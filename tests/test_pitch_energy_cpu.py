@@ -90,4 +90,4 @@ def test_token_value_abi_declared():
     assert ret == 'int' and [n for _, n in args][-2:] == ['ws', 'stream'] and len(args) == 18
     ret, args = protos['ft_pitch_norm']
     assert ret == 'int' and [n for _, n in args] == ['values', 'n', 'stats', 'ws', 'stream']
-    assert re.search(r'#define FWDTACO_ABI_VERSION (\d+)', open(_lib.HEADER_PATH).read()).group(1) == '7'
+    assert re.search(r'#define FWDTACO_ABI_VERSION (\d+)', open(_lib.HEADER_PATH).read()).group(1) == '8'
