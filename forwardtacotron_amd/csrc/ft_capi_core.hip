@@ -39,7 +39,7 @@ int ft_bn_stat_partials(const float* y, int B, int Tbuf, int C, int group, doubl
 extern "C" size_t ft_conv_stats_workspace(int B, int Tbuf, int C);
 
 // Workgroup slots of the 2-per-CU GEMM kernels on a stream (512 on an unrestricted one): the weight-gradient planner sizes
-// its one-wave grids by it (ft_gemm.hip: plan_tn).
+// its one-wave grids by it (ft_gemm_plan.h: plan_tn).
 namespace {
 std::mutex g_slots_mu;
 std::vector<std::pair<hipStream_t, int>> g_stream_slots;
@@ -162,7 +162,7 @@ static int linear_multi_fwd(const float* x, long ldx, int ntasks, const float* c
       tiles += (long)ft_cdiv(as_rows, 128) * ft_cdiv(out_f[i], 128);
       if (out_f[i] > maxN) maxN = out_f[i];
     }
-    b.force_tile = ft_rows_tile_is_big(tiles, as_rows > 0x7fffffffL ? 0x7fffffff : (int)as_rows, maxN) ? 2 : 1;
+    b.force_tile = gemm_plan::tiles_big(tiles, as_rows > 0x7fffffffL ? 0x7fffffff : (int)as_rows, maxN) ? 2 : 1;
   }
   for (int i = 0; i < ntasks; ++i) {
     FtGemmTask& t = b.t[i];

@@ -555,76 +555,12 @@ __global__ void ft_bank_wgrad_reduce_kernel(const float* __restrict__ slab, Bank
   dst.p[member][((long)co * N + n) * kk + j] = acc;
 }
 
-struct TNPlan {
-  int tm, tn, S, rows_per_split;
-};
-
-// FT_GEMM_B3_TN: 0 = weight gradients never take the bf16-split path, 1 = every tile size does, default: 128x128 only
-int tn_b3_mode() {
-  static const int mode = [] {
-    const char* e = getenv("FT_GEMM_B3_TN");
-    return e ? (e[0] == '1' ? 2 : (e[0] == '0' ? 0 : 1)) : 1;
-  }();
-  return ft_gemm_b3_enabled() ? mode : 0;
-}
-
-// split path usable (aligned operands): its 128x128 tile runs ~1.35x the f32 kernels' rate, so it is preferred whenever
-// tiles x split-K can still fill the chip -- the extra slabs it needs cost a few microseconds of HBM traffic
-TNPlan plan_tn(const FtGemmTNTask& t, bool b3_ok, long slots = 512) {
-  TNPlan p;
-  const int nz = t.nz > 1 ? t.nz : 1;
-  long maxs = (t.R + 4 * BK - 1) / (4 * BK);      // at least 128 rows per split
-  if (maxs < 1) maxs = 1;
-  const long tiles128 = (long)ft_cdiv(t.M, 128) * ft_cdiv(t.N, 128) * t.taps * nz;
-  bool small = tiles128 < 64 || t.M <= 64 || t.N <= 64;
-  // ... as long as every split still has >= 1024 rows to amortise its prologue and its slab
-  if (b3_ok && tn_b3_mode() >= 1 && t.M > 64 && t.N > 64 && tiles128 * (t.R / 1024) >= 256) small = false;
-  p.tm = p.tn = small ? 1 : 2;
-  int bm = 64 * p.tm;
-  long tiles = (long)ft_cdiv(t.M, bm) * ft_cdiv(t.N, bm) * t.taps * nz;
-  long want = tiles >= slots ? 1 : (slots + tiles - 1) / tiles;
-  // the split-path kernel holds exactly 2 workgroups per CU (53 KB LDS, 220 VGPRs) = 512 slots: a grid slightly above
-  // one full wave pays a second, nearly empty one (576 workgroups ran at 94 TF, 512 at 134) -> round DOWN there
-  const bool split_path = b3_ok && tn_b3_mode() >= 1 && p.tm == 2;
-  if (split_path && tiles < slots) want = slots / tiles;
-  if (t.bankC > 0) {
-    // conv-bank mode: member kk only has taps j < kk, i.e. (K+1)/(2K) of the grid does work; aim for ~4 waves of
-    // workgroups so that the last, partial wave costs little
-    const long K = t.taps;
-    const long live = tiles * (K + 1) / (2 * K);
-    want = (4 * slots + live - 1) / (live > 0 ? live : 1);
-  }
-  static const long force_s = [] {             // FT_TN_FORCE_S=<n>: tuning aid (lab/tn_split_lab.py)
-    const char* e = getenv("FT_TN_FORCE_S");
-    return e ? atol(e) : 0L;
-  }();
-  if (force_s > 0) want = force_s;
-  long S = want < maxs ? want : maxs;
-  if (S > 65535 / ((long)t.taps * nz)) S = 65535 / ((long)t.taps * nz);
-  if (S < 1) S = 1;
-  long rps = (t.R + S - 1) / S;
-  rps = ((rps + BK - 1) / BK) * BK;
-  if (rps < BK) rps = BK;
-  S = (t.R + rps - 1) / rps;
-  if (S < 1) S = 1;
-  p.S = (int)S;
-  p.rows_per_split = (int)rps;
-  return p;
-}
-
 // FT_GEMM_LOG=1: every launch is timed with HIP events on its stream (synchronising) and one line per launch goes
 // to stderr -- a profiling aid for tools/gemm_report.py, never enabled in a timed run.
 struct GemmLog {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   hipStream_t stream = nullptr;
-  static bool on() {
-    static int v = -1;
-    if (v < 0) {
-      const char* e = getenv("FT_GEMM_LOG");
-      v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
-  }
+  static bool on() { return ft_gemm_switches().log == 1; }
   void begin(hipStream_t s) {
     if (!on()) return;
     stream = s;
@@ -645,15 +581,29 @@ struct GemmLog {
   }
 };
 
+// The kernels of this file by planned variant.  The f32 kernels serve both precisions: the bf16 mode only re-routes
+// launches that can take the bf16 pipe (ft_gemm_b3.hip has those variants' table).
+static_assert(BK == gemm_plan::BK, "the planner rounds TN splits to this file's stage depth");
+const FtGemmInstance g_instances[] = {
+    {FT_GV_ROWS_F32_64_NT_FAST, -1, ft_gemm_rows_kernel<1, 1, false, true>, nullptr},
+    {FT_GV_ROWS_F32_64_NT_SLOW, -1, ft_gemm_rows_kernel<1, 1, false, false>, nullptr},
+    {FT_GV_ROWS_F32_64_NN_FAST, -1, ft_gemm_rows_kernel<1, 1, true, true>, nullptr},
+    {FT_GV_ROWS_F32_64_NN_SLOW, -1, ft_gemm_rows_kernel<1, 1, true, false>, nullptr},
+    {FT_GV_ROWS_F32_128_NT_FAST, -1, ft_gemm_rows_kernel<2, 2, false, true>, nullptr},
+    {FT_GV_ROWS_F32_128_NT_SLOW, -1, ft_gemm_rows_kernel<2, 2, false, false>, nullptr},
+    {FT_GV_ROWS_F32_128_NN_FAST, -1, ft_gemm_rows_kernel<2, 2, true, true>, nullptr},
+    {FT_GV_ROWS_F32_128_NN_SLOW, -1, ft_gemm_rows_kernel<2, 2, true, false>, nullptr},
+    {FT_GV_TN_F32_64_FAST, -1, nullptr, ft_gemm_tn_kernel<1, 1, true>},
+    {FT_GV_TN_F32_64_SLOW, -1, nullptr, ft_gemm_tn_kernel<1, 1, false>},
+    {FT_GV_TN_F32_128_FAST, -1, nullptr, ft_gemm_tn_kernel<2, 2, true>},
+    {FT_GV_TN_F32_128_SLOW, -1, nullptr, ft_gemm_tn_kernel<2, 2, false>},
+};
+
 }  // namespace
 
-bool ft_gemm_b3_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("FT_GEMM_B3");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
+const gemm_plan::Switches& ft_gemm_switches() {
+  static const gemm_plan::Switches sw([](const char* name) -> const char* { return getenv(name); });
+  return sw;
 }
 
 static int g_gemm_precision = 0;
@@ -670,129 +620,59 @@ extern "C" int ft_gemm_variant_counts(long* counts, int n) {
   for (int i = 0; i < n && i < FT_GV_COUNT; ++i) counts[i] = g_ft_gemm_variant[i];
   return FT_GV_COUNT;
 }
+static long g_tn_pipelined = 0;
+extern "C" int ft_gemm_tn_pipelined_launches(void) { return (int)g_tn_pipelined; }
 
-size_t ft_gemm_tn_workspace_floats(const FtGemmTNTask& t) {
-  // the query does not know the operands' alignment yet: cover both plans the launcher may pick
-  const TNPlan p0 = plan_tn(t, false), p1 = plan_tn(t, true);
-  return (size_t)(p0.S > p1.S ? p0.S : p1.S) * t.taps * (t.nz > 1 ? t.nz : 1) * t.M * t.N;
-}
-
-// Split-K plan of an NT launch (FtGemmBatch.ksplit_slab): only single-task / chained products with few 128x128 output
-// tiles, a long stage sequence (>= 128 stages of 16 k) and a plain epilogue; S ranges of >= 32 stages each, S * tiles <= the
-// stream's slots
-static int rows_ksplit_plan(const FtGemmBatch& b, int ntasks, hipStream_t stream) {
-  static const bool enabled = [] {                   // FT_GEMM_KSPLIT=0: never split (A/B knob)
-    const char* e = getenv("FT_GEMM_KSPLIT");
-    return !(e && e[0] == '0');
-  }();
-  const bool chained = b.chain > 1;
-  if (!enabled || !(chained ? b.chain == ntasks : ntasks == 1) || !ft_gemm_b3_enabled()) return 1;
-  const FtGemmTask& t0 = b.t[0];
-  if (t0.nz > 1 || t0.relu || t0.scale || t0.stat || b.hw_mode || b.relu_mask || b.out_lens || t0.N % 4 != 0 || t0.M <= 64 || t0.N <= 64) return 1;
-  if (!ft_rows_b3p_ok(b, ntasks)) return 1;
-  long stages = 0;
-  for (int i = 0; i < ntasks; ++i) stages += (long)b.t[i].taps * ft_cdiv(b.t[i].K, 16);
-  const long tiles = (long)ft_cdiv(t0.M, 128) * ft_cdiv(t0.N, 128);
-  const long slots = ft_stream_slots(stream);
-  if (stages < 128) return 1;                      // (a short contraction gains nothing: launch + second pass)
-  long S = slots / (tiles > 0 ? tiles : 1);
-  if (S > stages / 32) S = stages / 32;
-  if (S > 16) S = 16;
-  if (S < 2) return 1;
-  const long per = (stages + S - 1) / S;
-  return (int)((stages + per - 1) / per);            // no empty range
+size_t ft_gemm_tn_workspace_floats(const FtGemmTNTask& task) {
+  // the query does not know the operands yet: the larger of the plan of unaligned operands and the plan of aligned
+  // ones with padded rows, one of which the launcher will make
+  FtGemmTNTask t = task;
+  gemm_plan::normalise(t);
+  t.a_vec = t.b_vec = 0;
+  const size_t slow = gemm_plan::plan_tn(t, 0, 512, ft_gemm_switches()).need_floats;
+  t.a_vec = t.b_vec = t.rowpad = 1;
+  t.lda = t.lda > t.M + 3 ? t.lda : t.M + 3;
+  t.ldb = t.ldb > t.N + 3 ? t.ldb : t.N + 3;
+  const size_t fast = gemm_plan::plan_tn(t, 0, 512, ft_gemm_switches()).need_floats;
+  return slow > fast ? slow : fast;
 }
 
 size_t ft_rows_ksplit_floats(const FtGemmBatch& batch, int ntasks, hipStream_t stream) {
-  const int S = rows_ksplit_plan(batch, ntasks, stream);
-  return S > 1 ? (size_t)S * batch.t[0].M * batch.t[0].N : 0;
+  return gemm_plan::rows_ksplit_floats(batch, ntasks, ft_stream_slots(stream), ft_gemm_switches());
 }
 
 int ft_launch_gemm_rows(FtGemmBatch* batch, int ntasks, bool b_ncontig, hipStream_t stream) {
   FT_REQUIRE(ntasks >= 1 && ntasks <= FT_MAX_TASKS, "gemm_rows: bad task count %d", ntasks);
   int maxM = 0, maxN = 0;
-  long tiles128 = 0;
-  for (int i = 0; i < ntasks; ++i) {
-    FtGemmTask& t = batch->t[i];
-    FT_REQUIRE(t.M >= 0 && t.N >= 0 && t.K >= 0 && t.taps >= 1, "gemm_rows: bad dims");
-    FT_REQUIRE(t.amap.Tlog > 0, "gemm_rows: bad row map");
-    if (t.cmap.Tlog <= 0) t.cmap = ft_rowmap_identity(t.M);     // tasks built with memset(0): identity output
-    if (t.nz <= 1) {
-      t.nz = t.nz1 = 1;
-      t.sA0 = t.sA1 = t.sB0 = t.sB1 = t.sC0 = t.sC1 = 0;
-    }
-    FT_REQUIRE(t.nz == 1 || ntasks == 1, "gemm_rows: strided batch needs a single task");
-    FT_REQUIRE(t.nz1 >= 1 && t.nz % t.nz1 == 0, "gemm_rows: bad batch split");
-    t.a_vec = (t.lda % 4 == 0) && (((uintptr_t)t.A) % 16 == 0) && (t.sA0 % 4 == 0) && (t.sA1 % 4 == 0);
-    t.b_vec = (t.ldb % 4 == 0) && (t.b_tap_stride % 4 == 0) && (((uintptr_t)t.B) % 16 == 0) && (t.sB0 % 4 == 0) &&
-              (t.sB1 % 4 == 0);
-    if (t.M > maxM) maxM = t.M;
-    if (t.N > maxN) maxN = t.N;
-    tiles128 += (long)ft_cdiv(t.M, 128) * ft_cdiv(t.N, 128) * t.nz;
-  }
-  if (maxM == 0 || maxN == 0) return FT_OK;
-  for (int i = ntasks; i < FT_MAX_TASKS; ++i) batch->t[i] = batch->t[0];
-  const bool chained = batch->chain > 1;
-  if (chained) {
-    FT_REQUIRE(batch->chain == ntasks, "gemm_rows: chain must cover all tasks");
-    for (int i = 0; i < ntasks; ++i)
-      FT_REQUIRE(batch->t[i].M == batch->t[0].M && batch->t[i].N == batch->t[0].N && batch->t[i].nz == 1,
-                 "gemm_rows: chained tasks must share M and N");
-    tiles128 /= ntasks;
-  } else {
-    batch->chain = 0;
-  }
-  bool big = batch->force_tile ? batch->force_tile == 2 : ft_rows_tile_is_big(tiles128, maxM, maxN);
-  batch->ksplit = 0;
-  if (batch->ksplit_slab) {
-    bool ok = !b_ncontig && ft_gemm_precision() == 0;
-    for (int i = 0; i < ntasks && ok; ++i) {
-      const FtGemmTask& t = batch->t[i];
-      ok = (t.lda % 4 == 0) && (((uintptr_t)t.A) % 16 == 0) && (t.ldb % 4 == 0) && (t.b_tap_stride % 4 == 0) &&
-           (((uintptr_t)t.B) % 16 == 0) && t.K % 4 == 0;
-    }
-    const int S = ok ? rows_ksplit_plan(*batch, ntasks, stream) : 1;
-    if (S > 1) {
-      batch->ksplit = S;
-      big = true;
-    }
-  }
-  const int bm = big ? 128 : 64;
-  dim3 grid(ft_cdiv(maxM, bm), ft_cdiv(maxN, bm), chained ? 1 : (ntasks == 1 ? batch->t[0].nz : ntasks));
-  if (batch->ksplit > 1) grid.z = batch->ksplit;
-  FT_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "gemm_rows: grid too large");
-  bool fast = true;
   for (int i = 0; i < ntasks; ++i) {
     const FtGemmTask& t = batch->t[i];
-    const bool k_ok = t.K % 4 == 0 || (b_ncontig && t.a_rowpad && t.lda >= ((t.K + 3) & ~3));
-    fast = fast && t.a_vec && t.b_vec && k_ok && (!b_ncontig || t.N % 4 == 0);
+    FT_REQUIRE(t.M >= 0 && t.N >= 0 && t.K >= 0 && t.taps >= 1, "gemm_rows: bad dims");
+    FT_REQUIRE(t.amap.Tlog > 0, "gemm_rows: bad row map");
+    FT_REQUIRE(t.nz <= 1 || ntasks == 1, "gemm_rows: strided batch needs a single task");
+    FT_REQUIRE(t.nz <= 1 || (t.nz1 >= 1 && t.nz % t.nz1 == 0), "gemm_rows: bad batch split");
+    maxM = t.M > maxM ? t.M : maxM;
+    maxN = t.N > maxN ? t.N : maxN;
   }
-#define FT_ROWS_LAUNCH(TM_, BNC_)                                                                              \
-  do {                                                                                                         \
-    if (fast)                                                                                                  \
-      hipLaunchKernelGGL((ft_gemm_rows_kernel<TM_, TM_, BNC_, true>), grid, dim3(256), 0, stream, *batch);     \
-    else                                                                                                       \
-      hipLaunchKernelGGL((ft_gemm_rows_kernel<TM_, TM_, BNC_, false>), grid, dim3(256), 0, stream, *batch);    \
-  } while (0)
+  if (maxM == 0 || maxN == 0) return FT_OK;
+  if (batch->chain > 1) {
+    FT_REQUIRE(batch->chain == ntasks, "gemm_rows: chain must cover all tasks");
+    for (int i = 0; i < ntasks; ++i)
+      FT_REQUIRE(batch->t[i].M == batch->t[0].M && batch->t[i].N == batch->t[0].N && batch->t[i].nz <= 1,
+                 "gemm_rows: chained tasks must share M and N");
+  }
+  gemm_plan::normalise(*batch, ntasks);
+  const int precision = ft_gemm_precision();
+  const gemm_plan::RowsPlan p =
+      gemm_plan::plan_rows(*batch, ntasks, b_ncontig, precision, ft_stream_slots(stream), ft_gemm_switches());
+  FT_REQUIRE(p.grid[1] <= 65535 && p.grid[2] <= 65535, "gemm_rows: grid too large");
+  batch->ksplit = p.ksplit;
+  batch->stat_fused = p.stat_fused;
+  const FtGemmInstance* k = p.b3 ? ft_gemm_b3_instance(p.variant, precision) : ft_gemm_instance(g_instances, p.variant, precision);
+  if (!k || !k->rows) return FT_ERR_ARG;
   GemmLog log;
   log.begin(stream);
-  // the 64x64 tile gains nothing from the split path (its staging per MFMA is twice the 128-tile's): f32 kernel there
-  // bf16 precision mode: every NT-form fast launch takes the (one-plane) bf16 kernel, whatever its tile
-  const bool b3 = fast && !b_ncontig && ((big && ft_gemm_b3_enabled()) || ft_gemm_precision() == 1);
-  batch->stat_fused = b3 && big && !chained;      // only the 128x128 split kernel computes BatchNorm statistics
-  if (b3) {
-    (void)ft_launch_gemm_rows_b3(*batch, big, grid, stream);
-  } else {
-    ft_count_variant((big ? FT_GV_ROWS_F32_128_NT_FAST : FT_GV_ROWS_F32_64_NT_FAST) + (b_ncontig ? 2 : 0) + (fast ? 0 : 1));
-    if (big) {
-      if (b_ncontig) FT_ROWS_LAUNCH(2, true);
-      else FT_ROWS_LAUNCH(2, false);
-    } else {
-      if (b_ncontig) FT_ROWS_LAUNCH(1, true);
-      else FT_ROWS_LAUNCH(1, false);
-    }
-  }
-#undef FT_ROWS_LAUNCH
+  ft_count_variant(p.variant);
+  hipLaunchKernelGGL(k->rows, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(256), 0, stream, *batch);
   if (GemmLog::on()) {
     double fl = 0;
     long sk = 0;
@@ -801,11 +681,11 @@ int ft_launch_gemm_rows(FtGemmBatch* batch, int ntasks, bool b_ncontig, hipStrea
       fl += 2.0 * t.M * t.N * t.K * t.taps * t.nz;
       sk += (long)t.K * t.taps;
     }
-    log.end(b_ncontig ? "rowsNN" : (b3 ? (ft_gemm_precision() == 1 ? "rowsBF" : "rowsB3") : "rowsNT"), maxM, maxN, sk, ntasks, batch->t[0].nz,
-            big ? "128" : "64", fl);
+    log.end(b_ncontig ? "rowsNN" : (p.b3 ? (precision == 1 ? "rowsBF" : "rowsB3") : "rowsNT"), maxM, maxN, sk, ntasks,
+            batch->t[0].nz, p.big ? "128" : "64", fl);
   }
   int rc = ft_check_launch("gemm_rows");
-  if (rc == FT_OK && batch->ksplit > 1) rc = ft_launch_ksplit_reduce(batch->ksplit_slab, batch->ksplit, batch->t[0], stream);
+  if (rc == FT_OK && p.ksplit > 1) rc = ft_launch_ksplit_reduce(batch->ksplit_slab, p.ksplit, batch->t[0], stream);
   return rc;
 }
 
@@ -822,72 +702,45 @@ int ft_launch_gemm_tn(const FtGemmTNTask& task_in, float* workspace, size_t work
   FtGemmTNTask t = task_in;
   FT_REQUIRE(t.M >= 0 && t.N >= 0 && t.R >= 0 && t.taps >= 1, "gemm_tn: bad dims");
   if (t.M == 0 || t.N == 0) return FT_OK;
-  if (t.nz <= 1) {
-    t.nz = t.nz1 = 1;
-    t.sA0 = t.sA1 = t.sB0 = t.sB1 = t.sD0 = t.sD1 = 0;
-  }
-  FT_REQUIRE(t.nz1 >= 1 && t.nz % t.nz1 == 0, "gemm_tn: bad batch split");
-  t.a_vec = (t.lda % 4 == 0) && (((uintptr_t)t.A) % 16 == 0) && (t.sA0 % 4 == 0) && (t.sA1 % 4 == 0);
-  t.b_vec = (t.ldb % 4 == 0) && (((uintptr_t)t.B) % 16 == 0) && (t.sB0 % 4 == 0) && (t.sB1 % 4 == 0);
-  const bool m_ok = t.M % 4 == 0 || (t.rowpad && t.lda >= ((t.M + 3) & ~3));
-  const bool n_ok = t.N % 4 == 0 || (t.rowpad && t.ldb >= ((t.N + 3) & ~3));
-  const bool fast = t.a_vec && t.b_vec && m_ok && n_ok;
-  TNPlan p = plan_tn(t, fast, ft_stream_slots(stream));       // a CU-limited stream has fewer slots: fewer, longer splits
-  size_t need = (size_t)p.S * t.taps * t.nz * t.M * t.N;
-  FT_REQUIRE(workspace && workspace_floats >= need, "gemm_tn: workspace too small (%zu < %zu floats)",
-             workspace_floats, need);
-  const int bm = 64 * p.tm;
-  dim3 grid(ft_cdiv(t.M, bm), ft_cdiv(t.N, bm), p.S * t.taps * t.nz);
-  if (t.bankC > 0) {
-    FT_REQUIRE(t.bankC % bm == 0 && t.M % t.bankC == 0 && t.M / t.bankC <= FT_MAX_TASKS && t.taps == t.M / t.bankC &&
-                   t.nz == 1 && !t.accumulate,
+  FT_REQUIRE(t.nz <= 1 || (t.nz1 >= 1 && t.nz % t.nz1 == 0), "gemm_tn: bad batch split");
+  gemm_plan::normalise(t);
+  const int precision = ft_gemm_precision();
+  // a CU-limited stream has fewer slots: fewer, longer splits
+  const gemm_plan::TnPlan p = gemm_plan::plan_tn(t, precision, ft_stream_slots(stream), ft_gemm_switches());
+  FT_REQUIRE(workspace && workspace_floats >= p.need_floats, "gemm_tn: workspace too small (%zu < %zu floats)",
+             workspace_floats, p.need_floats);
+  if (t.bankC > 0)
+    FT_REQUIRE(t.bankC % (64 * p.tm) == 0 && t.M % t.bankC == 0 && t.M / t.bankC <= FT_MAX_TASKS &&
+                   t.taps == t.M / t.bankC && t.nz == 1 && !t.accumulate,
                "gemm_tn: bad conv-bank task");
-    const int K = t.taps;
-    grid = dim3((t.bankC / bm) * (K * (K + 1) / 2), ft_cdiv(t.N, bm), p.S);      // live (member, tap, tile) triples
-  }
-  FT_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "gemm_tn: grid too large");
+  FT_REQUIRE(p.grid[1] <= 65535 && p.grid[2] <= 65535, "gemm_tn: grid too large");
+  const FtGemmInstance* k = p.b3 ? ft_gemm_b3_instance(p.variant, precision) : ft_gemm_instance(g_instances, p.variant, precision);
+  if (!k || !k->tn) return FT_ERR_ARG;
   GemmLog log;
   log.begin(stream);
-  // bf16-split TN form (r-pair packed LDS tiles, ft_gemm_b3.hip): on by default for the 128x128 tile; the 64x64 tile
-  // has twice the staging per MFMA and stays on the f32 kernel unless FT_GEMM_B3_TN=1
-  const bool b3 = fast && (ft_gemm_precision() == 1 || tn_b3_mode() == 2 || (tn_b3_mode() == 1 && p.tm == 2));
-  if (b3) {
-    (void)ft_launch_gemm_tn_b3(t, workspace, p.S, p.rows_per_split, p.tm, grid, stream);
-  } else if (p.tm == 2) {
-    ft_count_variant(fast ? FT_GV_TN_F32_128_FAST : FT_GV_TN_F32_128_SLOW);
-    if (fast) hipLaunchKernelGGL((ft_gemm_tn_kernel<2, 2, true>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
-    else hipLaunchKernelGGL((ft_gemm_tn_kernel<2, 2, false>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
-  } else {
-    ft_count_variant(fast ? FT_GV_TN_F32_64_FAST : FT_GV_TN_F32_64_SLOW);
-    if (fast) hipLaunchKernelGGL((ft_gemm_tn_kernel<1, 1, true>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
-    else hipLaunchKernelGGL((ft_gemm_tn_kernel<1, 1, false>), grid, dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
-  }
+  ft_count_variant(p.variant);
+  g_tn_pipelined += p.pipelined;
+  hipLaunchKernelGGL(k->tn, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(256), 0, stream, t, workspace, p.S, p.rows_per_split);
   int rc = ft_check_launch("gemm_tn");
   if (rc) return rc;
-  long total = (long)t.nz * t.taps * t.M * t.N;
-  if (t.bankC > 0) {
+  const long total = (long)t.nz * t.taps * t.M * t.N;
+  char var[32] = "";
+  if (GemmLog::on()) snprintf(var, sizeof(var), "%d/S%d", 64 * p.tm, p.S);
+  if (p.reduce == gemm_plan::TN_REDUCE_BANK) {
     BankDst bd;
     for (int i = 0; i < FT_MAX_TASKS; ++i) bd.p[i] = t.bank_dst[i];
     hipLaunchKernelGGL(ft_bank_wgrad_reduce_kernel, dim3(ft_cdiv((long)t.M * t.N, 256), t.taps), dim3(256), 0, stream,
                        workspace, bd, t.M, t.N, t.bankC, p.S);
-    if (GemmLog::on()) {
-      char var[32];
-      snprintf(var, sizeof(var), "%d/S%d", 64 * p.tm, p.S);
-      const int K = t.M / t.bankC;
-      log.end("tnbank", t.M, t.N, t.R, t.taps, t.nz, var, 2.0 * t.bankC * t.N * t.R * (K * (K + 1) / 2));
-    }
+    const int K = t.M / t.bankC;
+    log.end("tnbank", t.M, t.N, t.R, t.taps, t.nz, var, 2.0 * t.bankC * t.N * t.R * (K * (K + 1) / 2));
     return ft_check_launch("bank_wgrad_reduce");
   }
-  if (t.taps * p.S <= 16)
+  if (p.reduce == gemm_plan::TN_REDUCE_PLAIN)
     hipLaunchKernelGGL(ft_splitk_reduce_kernel, dim3(ft_cdiv((long)t.nz * t.M * t.N, 256)), dim3(256), 0, stream, workspace,
                        t.dst, t.M, t.N, t.taps, p.S, t.ldm, t.ldn, t.ldj, t.accumulate, t.nz, t.nz1, t.sD0, t.sD1);
   else
     hipLaunchKernelGGL(ft_splitk_reduce_tap_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, stream, workspace, t.dst,
                        t.M, t.N, t.taps, p.S, t.ldm, t.ldn, t.ldj, t.accumulate, t.nz, t.nz1, t.sD0, t.sD1);
-  if (GemmLog::on()) {
-    char var[32];
-    snprintf(var, sizeof(var), "%d/S%d", 64 * p.tm, p.S);
-    log.end("tn", t.M, t.N, t.R, t.taps, t.nz, var, 2.0 * t.M * t.N * t.R * t.taps * t.nz);
-  }
+  log.end("tn", t.M, t.N, t.R, t.taps, t.nz, var, 2.0 * t.M * t.N * t.R * t.taps * t.nz);
   return ft_check_launch("splitk_reduce");
 }

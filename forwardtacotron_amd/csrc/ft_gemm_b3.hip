@@ -1182,95 +1182,30 @@ __global__ __launch_bounds__(256, 2) void ft_gemm_tn_b3p_kernel(FtGemmTNTask T, 
     }
 }
 
+// The kernels of this file by planned variant and precision: 0 = the exact 3-plane operand split, 1 = one bf16 plane
+// (ft_set_gemm_precision).  NT, FAST (16-B aligned operands, K % 4 == 0) launches only.
+const FtGemmInstance g_instances[] = {
+    {FT_GV_ROWS_B3_64, 0, ft_gemm_rows_b3_kernel<1, 1, 3>, nullptr},
+    {FT_GV_ROWS_B3_64, 1, ft_gemm_rows_b3_kernel<1, 1, 1>, nullptr},
+    {FT_GV_ROWS_B3_128, 0, ft_gemm_rows_b3_kernel<2, 2, 3>, nullptr},
+    {FT_GV_ROWS_B3_128, 1, ft_gemm_rows_b3_kernel<2, 2, 1>, nullptr},
+    {FT_GV_ROWS_B3P, 0, ft_gemm_rows_b3p_kernel<3>, nullptr},
+    {FT_GV_ROWS_B3P, 1, ft_gemm_rows_b3p_kernel<1>, nullptr},
+    {FT_GV_ROWS_B3P_KSPLIT, 0, ft_gemm_rows_b3p_kernel<3>, nullptr},      // the same kernel, batch.ksplit > 1 (fp32 only)
+    {FT_GV_TN_B3_64, 0, nullptr, ft_gemm_tn_b3_kernel<1, 1, 3>},
+    {FT_GV_TN_B3_64, 1, nullptr, ft_gemm_tn_b3_kernel<1, 1, 1>},
+    {FT_GV_TN_B3_128, 0, nullptr, ft_gemm_tn_b3_kernel<2, 2, 3>},
+    {FT_GV_TN_B3_128, 1, nullptr, ft_gemm_tn_b3_kernel<2, 2, 1>},
+    {FT_GV_TN_B3P, 0, nullptr, ft_gemm_tn_b3p_kernel<3>},
+    {FT_GV_TN_B3P, 1, nullptr, ft_gemm_tn_b3p_kernel<1>},
+};
+
 }  // namespace
 
-static long g_tn_pipelined = 0;
-extern "C" int ft_gemm_tn_pipelined_launches(void) { return (int)g_tn_pipelined; }
+const FtGemmInstance* ft_gemm_b3_instance(int variant, int precision) { return ft_gemm_instance(g_instances, variant, precision); }
 
-int ft_launch_gemm_tn_b3(const FtGemmTNTask& t, float* slab, int S, int rows_per_split, int tm, dim3 grid,
-                         hipStream_t stream) {
-  const bool bf16 = ft_gemm_precision() == 1;
-  static const bool pipelined = [] {                 // FT_GEMM_TN_PIPE=0: the two-barrier 128x128 kernel (A/B knob)
-    const char* e = getenv("FT_GEMM_TN_PIPE");
-    return !(e && e[0] == '0');
-  }();
-  // short splits (few stages per workgroup) do not amortise the deeper prologue: 256 x 256 x 26912 at 224 rows per split
-  // ran 54 -> 59 us on the pipelined kernel, the shapes with >= 1000 rows per split gain 17-25 % (lab/tn_pipe_ab.py)
-  if (tm == 2 && pipelined && rows_per_split % 16 == 0 && rows_per_split >= 512 && t.amap.Tlog == t.bmap.Tlog &&
-      t.amap.Tlog >= 16) {
-    // the pipelined kernel addresses rows with 31-bit byte offsets from the operand's base (buffer loads) and walks them
-    // with non-negative strides
-    auto span_ok = [](const FtRowMap& m, long R, long ld, int taps) {
-      if (m.bstride < 0 || m.tstride < 0) return false;
-      const long items = (R + m.Tlog - 1) / m.Tlog;
-      long lo = m.shift0 < 0 ? m.shift0 : 0, hi = m.shift0 > 0 ? m.shift0 : 0;
-      const long last = (long)m.shift0 + (long)(taps - 1) * m.shift_step;
-      lo = last < lo ? last : lo;
-      hi = last > hi ? last : hi;
-      lo -= taps;                                    // conv-bank mode: shifts tap - kk/2 within [-taps, taps]
-      hi += taps;
-      const long maxrow = (items + 1) * m.bstride + (m.Tlog + 16 + hi) * m.tstride;
-      (void)lo;                                      // rows below the base only occur masked (t + shift < 0)
-      return (maxrow + 1) * ld * 4 + 1024 < (1L << 31);
-    };
-    if (span_ok(t.amap, t.R, t.lda, t.taps) && span_ok(t.bmap, t.R, t.ldb, t.taps)) {
-      if (bf16) hipLaunchKernelGGL((ft_gemm_tn_b3p_kernel<1>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
-      else hipLaunchKernelGGL((ft_gemm_tn_b3p_kernel<3>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
-      ++g_tn_pipelined;
-      ft_count_variant(FT_GV_TN_B3P);
-      return FT_OK;
-    }
-  }
-  ft_count_variant(tm == 2 ? FT_GV_TN_B3_128 : FT_GV_TN_B3_64);
-  if (tm == 2) {
-    if (bf16) hipLaunchKernelGGL((ft_gemm_tn_b3_kernel<2, 2, 1>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
-    else hipLaunchKernelGGL((ft_gemm_tn_b3_kernel<2, 2, 3>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
-  } else {
-    if (bf16) hipLaunchKernelGGL((ft_gemm_tn_b3_kernel<1, 1, 1>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
-    else hipLaunchKernelGGL((ft_gemm_tn_b3_kernel<1, 1, 3>), grid, dim3(256), 0, stream, t, slab, S, rows_per_split);
-  }
-  return FT_OK;
-}
-
-// NT, FAST (16-B aligned operands, K % 4 == 0) launches only; grid / tile choice made by ft_launch_gemm_rows
 int ft_launch_ksplit_reduce(const float* slab, int S, const FtGemmTask& t, hipStream_t stream) {
   const long quads = ((long)t.M * t.N + 3) / 4;
   hipLaunchKernelGGL(ft_ksplit_reduce_kernel, dim3(ft_cdiv(quads, 256)), dim3(256), 0, stream, slab, S, t);
   return ft_check_launch("ksplit_reduce");
-}
-
-// may these tasks take the pipelined 128x128 kernel (the only one that implements split-K)?
-bool ft_rows_b3p_ok(const FtGemmBatch& batch, int ntask) {
-  static const bool pipelined = [] {                 // FT_GEMM_PIPE=0: the two-barrier 128x128 kernel (A/B knob)
-    const char* e = getenv("FT_GEMM_PIPE");
-    return !(e && e[0] == '0');
-  }();
-  // the pipelined kernel addresses a tile's rows with 32-bit byte offsets from the tile's first row (buffer loads)
-  bool span_ok = true;
-  for (int i = 0; i < (batch.t[0].nz > 1 ? 1 : ntask) && i < FT_MAX_TASKS; ++i) {
-    const FtGemmTask& t = batch.t[i];
-    const long tl = t.amap.Tlog, ts = t.amap.tstride, bs = t.amap.bstride;
-    const long rows = (tl < 128 ? tl : 128) * ts + (128 / tl + 2) * bs + tl * ts;     // bound on a tile's physical row span
-    span_ok = span_ok && ts >= 0 && bs >= 0 && rows * t.lda * 4 < (1L << 31) && 128L * t.ldb * 4 < (1L << 31);
-  }
-  return pipelined && span_ok;
-}
-
-int ft_launch_gemm_rows_b3(const FtGemmBatch& batch, bool big, dim3 grid, hipStream_t stream) {
-  const bool bf16 = ft_gemm_precision() == 1;
-  const int ntask = batch.chain > 1 ? batch.chain : (batch.ksplit > 1 ? 1 : (int)grid.z);
-  const bool p_ok = ft_rows_b3p_ok(batch, ntask);
-  FT_REQUIRE(batch.ksplit <= 1 || (big && p_ok), "gemm_rows: split-K planned for a launch the pipelined kernel cannot take");
-  ft_count_variant(big && p_ok ? (batch.ksplit > 1 ? FT_GV_ROWS_B3P_KSPLIT : FT_GV_ROWS_B3P) : (big ? FT_GV_ROWS_B3_128 : FT_GV_ROWS_B3_64));
-  if (big && p_ok) {
-    if (bf16) hipLaunchKernelGGL((ft_gemm_rows_b3p_kernel<1>), grid, dim3(256), 0, stream, batch);
-    else hipLaunchKernelGGL((ft_gemm_rows_b3p_kernel<3>), grid, dim3(256), 0, stream, batch);
-  } else if (big) {
-    if (bf16) hipLaunchKernelGGL((ft_gemm_rows_b3_kernel<2, 2, 1>), grid, dim3(256), 0, stream, batch);
-    else hipLaunchKernelGGL((ft_gemm_rows_b3_kernel<2, 2, 3>), grid, dim3(256), 0, stream, batch);
-  } else {
-    if (bf16) hipLaunchKernelGGL((ft_gemm_rows_b3_kernel<1, 1, 1>), grid, dim3(256), 0, stream, batch);
-    else hipLaunchKernelGGL((ft_gemm_rows_b3_kernel<1, 1, 3>), grid, dim3(256), 0, stream, batch);
-  }
-  return FT_OK;
 }

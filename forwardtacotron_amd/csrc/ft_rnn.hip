@@ -478,7 +478,7 @@ int rnn_layer_fwd(const float* x, int In, const float* const* wih, const float* 
     t.amap = FtRowMap{n, T, 1, n, 0, 0};            // rows (b, t0 + t) of the batch-major input
     t.cmap = FtRowMap{n, 1, B, n, 0, 0};            // time-major output
     // the same kernel as ft_linear_multi_fwd's two-task launch over all B * T rows takes: bit-identical results
-    b.force_tile = ft_rows_tile_is_big(2L * ft_cdiv((long)B * T, 128) * ft_cdiv(G * H, 128), B * T, G * H) ? 2 : 1;
+    b.force_tile = gemm_plan::tiles_big(2L * ft_cdiv((long)B * T, 128) * ft_cdiv(G * H, 128), B * T, G * H) ? 2 : 1;
     return ft_launch_gemm_rows(&b, 1, false, st);
   };
   int cs = nchunks > 1 ? (T + nchunks - 1) / nchunks : T;

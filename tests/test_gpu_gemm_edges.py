@@ -2,7 +2,7 @@
 
 tests/test_gpu_primitives.py checks the GEMM-shaped entry points at small odd shapes (the 64x64 f32 kernels) and at large
 ROUND shapes (the 128x128 bf16-split kernels).  This file covers what lies between: shapes just past the launcher's
-128-tile threshold (ft_rows_tile_is_big: 192 tiles -- 12,300 rows x 130..200 columns give 194) whose M, N and K are no
+128-tile threshold (gemm_plan::tiles_big: 192 tiles -- 12,300 rows x 130..200 columns give 194) whose M, N and K are no
 multiples of the tile or of the 16-deep stage.  Every case
 
   * asserts the launch-variant counter delta (hip.gemm_variant_counts) of the ONE kernel it is about -- a planner
@@ -393,7 +393,7 @@ def test_two_barrier_nt_kernel_behind_a_long_row_stride(H):
 
 
 # ---------------------------------------------------------------------------------------------------
-# split-K of NT launches (rows_ksplit_plan, ft_ksplit_reduce_kernel)
+# split-K of NT launches (gemm_plan::rows_ksplit, ft_ksplit_reduce_kernel)
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('rows,tmB', [(200, 0), (200, 8), (4096, 0), (4096, 32)])
 @pytest.mark.parametrize('acc', [0, 1])

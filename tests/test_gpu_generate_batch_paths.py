@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 
 # ---- masked eval convolution: 128-row tiles ------------------------------------------------------------------------
-# The launcher takes 128 x 128 tiles from 192 of them on (ft_rows_tile_is_big): Cout = 256 is 2 column tiles, so
+# The launcher takes 128 x 128 tiles from 192 of them on (gemm_plan::tiles_big): Cout = 256 is 2 column tiles, so
 # B * T >= 96 * 128 = 12288 rows.  B * T = 5 * 2480 = 12400 -> 97 row tiles, the last one ragged (112 rows).  Rows are
 # (b, t) = (row // T, row % T); M_TILE-row tile boundaries against the items' ends:
 #   item 0 ends ONE ROW BEHIND a boundary (last valid row 640 = first row of tile 5),

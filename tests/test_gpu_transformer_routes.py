@@ -209,7 +209,7 @@ def test_bf16_routes_are_bit_identical(monkeypatch, name):
 
 
 def test_wide_tile_gemms_ran_inside_the_composite(monkeypatch):
-    """The last case's row count is above the launcher's tile switch (csrc/ft_gemm.h: ft_rows_tile_is_big = at least 192
+    """The last case's row count is above the launcher's tile switch (csrc/ft_gemm_plan.h: tiles_big = at least 192
     128x128 tiles, M and N above 64): the in-projection [B*T, d] x [d, 3d] has ceil(B*T / 128) * ceil(3d / 128) tiles, so
     with d = 256 it switches at B*T > 31 * 128 = 3968 rows; 5 * 841 = 4205 cross it, B did not have to be raised.  In bf16
     mode the 128x128 tile is the pipelined kernel ('rows_b3p'), which nothing else in the case launches: its counter moves
