@@ -126,6 +126,41 @@ def resample_table(h: np.ndarray, half: int, up: int) -> np.ndarray:
     return tab
 
 
+def resample_device_table(cache: Dict[Tuple[int, int], Any], up: int, down: int, device):
+    """-> (the phase-major coefficient table on the device, half), built once per (up, down) and kept in `cache` (the
+    caller's: DSP and speaker.VoiceEncoder each own one)"""
+    ent = cache.get((up, down))
+    if ent is None:
+        h, half = resample_filter(down, up)                      # (up, down) is in lowest terms already
+        host = torch.zeros(_lib.query('ft_resample_table_floats', up, down, half), dtype=torch.float32).pin_memory()
+        flat = torch.from_numpy(resample_table(h, half, up).reshape(-1))
+        host[:flat.numel()] = flat
+        tab = _alloc(host.numel(), device=device)
+        tab.copy_(host, non_blocking=True)
+        ent = cache[(up, down)] = (tab, half, host)              # the pinned source stays alive with the copy
+    return ent[0], ent[1]
+
+
+def resample_intake(wavs, wav_len, device, what: str):
+    """-> (wav [B, ld] on the device with 16-byte aligned rows, lens [B] int64 on the device, Lmax, error flag or
+    None): the intake of ragged.py, then the rows of a padded batch re-laid where they are not aligned"""
+    wav, lens, L, err = ragged.intake(wavs, wav_len, device, what, row_multiple=4, allow_all_empty=False, alloc=_alloc)
+    if wav.shape[1] % 4 or not wav.is_contiguous() or wav.data_ptr() % 16:
+        buf = _alloc(len(wav), (L + 3) // 4 * 4, device=device)      # columns >= L are never read: every len <= L
+        buf[:, :L].copy_(wav)
+        wav = buf
+    return wav, lens, L, err
+
+
+def resample_ragged(cache: Dict[Tuple[int, int], Any], wav: torch.Tensor, lens: torch.Tensor, Lmax: int, up: int,
+                    down: int, err: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the one launch (ft_resample_poly_ragged) on a batch resample_intake laid out -> {'wav' [B, ldy], 'wav_len' [B]}"""
+    ldy = max(4, (-((-Lmax * up) // down) + 3) // 4 * 4)         # from the host's bound: no sync to allocate
+    tab, half = (None, 0) if up == down else resample_device_table(cache, up, down, wav.device)
+    y, out_len = H.resample_poly_ragged(wav, lens, Lmax, tab, up, down, half, ldy, err, alloc=_alloc)
+    return {'wav': y, 'wav_len': out_len}
+
+
 class DSP:
     def __init__(self, num_mels: int, sample_rate: int, hop_length: int, win_length: int, n_fft: int, fmin: float,
                  fmax: float, peak_norm: bool = False, trim_start_end_silence: bool = True,
@@ -190,34 +225,15 @@ class DSP:
     # ---- sample-rate conversion ----------------------------------------------------------------------
     def _rs_table(self, up: int, down: int):
         """-> (the phase-major coefficient table on the device, half), built once per (up, down)"""
-        ent = self._rs_tabs.get((up, down))
-        if ent is None:
-            h, half = resample_filter(down, up)                      # (up, down) is in lowest terms already
-            host = torch.zeros(_lib.query('ft_resample_table_floats', up, down, half), dtype=torch.float32).pin_memory()
-            flat = torch.from_numpy(resample_table(h, half, up).reshape(-1))
-            host[:flat.numel()] = flat
-            tab = _alloc(host.numel(), device=self.device)
-            tab.copy_(host, non_blocking=True)
-            ent = self._rs_tabs[(up, down)] = (tab, half, host)      # the pinned source stays alive with the copy
-        return ent[0], ent[1]
+        return resample_device_table(self._rs_tabs, up, down, self.device)
 
     def _rs_input(self, wavs, wav_len):
-        """-> (wav [B, ld] on the device with 16-byte aligned rows, lens [B] int64 on the device, Lmax, error flag or
-        None): the intake of ragged.py, then the rows of a padded batch re-laid where they are not aligned"""
-        wav, lens, L, err = ragged.intake(wavs, wav_len, self.device, 'resample_batch', row_multiple=4,
-                                          allow_all_empty=False, alloc=_alloc)
-        if wav.shape[1] % 4 or not wav.is_contiguous() or wav.data_ptr() % 16:
-            buf = _alloc(len(wav), (L + 3) // 4 * 4, device=self.device)      # columns >= L are never read: every len <= L
-            buf[:, :L].copy_(wav)
-            wav = buf
-        return wav, lens, L, err
+        """resample_intake under this object's name and device"""
+        return resample_intake(wavs, wav_len, self.device, 'resample_batch')
 
     def _resample(self, wav: torch.Tensor, lens: torch.Tensor, Lmax: int, up: int, down: int,
                   err: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
-        ldy = max(4, (-((-Lmax * up) // down) + 3) // 4 * 4)         # from the host's bound: no sync to allocate
-        tab, half = (None, 0) if up == down else self._rs_table(up, down)
-        y, out_len = H.resample_poly_ragged(wav, lens, Lmax, tab, up, down, half, ldy, err, alloc=_alloc)
-        return {'wav': y, 'wav_len': out_len}
+        return resample_ragged(self._rs_tabs, wav, lens, Lmax, up, down, err)
 
     def resample_batch(self, wavs, source_sr: int, target_sr: Optional[int] = None,
                        wav_len: Optional[Wav] = None) -> Dict[str, torch.Tensor]:
@@ -352,5 +368,5 @@ def split_wavs(out: Dict[str, Wav]) -> List[np.ndarray]:
     return [np.ascontiguousarray(wav[b, :int(wav_len[b])]) for b in range(wav.shape[0])]
 
 
-__all__ = ['DSP', 'MEL_PAD_VALUE', 'resample_filter', 'resample_len', 'resample_ratio', 'resample_table',
-           'sparse_mel_basis', 'split_items', 'split_wavs']
+__all__ = ['DSP', 'MEL_PAD_VALUE', 'resample_device_table', 'resample_filter', 'resample_intake', 'resample_len',
+           'resample_ragged', 'resample_ratio', 'resample_table', 'sparse_mel_basis', 'split_items', 'split_wavs']

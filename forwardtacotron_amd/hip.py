@@ -1541,3 +1541,88 @@ def overlap_add_ragged(frames: torch.Tensor, w2: torch.Tensor, mel_len: torch.Te
         _lib.call('ft_overlap_add_ragged', _p(frames), _p(w2), _p(mel_len), None if as_wav else _p(out),
                   _p(out) if as_wav else None, B, Tcap, Tmax, n_fft, hop, _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# speaker embeddings (csrc/ft_speaker.hip; the public interface is speaker.VoiceEncoder)
+# ---------------------------------------------------------------------------------------------------
+def spk_slices(n: int, hop: int, partial_frames: int, frame_step: int, cov_num: int, cov_den: int):
+    """(count, frames) of the slice rule at a length of n samples: the function the kernels apply on the device, on the
+    host (no device needed)"""
+    a, b = ctypes.c_long(0), ctypes.c_long(0)
+    _lib.call('ft_spk_slices', n, hop, partial_frames, frame_step, cov_num, cov_den, ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
+def lstm_fwd_uni(xp: torch.Tensor, whh: torch.Tensor, bhh: torch.Tensor, H: int, alloc=torch.empty):
+    """one direction from zero states: xp [T, B, 4H] (x W_ih^T + b_ih, time-major) -> (out_raw, cstate) [T, B, H]"""
+    _chk(xp, 'xp'); _chk(whh, 'whh'); _chk(bhh, 'bhh')
+    T, B, _ = xp.shape
+    out = alloc(T, B, H, dtype=torch.float32, device=xp.device)
+    cst = alloc(T, B, H, dtype=torch.float32, device=xp.device)
+    ws, nb = _rnn_workspace(4, B, H, xp.device)
+    _lib.call('ft_lstm_fwd_uni', _p(xp), _p(whh), _p(bhh), _p(out), _p(cst), B, T, H, _p(ws), nb, _stream())
+    return out, cst
+
+
+def spk_gain(wav: torch.Tensor, lens: torch.Tensor, Lmax: int, target: float, hop: int, partial_frames: int,
+             frame_step: int, cov_num: int, cov_den: int, normalize: bool, err: Optional[torch.Tensor] = None,
+             alloc=torch.empty):
+    """wav [B, ld] fp32, lens [B] int64 (device) -> (gain [B] fp32, n_partials [B] int64, frames [B] int64)"""
+    _chk(wav, 'wav'); _chk(lens, 'wav_len', torch.int64)
+    B, ld = wav.shape
+    gain = alloc(B, dtype=torch.float32, device=wav.device)
+    n_partials = alloc(B, dtype=torch.int64, device=wav.device)
+    frames = alloc(B, dtype=torch.int64, device=wav.device)
+    _lib.call('ft_spk_gain', _p(wav), ld, _p(lens), B, Lmax, float(target), hop, partial_frames, frame_step, cov_num,
+              cov_den, int(normalize), _p(gain), _p(n_partials), _p(frames), _p(err), _stream())
+    return gain, n_partials, frames
+
+
+def spk_pack(wav: torch.Tensor, lens: torch.Tensor, Lmax: int, gain: torch.Tensor, stride: int, n_fft: int,
+             alloc=torch.empty) -> torch.Tensor:
+    """-> packed [B * stride + n_fft]: gain * wav behind n_fft / 2 zeros, zero-extended, one stride per item"""
+    B, ld = wav.shape
+    packed = alloc(B * stride + n_fft, dtype=torch.float32, device=wav.device)
+    _lib.call('ft_spk_pack', _p(wav), ld, _p(lens), B, Lmax, _p(gain), _p(packed), stride, n_fft, _stream())
+    return packed
+
+
+def spk_mel_power(spec: torch.Tensor, Fp: int, rows_per_item: int, frames: torch.Tensor, w: torch.Tensor,
+                  meta: torch.Tensor, n_mels: int, B: int, alloc=torch.empty) -> torch.Tensor:
+    """split spectra [B * rows_per_item, 2 Fp] -> power mel [B * rows_per_item, n_mels], zero rows at t >= frames[b]"""
+    _chk(spec, 'spec'); _chk(frames, 'frames', torch.int64); _chk(w, 'w'); _chk(meta, 'meta', torch.int32)
+    mel = alloc(B * rows_per_item, n_mels, dtype=torch.float32, device=spec.device)
+    _lib.call('ft_spk_mel_power', _p(spec), spec.shape[1], Fp, rows_per_item, _p(frames), _p(w), _p(meta), w.numel(),
+              n_mels, B, _p(mel), _stream())
+    return mel
+
+
+def spk_gather_partials(mel: torch.Tensor, rows_per_item: int, frames: torch.Tensor, table: torch.Tensor, p0: int,
+                        P: int, partial_frames: int, B: int, alloc=torch.empty) -> torch.Tensor:
+    """slots p0 .. p0 + P - 1 of table [*, 2] int32 = (item, first frame) -> [partial_frames, P, n_mels] time-major"""
+    _chk(mel, 'mel'); _chk(table, 'table', torch.int32)
+    assert 0 <= p0 and p0 + P <= table.shape[0]
+    n_mels = mel.shape[1]
+    out = alloc(partial_frames, P, n_mels, dtype=torch.float32, device=mel.device)
+    _lib.call('ft_spk_gather_partials', _p(mel), rows_per_item, n_mels, _p(frames), table.data_ptr() + 8 * p0, P,
+              partial_frames, B, _p(out), _stream())
+    return out
+
+
+def spk_segment_mean_norm(rows: torch.Tensor, index: Optional[torch.Tensor], offsets: torch.Tensor,
+                          count: Optional[torch.Tensor], normalize_rows: bool, rows_out: Optional[torch.Tensor] = None,
+                          alloc=torch.empty) -> torch.Tensor:
+    """rows [N, E], offsets int64 [S + 1] (into index int64, or into the rows themselves) -> [S, E] unit mean rows"""
+    _chk(rows, 'rows'); _chk(offsets, 'offsets', torch.int64)
+    N, E = rows.shape
+    S = offsets.numel() - 1
+    if index is not None:
+        _chk(index, 'index', torch.int64)
+    if count is not None:
+        _chk(count, 'count', torch.int64)
+        assert count.numel() == S
+    out = alloc(S, E, dtype=torch.float32, device=rows.device)
+    _lib.call('ft_spk_segment_mean_norm', _p(rows), N, E, _p(index), _p(offsets), _p(count), S, int(normalize_rows),
+              _p(out), _p(rows_out), _stream())
+    return out

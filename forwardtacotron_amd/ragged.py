@@ -1,5 +1,6 @@
 """The intake of a ragged batch, shared by audio.DSP (preprocess_batch, resample_batch), vocoder.GriffinLim
-(griffinlim_batch) and pitch.LibrosaPitchExtractor (extract_batch).  The contract, stated here once:
+(griffinlim_batch), pitch.LibrosaPitchExtractor (extract_batch) and speaker.VoiceEncoder (embed_batch).  The contract,
+stated here once:
   * a batch is a list of 1-D wavs (gather_wavs pads them into one [B, ld] device buffer) or a padded batch with its
     lengths, int64 [B], on the host or on the device (device_lens);
   * host lengths are checked before any launch, and the FtError names the offending list;

@@ -930,6 +930,47 @@ int ft_pyin_viterbi(const float* lo_v, const float* lo_u, const long* frames, in
                     const float* logtri, const float* lognorm, const float* freqs, float ls, float lw, float LZ, float lN,
                     int* state, float* score, float* pitch, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- speaker embeddings (preprocess.py:80,173-182,218-227: resemblyzer's VoiceEncoder.embed_utterance per file and the
+ *      mean per speaker; speaker.VoiceEncoder; the definition is DESIGN.md section 7, "Speaker embedding") ------------ */
+/* A ragged batch as for the audio front end: wav [B, ld] fp32 (16-byte aligned rows, ld % 4 == 0), len [B] int64 on the
+ * device, 1 <= len[b] <= Lmax <= ld.  A len[b] outside [1, Lmax] is clamped into it and ft_spk_gain sets *err_flag = 1
+ * (int32 on the device, zeroed by the caller; NULL = no report).
+ * The slice rule (ft_spk_slices on the host; the kernels apply the same function to len[b] on the device): with hop,
+ * partial_frames pf, frame_step and min_coverage = cov_num / cov_den (0 <= cov_num <= cov_den <= 2^20), n_frames =
+ * ceil((n + 1) / hop), steps = max(1, n_frames - pf + frame_step + 1), one partial [i, i + pf) in frames per i in
+ * range(0, steps, frame_step); the last one is dropped if it is not the only one and (n - i hop) cov_den < cov_num pf hop.
+ * count = the partials kept, frames = i_last + pf = the mel frames they cover.
+ * ft_spk_gain (one workgroup per item): ms = (sum of w^2 over the item's samples, in fp64 and in an order that depends on
+ * len[b] alone) / len[b]; with normalize, gain[b] = g = target / sqrt(ms) rounded to fp32 once if g > 1, else 1 (also
+ * for ms == 0 or NaN); without, 1.  n_partials[b], frames[b] = the slice rule at len[b].
+ * ft_spk_pack: packed [B * stride + n_fft] (stride % 4 == 0, n_fft % 8 == 0): packed[b * stride + n_fft / 2 + j] =
+ * gain[b] * wav[b, j] (one fp32 multiplication) for j < len[b] where that lies inside the item's stride, zeros elsewhere
+ * and in the n_fft tail.  With stride a multiple of hop the frames of all items are rows of ONE GEMM with ldx = hop.
+ * ft_spk_mel_power: spec [B * rows_per_item, ld_spec] split spectra (Re at 0.., Im at Fp.., Fp % 4 == 0) -> mel [B *
+ * rows_per_item, n_mels] FRAME-major: mel[row, m] = sum over the bins of filter m, ascending, of w * (Re^2 + Im^2) (fp32
+ * fma chain; no square root, no log); rows t >= frames[b] of item b are zero.  The basis is ft_mel_project's sparse form
+ * (meta [n_mels, 3] int32 = first bin, number of bins, offset into w [nnz]).
+ * ft_spk_gather_partials: table [P, 2] int32 = (item, first frame) per slot -> out [pf, P, n_mels] TIME-major:
+ * out[t, p, :] = mel[item * rows_per_item + first + t, :] if first + pf <= frames[item], else zero (an unused slot).
+ * ft_spk_segment_mean_norm: rows [N, E] (E <= 1024); segment s is the entries offsets[s] .. offsets[s + 1] - 1 (int64
+ * [S + 1]) of index (int64; NULL: the rows themselves, contiguous), cut to its first count[s] entries where count (int64
+ * [S]) is not NULL.  With normalize_rows every row of a segment is first divided by its own 2-norm (and written to
+ * rows_out [N, E] where that is not NULL; rows of no segment are not written).  out[s] = m / |m|_2, m = (sum of the
+ * segment's rows in ascending order) / their number.  No epsilon: a zero norm, or an empty segment, gives NaN. */
+int ft_spk_slices(long n, int hop, int partial_frames, int frame_step, long cov_num, long cov_den, long* count,
+                  long* frames);
+int ft_spk_gain(const float* wav, long ld, const long* len, int B, long Lmax, double target, int hop, int partial_frames,
+                int frame_step, long cov_num, long cov_den, int normalize, float* gain, long* n_partials, long* frames,
+                int* err_flag, void* stream);
+int ft_spk_pack(const float* wav, long ld, const long* len, int B, long Lmax, const float* gain, float* packed,
+                long stride, int n_fft, void* stream);
+int ft_spk_mel_power(const float* spec, long ld_spec, int Fp, int rows_per_item, const long* frames, const float* w,
+                     const int* meta, int nnz, int n_mels, int B, float* mel, void* stream);
+int ft_spk_gather_partials(const float* mel, int rows_per_item, int n_mels, const long* frames, const int* table, int P,
+                           int partial_frames, int B, float* out, void* stream);
+int ft_spk_segment_mean_norm(const float* rows, int N, int E, const long* index, const long* offsets, const long* count,
+                             int S, int normalize_rows, float* out, float* rows_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
