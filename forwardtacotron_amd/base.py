@@ -100,9 +100,9 @@ class AcousticModel(nn.Module):
     # its own (or, through predictor_hook, inside the forward)
     independent_predictors: bool = True
     # token-side row count (incl. the conv bank's extra row), set per forward by the recurrent models: TrainStep keeps
-    # weight gradients of operands this short on the main stream (ops.GradSink.inline_rows)
+    # weight gradients of operands this short on the main stream (gradsink.Policy.inline_rows)
     wgrad_inline_rows: int = 0
-    wgrad_defer: bool = False       # recurrences ahead (ops.GradSink.defer); set per forward by the recurrent models
+    wgrad_defer: bool = False       # recurrences ahead (gradsink.Policy.defer); set per forward by the recurrent models
     # set by TrainStep around one forward: cut the graph below the decoder LSTM (model.regulate_and_decode), which
     # leaves (tensor below the cut, its detached twin above it) in _cut for the trainer's three-stage backward
     stage_backward: bool = False

@@ -20,7 +20,8 @@ from . import _lib
 from . import hip as H
 from . import ops
 from .base import AcousticModel, LengthRegulator, PAD_VALUE, _dropout, _seed, predictor_front, predictor_tail
-from .ops import _c, _emit, _emit_multi
+from .gradsink import batched_side_launches, emit, installed
+from .ops import _c
 
 _F4 = 4
 
@@ -152,9 +153,9 @@ def mha_bwd(tape, dout, in_w, in_b, out_w, out_b, need_dx=True, dx_into=None):
     rows = B * T
     dev = x.device
     datt = H.linear_bwd_data(dout, out_w)
-    g_ow = _emit(out_w, lambda o: H.linear_bwd_weight_raw(dout.data_ptr(), d, att.data_ptr(), d, o, rows, d, d),
-                 (dout, att))
-    g_ob = _emit(out_b, lambda o: H.colsum_raw(dout.data_ptr(), d, o, rows, d), (dout,), heavy='light')
+    g_ow = emit(out_w, lambda o: H.linear_bwd_weight_raw(dout.data_ptr(), d, att.data_ptr(), d, o, rows, d, d),
+                (dout, att))
+    g_ob = emit(out_b, lambda o: H.colsum_raw(dout.data_ptr(), d, o, rows, d), (dout,), heavy='light')
     if tape['fused']:
         dqkv = H.attn_bwd(qkv, att, datt, key_pad, tape['lse2'], nh, scale, p_drop, seed)
         g0 = dqkv.data_ptr()
@@ -181,8 +182,8 @@ def mha_bwd(tape, dout, in_w, in_b, out_w, out_b, need_dx=True, dx_into=None):
     dx = None
     if need_dx:
         dx = H.linear_bwd_data(dqkv, in_w, dx=dx_into, accumulate=dx_into is not None)
-    g_iw = _emit(in_w, lambda o: H.linear_bwd_weight_raw(g0, 3 * d, x.data_ptr(), d, o, rows, d, 3 * d), (dqkv, x))
-    g_ib = _emit(in_b, lambda o: H.colsum_raw(g0, 3 * d, o, rows, 3 * d), (dqkv,), heavy='light')
+    g_iw = emit(in_w, lambda o: H.linear_bwd_weight_raw(g0, 3 * d, x.data_ptr(), d, o, rows, d, 3 * d), (dqkv, x))
+    g_ib = emit(in_b, lambda o: H.colsum_raw(g0, 3 * d, o, rows, 3 * d), (dqkv,), heavy='light')
     return dx, g_iw, g_ib, g_ow, g_ob
 
 
@@ -230,8 +231,8 @@ def addln_bwd(tape, dy, gamma, beta, own_dres=False):
     dres = torch.empty_like(s) if tape['has_res'] and (tape['p'] > 0 or own_dres) else None
     _lib.call('ft_layernorm_bwd', dy.data_ptr(), s.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
               dx.data_ptr(), t.data_ptr(), _p(dres), rows, D, tape['p'], tape['seed'], H._stream())
-    dg, db = _emit_multi([gamma, beta], lambda o: H.colsum2_raw(t.data_ptr(), dy.data_ptr(), D, o[0], o[1], rows, D),
-                         (t, dy), heavy='light')
+    dg, db = emit([gamma, beta], lambda o: H.colsum2_raw(t.data_ptr(), dy.data_ptr(), D, o[0], o[1], rows, D),
+                  (t, dy), heavy='light')
     return dx, ((dres if dres is not None else dx) if tape['has_res'] else None), dg, db
 
 
@@ -259,8 +260,8 @@ def convbias_bwd(tape, dy, w, b, need_dx=True, dx_into=None):
     if need_dx:
         dx = dx_into if dx_into is not None else torch.empty_like(x)
         H.conv1d_bwd_data_raw(dy.data_ptr(), Cout, wp, dx, B, T, T, T, dx_into is not None, w=w)
-    dw = _emit(w, lambda o: H.conv1d_bwd_weight_raw(dy.data_ptr(), Cout, x, o, T, T), (dy, x))
-    db = _emit(b, lambda o: H.colsum_raw(dy.data_ptr(), Cout, o, B * T, Cout), (dy,), heavy='light')
+    dw = emit(w, lambda o: H.conv1d_bwd_weight_raw(dy.data_ptr(), Cout, x, o, T, T), (dy, x))
+    db = emit(b, lambda o: H.colsum_raw(dy.data_ptr(), Cout, o, B * T, Cout), (dy,), heavy='light')
     return dx, dw, db
 
 
@@ -324,7 +325,7 @@ def posenc_bwd_scale(dout, pe, scale):
         _lib.call('ft_posenc_bwd_scale', dout.data_ptr(), pe.data_ptr(), o.data_ptr(), B, T, D, ws.data_ptr(),
                   ws.numel(), H._stream())
 
-    return _emit(scale, dscale, heavy=False)
+    return emit(scale, dscale, heavy=False)
 
 
 class PosEncFn(Function):
@@ -457,7 +458,7 @@ def blocks_bwd_composite(state, dy, params):
     names = ('t2', 'd_y1', 'd_h2', 'd_h1', 'g_h1', 't1', 'd_h', 'd_sa', 'datt', 'dqkv')
     grads = (_CGrads * n)()
     scratch, outs, sunk = [], [None] * (12 * n), []
-    sink = ops._SINK
+    sink = installed()
     dy_ptr = dy.data_ptr()
     last_dh = None
     for i in range(n - 1, -1, -1):
@@ -478,9 +479,8 @@ def blocks_bwd_composite(state, dy, params):
         dy_ptr = ptrs['d_h']
         last_dh = (ar, offs[names.index('d_h')])
         for j, name in enumerate(_GRAD_FIELDS):
-            ent = ops._sink_view(ps[j])
-            if ent is not None:
-                sink.written.add(ent[0])        # claimed (a second emitter of the same parameter would get a fresh tensor)
+            ent = sink.claim(ps[j]) if sink is not None else None
+            if ent is not None:                 # (a second emitter of the same parameter would get a fresh tensor)
                 sunk.append(ent[0])
                 setattr(g, name, ent[1].data_ptr())
             else:
@@ -508,9 +508,7 @@ def blocks_bwd_composite(state, dy, params):
     _lib.call('ft_fft_blocks_bwd', _ct.byref(blocks), _ct.byref(grads), n, ws.data_ptr(), ws.numel(), wws.data_ptr(),
               wws.numel(), _p(sws), sws.numel() if sws is not None else 0, H._stream(), side_raw, sums_raw)
     if sums is not None:
-        sink.used.add(sums)
-        if sink.reducer_streams is not None:
-            sink.reducer_streams.add(sums)
+        sink.wrote_on(sums, tell_reducer=True)
     dx = last_dh[0][last_dh[1]:last_dh[1] + R * d].view(B, T, d)     # d wrt the first block's input, in place
     if sink is None:
         dx._ft_keep = (scratch, state['arenas'], state['keep'])       # no sink: everything ran on this stream, in order
@@ -518,13 +516,11 @@ def blocks_bwd_composite(state, dy, params):
         # read by the weight-gradient stream until joined; state['h'] is block 0's input, the operand of the LAST weight
         # gradient issued (its in-projection's): the caller drops `state` as soon as this returns, and a freed `h` is the
         # main stream's to reuse while that GEMM still reads it
-        sink.keep.append((scratch, state['arenas'], state['keep'], dy, state['h'], state['key_pad']))
+        sink.hold((scratch, state['arenas'], state['keep'], dy, state['h'], state['key_pad']))
         if side is not None:
-            sink.used.add(side)
-        for idx in sunk:
-            sink.used.add(torch.cuda.current_stream())
-            if sink.on_write is not None:
-                sink.on_write(idx)
+            sink.wrote_on(side)
+        if sunk:
+            sink.announce(sunk)
     return dx, outs
 
 
@@ -583,7 +579,7 @@ class TransformerFn(Function):
         for i in range(len(ctx.tapes) - 1, -1, -1):
             in_w, in_b, out_w, out_b, c1w, c1b, c2w, c2b, n1g, n1b, n2g, n2b = params[12 * i:12 * i + 12]
             t_mha, t_n1, t_c1, t_c2, t_n2 = ctx.tapes[i]
-            with ops.batched_side_launches():       # the block's six weight / six bias gradients: one side-stream hand-over
+            with batched_side_launches():       # the block's six weight / six bias gradients: one side-stream hand-over
                 d_y1, d_h2, g_n2g, g_n2b = addln_bwd(t_n2, d, n2g, n2b, own_dres=True)
                 d_h1, g_c2w, g_c2b = convbias_bwd(t_c2, d_h2, c2w, c2b)
                 d_y1, g_c1w, g_c1b = convbias_bwd(t_c1, d_h1, c1w, c1b, dx_into=d_y1)          # + the residual path

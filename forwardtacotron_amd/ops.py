@@ -12,265 +12,19 @@ import torch
 from torch.autograd import Function
 
 from . import hip as H
+from .gradsink import claim, emit, emit_copies, flush_begin, flush_end, installed
 
 _F4 = 4  # sizeof(float)
 
 
+def __getattr__(name):
+    if name == '_SINK':             # the installed gradient sink under the name it had while it lived here (read-only)
+        return installed()
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
+
+
 def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
-
-
-# ---------------------------------------------------------------------------------------------------
-# Gradient sink (installed by trainer.TrainStep; absent = plain autograd semantics).
-#
-# Every parameter of the model receives exactly one gradient contribution per backward pass, so the
-# weight-gradient kernels can write STRAIGHT into the trainer's flat gradient buffer (no temporary, no
-# AccumulateGrad add) and the backward returns None for that input.  Weight gradients are off the
-# critical data-gradient chain, so with a sink the GEMM-shaped ones are issued on a second HIP stream and
-# overlap the latency-bound persistent recurrences; the trainer joins that stream before the optimiser.
-# ---------------------------------------------------------------------------------------------------
-class GradSink:
-    def __init__(self, views, stream=None, on_write=None):
-        self.views = views              # {param.data_ptr(): (index, grad view tensor)}
-        self.written = set()
-        self.stream = stream            # side stream for weight-gradient GEMMs (None: current stream)
-        self.on_write = on_write        # callback(index) -> lets the bucketed all-reduce count arrivals
-        # weight-gradient GEMMs whose operands have at most this many rows stay on the CURRENT stream (0: none do).
-        # ForwardTacotron sets it to its token-side row count: those gradients (prenet, predictors) only become
-        # computable at the very end of the backward, right after the first LSTM's four big weight gradients landed
-        # on the side stream -- left there they queue behind them while the main stream has nothing left to do
-        # (1.9 ms of a 28.4 ms step); on the main stream the two tails overlap.  FastPitch, whose whole token side
-        # is launch-bound, is faster with everything on the side stream and leaves it at 0.
-        self.inline_rows = 0
-        # defer = True: side-stream weight gradients are not launched where they are emitted but queued, and launched
-        # in one go right before the next recurrence's BPTT kernel (ops.flush_deferred) -- the persistent recurrences
-        # leave most of the chip idle, while between them the main stream's own GEMM / BatchNorm chain wants it all
-        self.defer = False
-        self.pending = []               # (compute, views, deps, indices, ready event)
-        self.held = set()               # indices queued in `pending`: claimed, not yet issued (the all-reduce must wait)
-        self.main = None
-        self.used = set()               # streams gradient writes were issued on this step
-        # operands of side-stream launches, kept REFERENCED until the step has joined the side stream.  record_stream only
-        # keeps their memory from being recycled; it does not keep autograd from ADDING INTO them: a gradient tensor handed
-        # to two consumers (LayerNorm's dx for branch and residual, AddBackward's grad for both addends) is accumulated
-        # in place -- on the emitting stream -- as soon as it is uniquely owned, i.e. right after the conv / linear node
-        # whose weight gradient is still reading it on the side stream has returned (seen as rare wrong conv2 weight
-        # gradients in MultiFastPitch's predictors).  A live reference makes autograd add out of place instead.
-        self.keep = []
-        # late_ok (set per step by the trainer): weight gradients emitted with late=True are not sent to the side stream but
-        # run on the step's MAIN stream at the very end of the backward (flush_deferred) -- with the predictors' stage out of
-        # the tail the main stream finishes its chain 0.8 ms before the side stream has worked off the LSTM's four weight
-        # gradients; one of the four rebalances the two.
-        self.late_ok = False
-        self.late = []
-        # set by the trainer: the set of streams a gradient bucket's all-reduce waits for; whoever writes gradients on yet
-        # another stream adds it here
-        self.reducer_streams = None
-
-    def begin_step(self):
-        self.written.clear()
-        self.late.clear()
-        self.pending.clear()
-        self.held.clear()
-        self.used.clear()
-        self.keep.clear()
-        self.main = torch.cuda.current_stream() if torch.cuda.is_available() else None   # the step's critical stream
-
-
-_SINK: Optional[GradSink] = None
-
-
-def set_grad_sink(sink: Optional[GradSink]) -> None:
-    global _SINK
-    _SINK = sink
-
-
-def _sink_view(w: torch.Tensor):
-    """(index, view) of w's slot in the flat gradient buffer if a sink is installed and the slot is still
-    unwritten this step, else None."""
-    if _SINK is None:
-        return None
-    ent = _SINK.views.get(w.data_ptr())
-    if ent is None or ent[0] in _SINK.written:
-        return None
-    return ent
-
-
-def _sink_done(idx: int) -> None:
-    _SINK.written.add(idx)
-    # The write was just issued on (or handed over from) the current stream.  Autograd only joins the streams on which
-    # it accumulated a leaf gradient itself, and the sink's parameters never get there, so whoever applies the
-    # gradients must wait for every stream recorded here (a predictor's backward runs on the predictor side stream).
-    _SINK.used.add(torch.cuda.current_stream())
-    if _SINK.on_write is not None:
-        _SINK.on_write(idx)
-
-
-def _side_launch(compute, views, deps, idxs) -> None:
-    """run compute(views) on the sink's side stream now, or queue it (GradSink.defer)"""
-    if _SINK.defer:
-        for i in idxs:
-            _SINK.written.add(i)        # the slot is taken; the reducer hears about it when the launch is issued
-            _SINK.held.add(i)
-        # The operands are complete once the EMITTING stream gets here, and the flush may run on another stream (a
-        # predictor's recurrence on its side stream flushes gradients the main stream emitted): the item remembers its
-        # stream and the flush makes the side stream wait for that stream's position AT FLUSH TIME -- one join per
-        # (flush, emitting stream), however many items; a variant with one event per item measured 1.2 ms slower.
-        _SINK.pending.append((compute, views, deps, idxs, torch.cuda.current_stream()))
-        return
-    side = _SINK.stream
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        compute(views)
-    # the operands stay referenced until the step has joined the side stream (GradSink.keep): nothing can recycle or
-    # overwrite them under the side stream, and no record_stream bookkeeping is needed
-    _SINK.keep.append(deps)
-    for i in idxs:
-        _sink_done(i)
-
-
-def flush_begin():
-    """First half of a flush: joins the side stream with the emitting streams NOW (so that it does not wait for whatever
-    the caller launches next) and hands back the queued launches; flush_end issues them.  A recurrence's backward calls
-    flush_begin, launches its BPTT kernel, then flush_end: the persistent kernel (all of whose workgroups must become
-    co-resident) is dispatched before the GEMMs that would otherwise fill every CU's registers first."""
-    sink = _SINK
-    if sink is None or not sink.pending:
-        return None
-    side = sink.stream
-    pend, sink.pending = sink.pending, []
-    seen = []
-    for _, _, _, _, st in pend:
-        if st not in seen:
-            seen.append(st)
-            side.wait_stream(st)
-    return pend
-
-
-def flush_end(pend) -> None:
-    if not pend:
-        return
-    sink = _SINK
-    side = sink.stream
-    with torch.cuda.stream(side):
-        for compute, views, deps, idxs, _ in pend:
-            compute(views)
-            sink.keep.append(deps)
-    for _, _, _, idxs, _ in pend:
-        for i in idxs:
-            sink.held.discard(i)
-            if sink.on_write is not None:
-                sink.on_write(i)
-
-
-class batched_side_launches:
-    """`with batched_side_launches():` -- the side-stream weight gradients (and 'light' bias-gradient sums) emitted inside
-    are queued and issued together at the end: ONE stream join and ONE stream switch for the lot instead of one per
-    parameter (a FastPitch step emitted 88 of them one by one: 3.2 ms of host time in torch's stream calls).  No-op
-    without a sink or when the sink defers already (recurrent models flush before their BPTT kernels instead)."""
-
-    def __enter__(self):
-        self.on = _SINK is not None and not _SINK.defer
-        if self.on:
-            _SINK.defer = True
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            flush_end(flush_begin())
-            _SINK.defer = False
-        return False
-
-
-def flush_deferred() -> None:
-    """issue every queued side-stream weight gradient (no-op without a deferring sink), then the ones kept for the end of
-    the main stream's chain (GradSink.late)"""
-    flush_end(flush_begin())
-    sink = _SINK
-    if sink is not None and sink.late:
-        late, sink.late = sink.late, []
-        for compute, view, deps, idx in late:
-            compute(view)
-            sink.keep.append(deps)
-            sink.held.discard(idx)
-            sink.used.add(torch.cuda.current_stream())
-            if sink.on_write is not None:
-                sink.on_write(idx)
-
-
-def _emit(w: torch.Tensor, compute, deps=(), heavy=True, late: bool = False, inline_ok: bool = True):
-    """Produces the gradient of parameter `w`: compute(out) must overwrite `out` (same shape as w).
-    Without a sink: returns a fresh tensor (autograd accumulates it).  With a sink: writes the flat-buffer
-    view (on the side stream when `heavy`) and returns None.  heavy='light': a small reduction (bias gradient) that nothing
-    on the step's critical stream waits for -- it joins the queued side-stream launches of a deferring sink (22 column
-    sums + finalizes = 0.4 ms of the ForwardTacotron step's main stream) and stays inline otherwise."""
-    ent = _sink_view(w)
-    if ent is None:
-        out = torch.empty_like(w)
-        compute(out)
-        return out
-    idx, view = ent
-    if late and _SINK.late_ok and _SINK.defer:
-        _SINK.written.add(idx)
-        _SINK.held.add(idx)             # claimed; the all-reduce hears about it when it is issued
-        _SINK.late.append((compute, view, deps, idx))
-        return None
-    if heavy == 'light':
-        heavy = _SINK.defer and bool(deps) and os.environ.get('FT_BIAS_GRADS_SIDE', '1') == '1'
-    side = _SINK.stream if heavy else None
-    if side is not None and inline_ok and deps and deps[0].numel() // deps[0].shape[-1] <= _SINK.inline_rows:
-        side = None                     # short (token-side) operands: see GradSink.inline_rows
-    if side is None:
-        compute(view)
-        _sink_done(idx)
-    else:
-        _side_launch(compute, view, deps, (idx,))
-    return None
-
-
-def _emit_multi(ws, compute, deps=(), heavy=True):
-    """_emit for several parameters whose gradients one launch produces together: compute(outs).  heavy='light': as in
-    _emit (joins a batch of queued side-stream launches, inline otherwise)."""
-    ents = [_sink_view(w) for w in ws]
-    if any(e is None for e in ents):
-        outs = [torch.empty_like(w) for w in ws]
-        compute(outs)
-        return outs
-    if heavy == 'light':
-        heavy = _SINK.defer and bool(deps) and os.environ.get('FT_BIAS_GRADS_SIDE', '1') == '1'
-    side = _SINK.stream if heavy else None
-    if side is not None and deps and deps[0].numel() // deps[0].shape[-1] <= _SINK.inline_rows:
-        side = None
-    views = [e[1] for e in ents]
-    if side is None:
-        compute(views)
-        for e in ents:
-            _sink_done(e[0])
-    else:
-        _side_launch(compute, views, deps, tuple(e[0] for e in ents))
-    return [None] * len(ws)
-
-
-def _emit_copies(ws, values):
-    """_emit_copy for several parameters at once: one launch for all the slots the sink still has open."""
-    ents = [_sink_view(w) for w in ws]
-    outs = [v if e is None else None for e, v in zip(ents, values)]
-    todo = [(e, v) for e, v in zip(ents, values) if e is not None]
-    if todo:
-        H.copy_segments([v for _, v in todo], [e[1] for e, _ in todo])
-        for e, _ in todo:
-            _sink_done(e[0])
-    return outs
-
-
-def _emit_copy(w: torch.Tensor, value: torch.Tensor):
-    """Small vector gradients that a fused kernel already produced in `value`."""
-    ent = _sink_view(w)
-    if ent is None:
-        return value
-    ent[1].copy_(value.view_as(ent[1]))
-    _sink_done(ent[0])
-    return None
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -290,7 +44,7 @@ class EmbeddingFn(Function):
         idx, w = ctx.saved_tensors
         dout = _c(dout)
         V = w.shape[0]
-        dw = _emit(w, lambda out: H.embedding_bwd(idx, dout, V, EmbeddingFn._onehot_cache, out=out), (dout, idx))
+        dw = emit(w, lambda out: H.embedding_bwd(idx, dout, V, EmbeddingFn._onehot_cache, out=out), (dout, idx))
         return None, dw
 
 
@@ -322,10 +76,10 @@ class LinearFn(Function):
             else:
                 H.linear_bwd_weight_raw(dy.data_ptr(), out_f, x.data_ptr(), in_f, out, rows, in_f, out_f)
 
-        dw = _emit(w, wgrad, (dy, x))
+        dw = emit(w, wgrad, (dy, x))
         db = None
         if b is not None:
-            db = _emit(b, lambda out: H.colsum_raw(dy.data_ptr(), out_f, out, rows, out_f), (dy,), heavy='light')
+            db = emit(b, lambda out: H.colsum_raw(dy.data_ptr(), out_f, out, rows, out_f), (dy,), heavy='light')
         return dx, dw, db, None
 
 
@@ -370,20 +124,17 @@ class BatchNormConvFn(Function):
         B, T, Cin = x.shape
         Cout, _, k = w.shape
         Tbuf = y.shape[1]
-        eg, eb = _sink_view(gamma), _sink_view(beta)
+        eg, eb = claim(gamma), claim(beta)          # bn_bwd writes the two slots itself
         dy, dgamma, dbeta = H.bn_bwd(dout, y, gamma, mean, rstd, group=0, relu=ctx.relu,
                                      dgamma=eg[1] if eg else None, dbeta=eb[1] if eb else None)
-        if eg:
-            _sink_done(eg[0])
-            dgamma = None
-        if eb:
-            _sink_done(eb[0])
-            dbeta = None
+        if eg or eb:
+            installed().announce([e[0] for e in (eg, eb) if e])
+        dgamma, dbeta = None if eg else dgamma, None if eb else dbeta
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             H.conv1d_bwd_data_raw(dy.data_ptr(), Cout, wp, dx, B, T, Tbuf, Tbuf, False, w=w)
-        dw = _emit(w, lambda out: H.conv1d_bwd_weight_raw(dy.data_ptr(), Cout, x, out, Tbuf, Tbuf), (dy, x))
+        dw = emit(w, lambda out: H.conv1d_bwd_weight_raw(dy.data_ptr(), Cout, x, out, Tbuf, Tbuf), (dy, x))
         dres = dout if ctx.has_res else None
         return dx, dw, dgamma, dbeta, dres, None, None, None
 
@@ -431,17 +182,17 @@ class ConvBankFn(Function):
             dy, dgamma, dbeta = H.bn_bwd(dz, ybank, gamma, mean, rstd, group=C, relu=True)
         dx = H.conv_bank_bwd_data(dy, wp_all, K, C, Cin, T, ws=ws) if ctx.needs_input_grad[0] else None
         if C % 128 == 0:        # all members' weight gradients in one launch
-            dws = _emit_multi(ws, lambda outs: H.conv_bank_bwd_weight(dy, x, outs, C), (dy, x))
+            dws = emit(ws, lambda outs: H.conv_bank_bwd_weight(dy, x, outs, C), (dy, x))
         else:
             dws = []
             for i in range(K):
                 k = i + 1
                 Tvalid = T + (1 if k % 2 == 0 else 0)
                 dptr = dy.data_ptr() + i * C * _F4
-                dws.append(_emit(ws[i], lambda out, dptr=dptr, Tvalid=Tvalid: H.conv1d_bwd_weight_raw(
+                dws.append(emit(ws[i], lambda out, dptr=dptr, Tvalid=Tvalid: H.conv1d_bwd_weight_raw(
                     dptr, K * C, x, out, T + 1, Tvalid), (dy, x)))
-        both = _emit_copies(list(gs) + list(bs), [dgamma[i * C:(i + 1) * C] for i in range(K)] +
-                            [dbeta[i * C:(i + 1) * C] for i in range(K)])
+        both = emit_copies(list(gs) + list(bs), [dgamma[i * C:(i + 1) * C] for i in range(K)] +
+                           [dbeta[i * C:(i + 1) * C] for i in range(K)])
         dgs, dbs = both[:K], both[K:]
         return (dx, None, None, None, None, None, *dws, *dgs, *dbs)
 
@@ -488,11 +239,11 @@ class HighwayFn(Function):
         d12, dx = H.highway_gate_bwd(_c(dout), x12, x)
         p = d12.data_ptr()
         H.linear_bwd_data_multi([p, p + C * _F4], 2 * C, [w1, w2], dx, rows, C, accumulate=True)
-        dw1 = _emit(w1, lambda out: H.linear_bwd_weight_raw(p, 2 * C, x.data_ptr(), C, out, rows, C, C), (d12, x))
-        dw2 = _emit(w2, lambda out: H.linear_bwd_weight_raw(p + C * _F4, 2 * C, x.data_ptr(), C, out, rows, C, C),
-                    (d12, x))
-        db1 = _emit(b1, lambda out: H.colsum_raw(p, 2 * C, out, rows, C), (d12,), heavy='light')
-        db2 = _emit(b2, lambda out: H.colsum_raw(p + C * _F4, 2 * C, out, rows, C), (d12,), heavy='light')
+        dw1 = emit(w1, lambda out: H.linear_bwd_weight_raw(p, 2 * C, x.data_ptr(), C, out, rows, C, C), (d12, x))
+        dw2 = emit(w2, lambda out: H.linear_bwd_weight_raw(p + C * _F4, 2 * C, x.data_ptr(), C, out, rows, C, C),
+                   (d12, x))
+        db1 = emit(b1, lambda out: H.colsum_raw(p, 2 * C, out, rows, C), (d12,), heavy='light')
+        db2 = emit(b2, lambda out: H.colsum_raw(p + C * _F4, 2 * C, out, rows, C), (d12,), heavy='light')
         return dx, dw1, db1, dw2, db2
 
 
@@ -534,13 +285,13 @@ class HighwayStackFn(Function):
             x = xs[i]
             d12_below = H.highway_bwd_data(d12, w1, w2, dx, below=(x12s[i - 1], xs[i - 1]) if i > 0 else None)
             p = d12.data_ptr()
-            grads[4 * i] = _emit(w1, lambda out, p=p, x=x: H.linear_bwd_weight_raw(p, 2 * C, x.data_ptr(), C, out, rows, C, C),
-                                 (d12, x))
-            grads[4 * i + 2] = _emit(w2, lambda out, p=p, x=x: H.linear_bwd_weight_raw(p + C * _F4, 2 * C, x.data_ptr(), C, out,
-                                                                                    rows, C, C), (d12, x))
-            grads[4 * i + 1] = _emit(b1, lambda out, p=p: H.colsum_raw(p, 2 * C, out, rows, C), (d12,), heavy='light')
-            grads[4 * i + 3] = _emit(b2, lambda out, p=p: H.colsum_raw(p + C * _F4, 2 * C, out, rows, C), (d12,),
-                                     heavy='light')
+            grads[4 * i] = emit(w1, lambda out, p=p, x=x: H.linear_bwd_weight_raw(p, 2 * C, x.data_ptr(), C, out, rows, C, C),
+                                (d12, x))
+            grads[4 * i + 2] = emit(w2, lambda out, p=p, x=x: H.linear_bwd_weight_raw(p + C * _F4, 2 * C, x.data_ptr(), C, out,
+                                                                                   rows, C, C), (d12, x))
+            grads[4 * i + 1] = emit(b1, lambda out, p=p: H.colsum_raw(p, 2 * C, out, rows, C), (d12,), heavy='light')
+            grads[4 * i + 3] = emit(b2, lambda out, p=p: H.colsum_raw(p + C * _F4, 2 * C, out, rows, C), (d12,),
+                                    heavy='light')
             d12 = d12_below
         return (dx, *grads)
 
@@ -575,15 +326,15 @@ def _rnn_param_grads(dxp, dhp, x, hid, G, Hh, params, need_dx, late_last=False):
     if dx is not None:          # both directions' input-projection data gradients in one chained launch
         H.linear_bwd_data_multi([dxp.data_ptr(), dxp.data_ptr() + GH * _F4], 2 * GH, [params[0], params[4]], dx,
                                 rows, GH, dy_tm_B=B, dx_tm_B=0)
-    gb = _emit_copies([params[2], params[3], params[6], params[7]],
-                      [dbx[0:GH], dbh[0:GH], dbx[GH:2 * GH], dbh[GH:2 * GH]])
+    gb = emit_copies([params[2], params[3], params[6], params[7]],
+                     [dbx[0:GH], dbh[0:GH], dbx[GH:2 * GH], dbh[GH:2 * GH]])
     for d in range(2):
         w_ih, w_hh = params[4 * d], params[4 * d + 1]
         px = dxp.data_ptr() + d * GH * _F4
         ph = dhp.data_ptr() + d * GH * _F4
-        g_ih = _emit(w_ih, lambda out, px=px: H.linear_bwd_weight_raw(
+        g_ih = emit(w_ih, lambda out, px=px: H.linear_bwd_weight_raw(
             px, 2 * GH, x.data_ptr(), I, out, rows, I, GH, B=B, T=T, dy_tm=True, x_tm=False), (dxp, x))
-        g_hh = _emit(w_hh, lambda out, ph=ph, d=d: H.linear_bwd_weight_raw(
+        g_hh = emit(w_hh, lambda out, ph=ph, d=d: H.linear_bwd_weight_raw(
             ph, 2 * GH, hid.data_ptr() + d * Hh * _F4, 2 * Hh, out, rows, Hh, GH, B=B, T=T,
             x_shift=-1 if d == 0 else 1, dy_tm=True, x_tm=True), (dhp, hid), late=late_last and d == 1)
         grads += [g_ih, g_hh, gb[2 * d], gb[2 * d + 1]]
@@ -669,7 +420,7 @@ class BiLSTMFn(Function):
         dg = H.lstm_bwd(dout_tm, raw, cst, gates, H.transpose2d(params[1]),
                         H.transpose2d(params[5]), lens if ctx.has_lens else None, Hh)
         flush_end(pend)
-        # (one of the decoder LSTM's four weight gradients may run at the end of the main stream's chain: GradSink.late)
+        # (one of the decoder LSTM's four weight gradients may run at the end of the main stream's chain: gradsink.Policy.late_ok)
         dx, g = _rnn_param_grads(dg, dg, x, raw, 4, Hh, params, ctx.needs_input_grad[0], late_last=True)
         return (dx, None, None, *g)
 
@@ -740,16 +491,16 @@ class LRBiLSTMFn(Function):
             dx = torch.empty_like(x)
             H.linear_bwd_data_multi([dP.data_ptr(), dP.data_ptr() + GH * _F4], 2 * GH, [params[0], params[4]], dx,
                                     B * Tx, GH)
-        gb = _emit_copies([params[2], params[3], params[6], params[7]], [db[0:GH], db[0:GH], db[GH:], db[GH:]])
+        gb = emit_copies([params[2], params[3], params[6], params[7]], [db[0:GH], db[0:GH], db[GH:], db[GH:]])
         grads: List[Optional[torch.Tensor]] = []
         for d in range(2):
             w_ih, w_hh = params[4 * d], params[4 * d + 1]
             px = dP.data_ptr() + d * GH * _F4
             ph = dg.data_ptr() + d * GH * _F4
             # (token-level operands, but not the step's tail: they go to the side stream like every frame-side gradient)
-            g_ih = _emit(w_ih, lambda out, px=px: H.linear_bwd_weight_raw(px, 2 * GH, x.data_ptr(), I, out, B * Tx, I, GH),
-                         (dP, x), inline_ok=False)
-            g_hh = _emit(w_hh, lambda out, ph=ph, d=d: H.linear_bwd_weight_raw(
+            g_ih = emit(w_ih, lambda out, px=px: H.linear_bwd_weight_raw(px, 2 * GH, x.data_ptr(), I, out, B * Tx, I, GH),
+                        (dP, x), inline_ok=False)
+            g_hh = emit(w_hh, lambda out, ph=ph, d=d: H.linear_bwd_weight_raw(
                 ph, 2 * GH, raw.data_ptr() + d * Hh * _F4, 2 * Hh, out, B * T, Hh, GH, B=B, T=T,
                 x_shift=-1 if d == 0 else 1, dy_tm=True, x_tm=True), (dg, raw), late=d == 1)
             grads += [g_ih, g_hh, gb[2 * d], gb[2 * d + 1]]

@@ -183,7 +183,7 @@ class BucketedAllReduce:
         self.armed = False
         self.streams = set()
         self.seen = set()
-        self.held = None                # set of parameter indices a gradient sink still owes (ops.GradSink.held)
+        self.owes = None                # owes(j): a gradient sink still owes parameter j (gradsink.GradSink.owes)
         self.comm_stream = None
         self._hooks = []
         if not self.active:
@@ -204,7 +204,7 @@ class BucketedAllReduce:
         def hook(p):
             # a gradient sink that has claimed this parameter announces it itself, when its kernel is really issued
             # (deferred weight gradients are issued later than autograd visits the leaf)
-            if self.held is not None and j in self.held:
+            if self.owes is not None and self.owes(j):
                 return
             self.notify(j)
         return hook

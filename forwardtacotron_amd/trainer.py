@@ -26,12 +26,13 @@ to the per-step recurrence kernels and carries on.
 """
 import gc
 import os
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
 from . import _lib
+from . import gradsink
 from . import hip as H
 from . import ops
 from .base import AcousticModel
@@ -85,10 +86,10 @@ class TrainStep:
         self.wgrad_stream = self._make_wgrad_stream(dev, None if 'FT_WGRAD_CUS' in os.environ
                                                     else (28 if model.recurrent else 0))
         self.reducer.streams.add(self.wgrad_stream)
-        self.sink = ops.GradSink({p.data_ptr(): (i, p.grad) for i, p in enumerate(self.flat.params)},
-                                 stream=self.wgrad_stream, on_write=self.reducer.notify)
-        self.reducer.held = self.sink.held
-        self.sink.reducer_streams = self.reducer.streams     # streams a bucket's all-reduce must wait for
+        self.sink = gradsink.GradSink({p.data_ptr(): (i, p.grad) for i, p in enumerate(self.flat.params)},
+                                      stream=self.wgrad_stream, on_write=self.reducer.notify,
+                                      reducer_streams=self.reducer.streams)   # streams a bucket's all-reduce must wait for
+        self.reducer.owes = self.sink.owes
         self.packs: Optional[H.PackCache] = None
         self.main_stream = (torch.cuda.Stream(device=dev, priority=-1)
                             if os.environ.get('FT_MAIN_PRIORITY', '1') == '1' else None)
@@ -107,6 +108,7 @@ class TrainStep:
             self._did_freeze = False
         self._gc_frozen = True
         self.reducer.close()
+        self.reducer.owes = None
         self.sink.on_write = None
 
     @staticmethod
@@ -172,6 +174,41 @@ class TrainStep:
             plan = H.rnn_plan(3, True, int(B), 64, int(h))
             return 0.0 if plan is None else (plan['aligned'] or plan['spread']) / 32.0 * 100.0
         return demand(post.hidden_size) + max(demand(r.hidden_size) for r in preds) <= H._lib.lib().ft_rnn_admit_budget_pct()
+
+    @staticmethod
+    def _backward_order(independent: bool, recurrent: bool, has_cut: bool, pred_first: bool, switches) -> Tuple[str, bool]:
+        """-> (the step's backward calls in order, whether late weight gradients are allowed: gradsink.Policy.late_ok), from
+        the model's kind, whether its forward left a cut below the LSTM, whether the predictors' stage may go first
+        (_predictors_first) and the switches (a mapping: os.environ)."""
+        # EARLY predictor backward (FT_PRED_BWD_EARLY=1, off by default): the predictors' loss terms depend on nothing but
+        # the predictors' own outputs and the batch's targets (forward_trainer.py:86-93), so their whole backward can be
+        # issued on the predictors' stream right behind their forward, INSIDE the model's forward (model.predictor_hook),
+        # beside the trunk's forward recurrences instead of in the tail of the step.  Measured (DESIGN.md, round-2 table):
+        # the tail does not get shorter (it is bound by the main stream's own chain and the LSTM's weight gradients, the
+        # predictors' stage ran in their shadow) while the LSTM's forward recurrence stretches 4.1 -> 5.5 ms beside the
+        # predictors' BPTT kernels: 24.6 -> 25.8 ms.  Same gradients bit for bit either way (tests run both).
+        if independent and switches.get('FT_PRED_BWD_EARLY', '0') == '1':
+            return 'early', False
+        # The predictor branches share nothing with the trunk (each has its own embedding; the trunk is fed the
+        # batch's pitch / energy / pitch_cond, forward_tacotron.py:129-159) and run on their own side stream.
+        # One backward over the summed loss issues their nodes LAST (autograd orders ready nodes by creation
+        # order, the predictors were created first): 1.9 ms of predictor BPTT + conv backward at the end of the
+        # step with the main stream idle.  Issued FIRST they collide with the trunk's recurrences instead (a
+        # persistent LSTM BPTT fills its XCD slots: it would wait for every queued predictor BPTT, +1 ms).  So
+        # the backward runs in three stages: postnet .. LSTM (down to the cut below the LSTM), then the
+        # predictors -- their BPTT kernels queue behind the LSTM's and run beside the prenet's GEMMs -- then
+        # LR .. prenet, whose GRU fits next to a predictor's.
+        if not (independent and recurrent and has_cut and switches.get('FT_STAGED_BACKWARD', '1') == '1'):
+            return 'single', False
+        if pred_first:
+            # The predictors' stage issued FIRST: it then runs beside the postnet GRU's BPTT and the postnet's conv
+            # backward -- the first 4 ms of the backward, of which 2 ms are a recurrence that leaves most of the chip
+            # idle -- instead of in the tail of the step, where it was the last stream to finish (the LSTM's BPTT,
+            # which fills its XCD slots, waits on the device for the predictors' BPTT kernels: they are long done).
+            # Only where the predictors' BPTT grids fit BESIDE the postnet GRU's (_predictors_first): otherwise they
+            # queue behind it and the stage delays the trunk (multispeaker: 38.0 -> 38.9 ms).
+            return 'pred-main-cut', switches.get('FT_WGRAD_LATE', '1') == '1'
+        return 'main-pred-cut', False
 
     def _weight_packs(self) -> H.PackCache:
         """the re-laid-out weight copies of this model (hip.PackCache), rebuilt only if the flat buffer moved"""
@@ -268,34 +305,28 @@ class TrainStep:
         H.pack_cache = packs
         old_precision = H.set_gemm_precision(model.matmul_dtype)    # forward AND backward
         independent = bool(model.independent_predictors)
-        # EARLY predictor backward (FT_PRED_BWD_EARLY=1, off by default): the predictors' loss terms depend on nothing but
-        # the predictors' own outputs and the batch's targets (forward_trainer.py:86-93), so their whole backward can be
-        # issued on the predictors' stream right behind their forward, INSIDE the model's forward (model.predictor_hook),
-        # beside the trunk's forward recurrences instead of in the tail of the step.  Measured:
-        # the tail does not get shorter (it is bound by the main stream's own chain and the LSTM's weight gradients, the
-        # predictors' stage ran in their shadow) while the LSTM's forward recurrence stretches 4.1 -> 5.5 ms beside the
-        # predictors' BPTT kernels: 24.6 -> 25.8 ms.  Same gradients bit for bit either way (tests run both).
-        early = independent and os.environ.get('FT_PRED_BWD_EARLY', '0') == '1'
-        # staged backward (see below): only this trainer asks the model to cut its graph below the LSTM
-        staged = (not early and independent and model.recurrent
-                  and os.environ.get('FT_STAGED_BACKWARD', '1') == '1')
+        # what the step does if the model cuts its graph below the LSTM (only this trainer asks it to): see _backward_order
+        order, _ = self._backward_order(independent, model.recurrent, True, False, os.environ)
+        early, staged = order == 'early', order == 'main-pred-cut'
         model.stage_backward = staged
         model._cut = None
         side_terms: Dict[str, torch.Tensor] = {}
 
-        def arm_sink():
-            self.sink.inline_rows = int(model.wgrad_inline_rows)
-            # models with recurrences queue their side-stream weight gradients and issue them beside the next BPTT kernel
-            self.sink.defer = bool(model.wgrad_defer) and os.environ.get('FT_WGRAD_DEFER', '1') == '1'
+        def set_policy(late_ok: bool = False) -> None:
+            # the step's schedule switches, read once; models with recurrences queue their side-stream weight gradients
+            # and issue them beside the next BPTT kernel
+            self.sink.set_policy(inline_rows=model.wgrad_inline_rows,
+                                 defer=bool(model.wgrad_defer) and os.environ.get('FT_WGRAD_DEFER', '1') == '1',
+                                 late_ok=late_ok, bias_side=os.environ.get('FT_BIAS_GRADS_SIDE', '1') == '1')
 
         def predictor_hook(p: Dict[str, torch.Tensor]) -> None:
             # called by the model on the predictors' stream, right behind their forward
-            arm_sink()
+            set_policy()
             # the LengthRegulator clamps batch['dur'] in place (on the main stream, possibly at this very moment) and the
             # reference's loss sees the clamped tensor (forward_trainer.py:79-86): clamp a copy, either read gives the same
             terms, root = self.side_losses(p, batch, pitch_target, energy_target, dur_target=batch['dur'].clamp(min=0.0))
             root.backward()                 # ends by joining the CALLING stream (this one) with the streams it used
-            self.sink.used.add(torch.cuda.current_stream())
+            self.sink.wrote_on(torch.cuda.current_stream())
             side_terms.update({k: v.detach() for k, v in terms.items()})
             side_terms['_root'] = root.detach()
 
@@ -305,38 +336,31 @@ class TrainStep:
             self.sink.begin_step()
             if early:
                 model.predictor_hook = predictor_hook
-                ops.set_grad_sink(self.sink)
+                gradsink.install(self.sink)
             try:
                 pred = model(batch)
             finally:
                 model.stage_backward = False
                 model.predictor_hook = None
-            arm_sink()
-            ops.set_grad_sink(self.sink)
+            gradsink.install(self.sink)
             for v in side_terms.values():       # allocated on the predictors' stream, read from here on
                 v.record_stream(torch.cuda.current_stream())
             if early and '_root' in side_terms:
                 m1 = ops.masked_l1(pred['mel'], batch['mel'], batch['mel_len'])
                 m2 = ops.masked_l1(pred['mel_post'], batch['mel'], batch['mel_len'])
                 (m1 + m2).backward()
-                ops.flush_deferred()
+                self.sink.flush_all()
                 L = dict(mel=m1, mel_post=m2, **{k: v for k, v in side_terms.items() if k != '_root'})
                 L['loss'] = m1.detach() + m2.detach() + side_terms['_root']
             else:
                 L = self.losses(pred, batch, pitch_target, energy_target)
-                # The predictor branches share nothing with the trunk (each has its own embedding; the trunk is fed the
-                # batch's pitch / energy / pitch_cond, forward_tacotron.py:129-159) and run on their own side stream.
-                # One backward over the summed loss issues their nodes LAST (autograd orders ready nodes by creation
-                # order, the predictors were created first): 1.9 ms of predictor BPTT + conv backward at the end of the
-                # step with the main stream idle.  Issued FIRST they collide with the trunk's recurrences instead (a
-                # persistent LSTM BPTT fills its XCD slots: it would wait for every queued predictor BPTT, +1 ms).  So
-                # the backward runs in three stages: postnet .. LSTM (down to the cut below the LSTM), then the
-                # predictors -- their BPTT kernels queue behind the LSTM's and run beside the prenet's GEMMs -- then
-                # LR .. prenet, whose GRU fits next to a predictor's.
                 side_root, main_root = L.pop('_roots')
                 cut = model._cut
                 model._cut = None
                 first = staged and cut is not None and self._predictors_first(model, int(batch['x'].shape[0]))
+                # (early, but the model never called the hook: one backward)
+                order, late_ok = ('single', False) if early else self._backward_order(
+                    independent, model.recurrent, cut is not None, first, os.environ)
 
                 def predictors_backward():
                     # backward() ends by making the CALLING stream wait for every stream it ran nodes on: called from
@@ -348,37 +372,20 @@ class TrainStep:
                     with torch.cuda.stream(pstream):
                         side_root.backward()
                     side_root.record_stream(pstream)
-                    self.sink.used.add(pstream)
+                    self.sink.wrote_on(pstream)
 
-                self.sink.late_ok = first and os.environ.get('FT_WGRAD_LATE', '1') == '1'
-                if first:
-                    # The predictors' stage issued FIRST: it then runs beside the postnet GRU's BPTT and the postnet's conv
-                    # backward -- the first 4 ms of the backward, of which 2 ms are a recurrence that leaves most of the chip
-                    # idle -- instead of in the tail of the step, where it was the last stream to finish (the LSTM's BPTT,
-                    # which fills its XCD slots, waits on the device for the predictors' BPTT kernels: they are long done).
-                    # Only where the predictors' BPTT grids fit BESIDE the postnet GRU's (_predictors_first): otherwise they
-                    # queue behind it and the stage delays the trunk (multispeaker: 38.0 -> 38.9 ms).
-                    predictors_backward()
-                    main_root.backward()
-                    cut[0].backward(cut[1].grad)
-                elif staged and cut is not None:
-                    main_root.backward()
-                    predictors_backward()
-                    cut[0].backward(cut[1].grad)
-                else:
-                    L['loss'].backward()
-                ops.flush_deferred()
+                set_policy(late_ok)
+                stages = {'pred': predictors_backward, 'main': main_root.backward,
+                          'cut': lambda: cut[0].backward(cut[1].grad), 'single': L['loss'].backward}
+                for stage in order.split('-'):
+                    stages[stage]()
+                self.sink.flush_all()
         finally:
-            ops.set_grad_sink(None)
+            gradsink.install(None)
             H.pack_cache = None
             packs.release()
             H.set_gemm_precision(old_precision)
-        cur = torch.cuda.current_stream()
-        cur.wait_stream(self.wgrad_stream)
-        for st in self.sink.used:               # e.g. the predictors' side stream: its backward wrote gradients too
-            if st != cur and st != self.wgrad_stream:
-                cur.wait_stream(st)
-        self.sink.keep.clear()                  # joined: nothing reads the side launches' operands any more
+        self.sink.join(torch.cuda.current_stream())
         self.reducer.finish()
         self.optimizer_step()
         out = {k: v.detach() for k, v in L.items()}

@@ -120,34 +120,34 @@ def test_mid_size_train_step_vs_oracle():
 
 
 def test_deferred_weight_gradients_wait_for_the_emitting_stream():
-    """A queued (GradSink.defer) weight gradient may be flushed from ANOTHER stream than the one that emitted it (a
+    """A queued (gradsink.Policy.defer) weight gradient may be flushed from ANOTHER stream than the one that emitted it (a
     predictor's recurrence on its side stream flushes what the main stream queued): the side stream must then wait for
     the EMITTING stream's position, not the flusher's.  Stream A is held up by a long spin before it produces the
     operand; the flush comes from an idle stream B right away."""
-    from forwardtacotron_amd import ops
+    from forwardtacotron_amd import gradsink
     dev = torch.device('cuda')
     w = torch.zeros(1 << 20, device=dev)
     view = torch.full_like(w, -1.0)
     src = torch.zeros_like(w)
     A, B_, side = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
-    sink = ops.GradSink({w.data_ptr(): (0, view)}, stream=side)
-    sink.defer = True
+    sink = gradsink.GradSink({w.data_ptr(): (0, view)}, stream=side)
+    sink.set_policy(defer=True)
     sink.begin_step()
-    ops.set_grad_sink(sink)
+    gradsink.install(sink)
     try:
         torch.cuda.synchronize()
         with torch.cuda.stream(A):
             torch.cuda._sleep(200_000_000)                  # ~0.1 s: the operand is NOT ready for a long time
             src.fill_(3.0)
-            r = ops._emit(w, lambda out: out.copy_(src), (src.view(1024, -1),))
+            r = gradsink.emit(w, lambda out: out.copy_(src), (src.view(1024, -1),))
             assert r is None and sink.pending and 0 in sink.held
         with torch.cuda.stream(B_):
-            ops.flush_deferred()
+            sink.flush_all()
         assert not sink.pending and not sink.held
         torch.cuda.synchronize()
         assert float(view.min()) == 3.0 and float(view.max()) == 3.0
     finally:
-        ops.set_grad_sink(None)
+        gradsink.install(None)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -283,13 +283,16 @@ def test_recurrence_fault_fallback_policy_continues_on_per_step_kernels():
 
 
 @pytest.mark.parametrize('env', [{'FT_PRED_BWD_EARLY': '1'}, {'FT_STAGED_BACKWARD': '0'}, {'FT_PRED_STAGE_FIRST': '0'},
-                                 {'FT_WGRAD_LATE': '0'}, {'FT_WGRAD_CUS': '0'}])
+                                 {'FT_WGRAD_LATE': '0'}, {'FT_WGRAD_CUS': '0'}, {'FT_BIAS_GRADS_SIDE': '0'},
+                                 {'FT_WGRAD_DEFER': '0'}])
 def test_step_schedule_variants_give_the_same_update(env, monkeypatch):
     """The backward of a step can be scheduled in several ways -- three stages with the predictors' stage first (the
     default where their BPTT grids fit beside the postnet GRU's) or in the middle, one backward call, the predictors' backward issued from inside the forward (model.predictor_hook), the
     weight-gradient stream unrestricted instead of limited to 28 CUs per XCD (ft_stream_create_cu_limited: fewer slots,
     so the weight-gradient planner picks other split counts -- the slabs are still summed in a fixed order, but a
-    different one: this variant is compared to rounding, the others bit for bit) -- and every parameter's gradient
+    different one: this variant is compared to rounding, the others bit for bit), the bias-gradient sums inline instead
+    of queued for the side stream, the side-stream weight gradients launched where they are emitted instead of beside the
+    next recurrence (only the issue time changes, neither the kernel nor its grid) -- and every parameter's gradient
     is written by exactly one kernel launch in all of them: the update must not depend on the schedule, bit for bit.
     The batch has a negative duration: the LengthRegulator clamps it in place and the duration loss must see the clamped
     value whichever stream computes it first (forward_trainer.py:79-86)."""

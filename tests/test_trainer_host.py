@@ -22,3 +22,48 @@ def test_predictor_stage_goes_first_only_where_its_bptt_grids_fit_beside_the_pos
     assert TrainStep._predictors_first(single, 32) is False
     monkeypatch.setenv('FT_PRED_STAGE_FIRST', '1')
     assert TrainStep._predictors_first(multi, 64) is True
+
+
+# (independent predictors, recurrent trunk, the forward left a cut, switches) -> (order, late_ok).  `first` is what
+# _predictors_first says for the model: the single-speaker flagship at bs = 32 (True) unless FT_PRED_STAGE_FIRST overrides.
+ORDERS = [
+    (True, True, True, {}, ('pred-main-cut', True)),                                # the flagship's default
+    (True, True, True, {'FT_WGRAD_LATE': '0'}, ('pred-main-cut', False)),
+    (True, True, True, {'FT_PRED_STAGE_FIRST': '1'}, ('pred-main-cut', True)),
+    (True, True, True, {'FT_PRED_STAGE_FIRST': '0'}, ('main-pred-cut', False)),     # late only with the predictors first
+    (True, True, True, {'FT_PRED_STAGE_FIRST': '0', 'FT_WGRAD_LATE': '1'}, ('main-pred-cut', False)),
+    (True, True, True, {'FT_STAGED_BACKWARD': '0'}, ('single', False)),
+    (True, True, True, {'FT_STAGED_BACKWARD': '0', 'FT_PRED_STAGE_FIRST': '1'}, ('single', False)),
+    (True, True, True, {'FT_PRED_BWD_EARLY': '1'}, ('early', False)),
+    (True, True, True, {'FT_PRED_BWD_EARLY': '1', 'FT_PRED_STAGE_FIRST': '1'}, ('early', False)),
+    (True, True, True, {'FT_PRED_BWD_EARLY': '1', 'FT_STAGED_BACKWARD': '0'}, ('early', False)),
+    (True, True, False, {}, ('single', False)),                                     # the model made no cut
+    (True, True, False, {'FT_PRED_STAGE_FIRST': '1'}, ('single', False)),
+    (True, False, False, {}, ('single', False)),                                    # no recurrent trunk (FastPitch)
+    (True, False, False, {'FT_PRED_STAGE_FIRST': '1'}, ('single', False)),
+    (True, False, False, {'FT_PRED_BWD_EARLY': '1'}, ('early', False)),
+    (False, True, False, {}, ('single', False)),                                    # no independent predictors
+    (False, True, False, {'FT_PRED_BWD_EARLY': '1'}, ('single', False)),
+    (False, True, True, {'FT_PRED_STAGE_FIRST': '1'}, ('single', False)),
+    (False, False, False, {'FT_PRED_BWD_EARLY': '1'}, ('single', False)),
+]
+
+
+def test_backward_order_table(monkeypatch):
+    """TrainStep._backward_order: one row per reachable combination of model kind, cut and switches.  (Before the
+    forward _step asks the model for a cut iff the same function, with a cut assumed, stages the backward.)"""
+    from forwardtacotron_amd.model import ForwardTacotron
+    from forwardtacotron_amd.trainer import TrainStep
+    single = ForwardTacotron(**data.SINGLESPEAKER_MODEL)
+    for independent, recurrent, has_cut, switches, want in ORDERS:
+        for k in ('FT_PRED_STAGE_FIRST', 'FT_PRED_BWD_EARLY', 'FT_STAGED_BACKWARD', 'FT_WGRAD_LATE'):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in switches.items():
+            monkeypatch.setenv(k, v)
+        first = TrainStep._predictors_first(single, 32)
+        assert first is (switches.get('FT_PRED_STAGE_FIRST', '1') == '1')
+        got = TrainStep._backward_order(independent, recurrent, has_cut, first, switches)
+        assert got == want, (independent, recurrent, has_cut, switches, got)
+    # the predictors may not go first (the multispeaker model's admission arithmetic): in the middle, nothing late
+    assert TrainStep._backward_order(True, True, True, False, {}) == ('main-pred-cut', False)
+    assert TrainStep._backward_order(True, True, True, False, {'FT_WGRAD_LATE': '1'}) == ('main-pred-cut', False)

@@ -1,12 +1,14 @@
 """The C-ABI calls of fixed scenarios as text, to show that a host-side change changed nothing.
 
-    python tools/call_trace.py --out FILE [--only A,B,C,D]
+    python tools/call_trace.py --out FILE [--only A,B,C,D,E,F,G]
 
 Every launch of the package goes through _lib.call(name, *args).  For the duration of a scenario this tool replaces that
 function and writes one line per call: the entry name, then its arguments as _lib.PROTOS types them -- scalars
 verbatim, pointers as 0 (null) or 1, and a `void*` argument whose name contains `stream` as the ordinal of that
-handle's first appearance in the scenario (s0, s1, ...).  What the lines pin down is therefore which entries ran, in
-which order, on which stream, with which sizes, seeds and switches; behind each scenario follows one line per returned
+handle's first appearance in the scenario (s0, s1, ...).  torch.cuda.Stream.wait_stream is replaced for the same time and
+writes `wait sA <- sB` with the same ordinals; consecutive waits of one stream with no call between them commute and are
+written sorted (the train step's final join walks a set of streams, whose order follows the handles' addresses).  What the lines pin down is therefore which entries ran, in which order,
+on which stream, behind which stream joins, with which sizes, seeds and switches; behind each scenario follows one line per returned
 tensor (`= key sha256-of-its-bytes`), which pins down the result.  Run it on two commits with FT_LIB pointing at one
 build of the same C sources and `diff` the two files: an empty diff is the proof.
 
@@ -25,6 +27,14 @@ torch.manual_seed(0)):
      with FT_ATTN_LENS unset and =0 (all three attention routes)
   D  the same model in training mode, B = 2, Tx = 16: forward and backward of the summed outputs in fp32 (per-operation
      nodes), bf16 (the C-issued composite) and bf16 with FT_FFT_COMPOSITE=0 (TransformerFn's Python loop)
+  E  ForwardTacotron, tiny_model.npz: two TrainStep.step calls from fresh weights -> the loss terms and every parameter;
+     under the default switches, under each input of test_step_schedule_variants_give_the_same_update and under
+     FT_PRED_STAGE_FIRST=1 (with =0 among the former: late weight gradients on and off whatever the admission arithmetic
+     says at these widths)
+  F  MultiForwardTacotron, tiny_multi.npz: the same, default switches
+  G  FastPitch, the same two steps: tiny_fastpitch.npz in fp32 (one node per operation: every side launch on its own) and
+     with FT_TRANSFORMER_NODE=1 (TransformerFn's Python loop: a block's launches batched); scenario D's model and batch in
+     bf16 (the composite) and with FT_FFT_SUMS_STREAM=1 on top
 
 Needs a GPU: there is no CPU fallback.
 """
@@ -41,7 +51,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from forwardtacotron_amd import _lib, data  # noqa: E402
-from helpers import TINY, TINY_FP, fp_state, load_npz, sub  # noqa: E402
+from helpers import TINY, TINY_FP, TINY_MULTI, TRAIN_CFG, TRAIN_CFG_MULTI, fp_state, load_npz, sub  # noqa: E402
 
 X_LEN = [40, 13, 1, 27, 40]
 
@@ -50,13 +60,13 @@ class Trace:
     """the lines of one output file; `scenario` swaps _lib.call for the time of one scenario"""
 
     def __init__(self):
-        self.lines, self.streams, self.calls = [], {}, 0
+        self.lines, self.streams, self.calls, self.waits = [], {}, 0, 0
 
     def _call(self, name, *args):
         out = [name]
         for (ctype, arg), v in zip(_lib.PROTOS[name][1], args):
             if ctype.replace(' ', '') == 'void*' and 'stream' in arg:
-                out.append(self.streams.setdefault(v or 0, f's{len(self.streams)}'))
+                out.append(self._ordinal(v))
             elif ctype.endswith('*'):
                 out.append('0' if v is None or v == 0 else '1')
             else:
@@ -65,23 +75,46 @@ class Trace:
         self.calls += 1
         return self._real(name, *args)
 
+    def _ordinal(self, handle):
+        return self.streams.setdefault(handle or 0, f's{len(self.streams)}')
+
     @contextlib.contextmanager
     def scenario(self, title):
         self.lines.append(f'## {title}')
-        self.streams, self.calls = {}, 0
+        self.streams, self.calls, self.waits = {}, 0, 0
+        real_wait = torch.cuda.Stream.wait_stream
+
+        def wait_stream(waiter, waited):
+            self.lines.append(f'wait {self._ordinal(waiter.cuda_stream)} <- {self._ordinal(waited.cuda_stream)}')
+            self.waits += 1
+            return real_wait(waiter, waited)
+
         self._real, _lib.call = _lib.call, self._call
+        torch.cuda.Stream.wait_stream = wait_stream
         try:
             yield
             torch.cuda.synchronize()
         finally:
             _lib.call = self._real
-        print(f'{title}: {self.calls} calls')
+            torch.cuda.Stream.wait_stream = real_wait
+        print(f'{title}: {self.calls} calls, {self.waits} stream waits')
 
     def result(self, out):
         for k in sorted(out):
             if torch.is_tensor(out[k]):
                 t = out[k].detach().cpu().contiguous()
                 self.lines.append(f'= {k} {tuple(t.shape)} {hashlib.sha256(t.numpy().tobytes()).hexdigest()}')
+
+
+def canonical(lines):
+    """the lines with every run of consecutive `wait sA <- ...` lines of one waiter sorted"""
+    out, run = [], []
+    for line in lines + ['']:
+        if run and not (line.startswith('wait ') and line.split()[1] == run[0].split()[1]):
+            out += sorted(run)
+            run = []
+        (run if line.startswith('wait ') else out).append(line)
+    return out[:-1]
 
 
 @contextlib.contextmanager
@@ -174,13 +207,81 @@ def scenario_d(tr):
             tr.result({f'grad/{k}': p.grad for k, p in m.named_parameters() if p.grad is not None})
 
 
-SCENARIOS = {'A': scenario_a, 'B': scenario_b, 'C': scenario_c, 'D': scenario_d}
+def train_steps(tr, title, make, batch, cfg, switches=None):
+    """two TrainStep.step calls of a fresh model (make() -> a model on the device) under `switches`"""
+    from forwardtacotron_amd.trainer import TrainStep
+    switches = switches or {}
+    with env(**switches):
+        torch.manual_seed(0)            # the dropout seeds
+        m = make()
+        ts = TrainStep(m, lr=2e-3, train_cfg=cfg)
+        with tr.scenario(title + ''.join(f', {k}={v}' for k, v in switches.items())):
+            for i in (1, 2):
+                out = ts.step({k: v.clone().cuda() for k, v in batch.items()})
+                tr.result({f'step{i}/{k}': v for k, v in out.items()})
+            ts.check()
+            tr.result({f'param/{k}': p for k, p in m.named_parameters()})
+        ts.close()
+
+
+# the inputs of tests/test_gpu_trainer.py::test_step_schedule_variants_give_the_same_update, then the predictors first
+STEP_SWITCHES = [{}, {'FT_PRED_BWD_EARLY': '1'}, {'FT_STAGED_BACKWARD': '0'}, {'FT_PRED_STAGE_FIRST': '0'},
+                 {'FT_WGRAD_LATE': '0'}, {'FT_WGRAD_CUS': '0'}, {'FT_BIAS_GRADS_SIDE': '0'}, {'FT_WGRAD_DEFER': '0'},
+                 {'FT_PRED_STAGE_FIRST': '1'}]
+
+
+def scenario_e(tr):
+    from forwardtacotron_amd.model import ForwardTacotron
+    M = load_npz('tiny_model.npz')
+
+    def make():
+        m = ForwardTacotron(**TINY)
+        m.load_state_dict(sub(M, 'sd/'))
+        return m.cuda()
+    for switches in STEP_SWITCHES:
+        train_steps(tr, 'E train steps', make, sub(M, 'batch/'), TRAIN_CFG, switches)
+
+
+def scenario_f(tr):
+    from forwardtacotron_amd.multi_model import MultiForwardTacotron
+    M = load_npz('tiny_multi.npz')
+
+    def make():
+        m = MultiForwardTacotron(**TINY_MULTI)
+        m.load_state_dict(sub(M, 'sd/'))
+        return m.cuda()
+    train_steps(tr, 'F train steps', make, sub(M, 'batch/'), TRAIN_CFG_MULTI)
+
+
+def scenario_g(tr):
+    from forwardtacotron_amd.fastpitch import FastPitch
+    Z = load_npz('tiny_fastpitch.npz')
+
+    def tiny():
+        m = FastPitch(**TINY_FP)
+        m.load_state_dict(fp_state(Z, 'sd/'))
+        return m.cuda()
+    train_steps(tr, 'G train steps tiny fp32', tiny, sub(Z, 'batch/'), TRAIN_CFG)
+    train_steps(tr, 'G train steps tiny fp32', tiny, sub(Z, 'batch/'), TRAIN_CFG, {'FT_TRANSFORMER_NODE': '1'})
+    cfg = production_fastpitch()[0]
+    batch = data.synthetic_batch(B=2, Tmax=16, n_mels=cfg['n_mels'], max_dur=6, seed=3)
+
+    def wide():
+        m = production_fastpitch()[1]
+        m.matmul_dtype = 'bf16'
+        return m
+    train_steps(tr, 'G train steps bf16 composite', wide, batch, TRAIN_CFG)
+    train_steps(tr, 'G train steps bf16 composite', wide, batch, TRAIN_CFG, {'FT_FFT_SUMS_STREAM': '1'})
+
+
+SCENARIOS = {'A': scenario_a, 'B': scenario_b, 'C': scenario_c, 'D': scenario_d, 'E': scenario_e, 'F': scenario_f,
+             'G': scenario_g}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', required=True)
-    ap.add_argument('--only', default='A,B,C,D')
+    ap.add_argument('--only', default='A,B,C,D,E,F,G')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('call_trace: needs an MI355X (no CPU fallback)')
@@ -190,7 +291,7 @@ def main():
         torch.manual_seed(0)
         SCENARIOS[key](tr)
     with open(a.out, 'w') as f:
-        f.write('\n'.join(tr.lines) + '\n')
+        f.write('\n'.join(canonical(tr.lines)) + '\n')
     print(f'{a.out}: {len(tr.lines)} lines')
 
 
