@@ -1626,3 +1626,90 @@ def spk_segment_mean_norm(rows: torch.Tensor, index: Optional[torch.Tensor], off
     _lib.call('ft_spk_segment_mean_norm', _p(rows), N, E, _p(index), _p(offsets), _p(count), S, int(normalize_rows),
               _p(out), _p(rows_out), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Tacotron teacher training (csrc/ft_taco_train.hip)
+# ---------------------------------------------------------------------------------------------------
+def taco_attend_bwd(ep: torch.Tensor, epq: torch.Tensor, P: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+                    b_hh: torch.Tensor, W: torch.Tensor, bW: torch.Tensor, cw: torch.Tensor, L: torch.Tensor,
+                    bL: torch.Tensor, v: torch.Tensor, hist: torch.Tensor, attn: torch.Tensor, dhist: torch.Tensor,
+                    ws: Optional[torch.Tensor] = None, alloc=torch.empty) -> dict:
+    """backward of ft_taco_attend from dhist [S,B,512] -> dict of dep, depq [B,Tx,256], dP [S,B,768], dw_ih_ctx [768,256]
+    (the gradient of w_ih[:, :256]; w_ih is [768, >= 256], only those columns are read), dw_hh, db_hh, dW, dbW, dcw, dL,
+    dbL, dv.  ws: a byte buffer of at least ft_taco_attend_bwd_workspace(B, Tx, S), or None for the stream's own."""
+    for n, t in (('ep', ep), ('epq', epq), ('P', P), ('w_ih', w_ih), ('w_hh', w_hh), ('b_hh', b_hh), ('W', W), ('bW', bW),
+                 ('cw', cw), ('L', L), ('bL', bL), ('v', v), ('hist', hist), ('attn', attn), ('dhist', dhist)):
+        _chk(t, n)
+    B, Tx, D = ep.shape
+    S = P.shape[0]
+    if (D != 256 or epq.shape != ep.shape or tuple(P.shape) != (S, B, 3 * D) or tuple(hist.shape) != (S, B, 2 * D)
+            or dhist.shape != hist.shape or tuple(attn.shape) != (B, S, Tx)):
+        raise _lib.FtError(f'taco_attend_bwd: inconsistent shapes ep {tuple(ep.shape)}, epq {tuple(epq.shape)}, P '
+                           f'{tuple(P.shape)}, hist {tuple(hist.shape)}, dhist {tuple(dhist.shape)}, attn {tuple(attn.shape)}')
+    nbytes = _lib.query('ft_taco_attend_bwd_workspace', B, Tx, S)
+    if nbytes == 0:
+        raise _lib.FtError(f'taco_attend_bwd: B >= 1, 1 <= Tx <= 1024 and S >= 1 are required (got B = {B}, Tx = {Tx}, '
+                           f'S = {S})')
+    if ws is None:
+        ws = workspace(nbytes, ep.device)
+    f32 = dict(dtype=torch.float32, device=ep.device)
+    out = dict(dep=alloc(B, Tx, D, **f32), depq=alloc(B, Tx, D, **f32), dP=alloc(S, B, 3 * D, **f32),
+               dw_ih_ctx=alloc(3 * D, D, **f32), dw_hh=alloc(3 * D, D, **f32), db_hh=alloc(3 * D, **f32),
+               dW=alloc(D, D, **f32), dbW=alloc(D, **f32), dcw=alloc(*cw.shape, **f32), dL=alloc(*L.shape, **f32),
+               dbL=alloc(D, **f32), dv=alloc(D, **f32))
+    _lib.call('ft_taco_attend_bwd', _p(ep), _p(epq), _p(P), _p(w_ih), w_ih.shape[1], _p(w_hh), _p(b_hh), _p(W), _p(bW),
+              _p(cw), _p(L), _p(bL), _p(v), _p(hist), _p(attn), _p(dhist), _p(out['dep']), _p(out['depq']), _p(out['dP']),
+              _p(out['dw_ih_ctx']), _p(out['dw_hh']), _p(out['db_hh']), _p(out['dW']), _p(out['dbW']), _p(out['dcw']),
+              _p(out['dL']), _p(out['dbL']), _p(out['dv']), B, Tx, S, _p(ws), ws.numel(), _stream())
+    return out
+
+
+def taco_lstm_zone_fwd(xp: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor, p: float, seed: int,
+                       alloc=torch.empty):
+    """nn.LSTMCell over the S steps of xp [S,B,4L] (x W_ih^T + b_ih) from zero states with zoneout p (mask of
+    ft_dropout(p, seed) over [S,B,L]: zoned where it is 0) -> (gates [S,B,4L] activated, c [S,B,L], zoned h [S,B,L])"""
+    _chk(xp, 'xp'); _chk(w_hh, 'w_hh'); _chk(b_hh, 'b_hh')
+    S, B, G = xp.shape
+    L = w_hh.shape[1]
+    if G != 4 * L or tuple(w_hh.shape) != (4 * L, L) or b_hh.numel() != 4 * L:
+        raise _lib.FtError(f'taco_lstm_zone_fwd: xp {tuple(xp.shape)}, w_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)}')
+    f32 = dict(dtype=torch.float32, device=xp.device)
+    gates, c, h = alloc(S, B, G, **f32), alloc(S, B, L, **f32), alloc(S, B, L, **f32)
+    _lib.call('ft_taco_lstm_zone_fwd', _p(xp), _p(w_hh), _p(b_hh), float(p), int(seed), _p(gates), _p(c), _p(h), B, S, L,
+              _stream())
+    return gates, c, h
+
+
+def taco_lstm_zone_bwd(dout: torch.Tensor, gates: torch.Tensor, c: torch.Tensor, w_hhT: torch.Tensor, p: float,
+                       seed: int, ws: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
+    """dout [S,B,L] = the gradient of the zoned h; w_hhT [L,4L] -> dxp [S,B,4L], the gradient of the pre-activations"""
+    _chk(dout, 'dout'); _chk(gates, 'gates'); _chk(c, 'c'); _chk(w_hhT, 'w_hhT')
+    S, B, L = dout.shape
+    if tuple(gates.shape) != (S, B, 4 * L) or c.shape != dout.shape or tuple(w_hhT.shape) != (L, 4 * L):
+        raise _lib.FtError(f'taco_lstm_zone_bwd: dout {tuple(dout.shape)}, gates {tuple(gates.shape)}, c '
+                           f'{tuple(c.shape)}, w_hhT {tuple(w_hhT.shape)}')
+    nbytes = _lib.query('ft_taco_lstm_zone_workspace', B, L)
+    if ws is None:
+        ws = workspace(nbytes, dout.device)
+    dxp = alloc(S, B, 4 * L, dtype=torch.float32, device=dout.device)
+    _lib.call('ft_taco_lstm_zone_bwd', _p(dout), _p(gates), _p(c), _p(w_hhT), float(p), int(seed), _p(dxp), B, S, L,
+              _p(ws), ws.numel(), _stream())
+    return dxp
+
+
+def relu_dropout_bwd(dy: torch.Tensor, y: torch.Tensor, p: float) -> torch.Tensor:
+    """y = dropout(relu(z), p) as stored -> dz = y > 0 ? dy / (1 - p) : 0"""
+    _chk(dy, 'dy'); _chk(y, 'y')
+    dz = torch.empty_like(y)
+    _lib.call('ft_relu_dropout_bwd', _p(dy), _p(y), _p(dz), y.numel(), float(p), _stream())
+    return dz
+
+
+def taco_mel_scatter(dwp: torch.Tensor, dw: torch.Tensor, n_mels: int, max_r: int, r: int) -> None:
+    """dwp [r * n_mels, L] (rows k * n_mels + n) -> dw [n_mels * max_r, L] (rows n * max_r + k), zeros where k >= r"""
+    _chk(dwp, 'dwp'); _chk(dw, 'dw')
+    L = dw.shape[1]
+    if tuple(dwp.shape) != (r * n_mels, L) or dw.shape[0] != n_mels * max_r:
+        raise _lib.FtError(f'taco_mel_scatter: dwp {tuple(dwp.shape)}, dw {tuple(dw.shape)}, r = {r}')
+    _lib.call('ft_taco_mel_scatter', _p(dwp), _p(dw), n_mels, max_r, r, L, _stream())

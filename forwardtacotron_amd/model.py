@@ -208,7 +208,14 @@ class CBHG(nn.Module):
             out.append(ts[0].detach().as_strided((K * C,), (1,)))
         return out
 
-    def forward(self, x: torch.Tensor, time_major_out: bool = False) -> torch.Tensor:
+    def _site(self, y: torch.Tensor, seeds, i: int) -> torch.Tensor:
+        """dropout site i (0: behind the pooled bank, 1: behind conv_project1); seeds: None = draw from base._seed(), else
+        the caller's pair of seeds, a None entry skipping its site (Tacotron.forward_train records what it passes)"""
+        if seeds is None:
+            return _dropout(y, self.dropout, self.training)
+        return y if seeds[i] is None else ops.DropoutFn.apply(y, self.dropout, seeds[i])
+
+    def forward(self, x: torch.Tensor, time_major_out: bool = False, seeds=None) -> torch.Tensor:
         if not self.training:
             return self._eval(x, time_major_out)
         K = len(self.bank_kernels)
@@ -217,9 +224,9 @@ class CBHG(nn.Module):
         gs = [m.bnorm.weight for m in self.conv1d_bank]
         bs = [m.bnorm.bias for m in self.conv1d_bank]
         y = ops.ConvBankFn.apply(x, K, gamma, beta, rm, rv, *ws, *gs, *bs)
-        y = _dropout(y, self.dropout, self.training)
+        y = self._site(y, seeds, 0)
         y = self.conv_project1(y)
-        y = _dropout(y, self.dropout, self.training)
+        y = self._site(y, seeds, 1)
         y = self.conv_project2(y, residual=x)
         y = ops.LinearFn.apply(y, self.pre_highway.weight, None)
         y = ops.highway_stack(y, list(self.highways))     # gates inside the GEMM epilogues (width % 32 == 0)

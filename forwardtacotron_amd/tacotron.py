@@ -4,6 +4,7 @@ seed-identical initialisation; the teacher-forced forward() and align() run on t
 
     reference (models/tacotron.py)                 here
     Tacotron.forward(batch), teacher forcing        Tacotron.forward(batch): inference only (no grad, no training mode)
+    -- (the same forward in train(), taco_trainer)  Tacotron.forward_train(batch): the training forward, with autograd
     -- (train_tacotron.py:117-136 runs forward)     Tacotron.align(batch): encoder + attention recurrence only
     Tacotron.generate(x, speaker_emb, steps)        Tacotron.generate: B = 1, eval mode, numpy outputs as the reference
     -- (generate takes one sentence)                Tacotron.generate_batch(x, x_len, speaker_emb, steps): a ragged batch,
@@ -42,6 +43,25 @@ is ft_dropout's counter-based mask over the site's tensor in its storage order: 
 encoder, TIME-major [S,B,256] and [S,B,128] for the decoder (the mask of an element is hip.dropout(ones, 0.5, seed)
 at the same position).  One mask per site covers all S steps; the reference draws a fresh one per step from torch's
 RNG, which cannot be matched bit for bit either way.
+
+Training: forward_train(batch) is forward() with the whole module tree in train(): batch-statistics BatchNorm (running
+statistics and num_batches_tracked updated), `step += 1`, and ten random sites.  It returns (mel_outputs, linear,
+attn_scores); the first two carry an autograd graph whose nodes are HIP kernel sequences (ops.py for the CBHGs, Linears,
+embedding and layouts; taco_ops.py for the PreNet layers, the attention recurrence with its BPTT ft_taco_attend_bwd, the
+zoneout LSTMCells ft_taco_lstm_zone_fwd / _bwd and mel_proj), attn_scores is NOT differentiable (the reference's trainer
+only scores it, taco_trainer.py:100).  The reference's loop -- optimizer.zero_grad(); loss.backward(); clip_grad_norm_;
+optimizer.step() with torch.optim.Adam -- works on the device tensors as it stands, with l1_loss() below for its two
+F.l1_loss terms.  Seed order of forward_train, one dropout_seed() per site with p > 0 (a site with p = 0 draws nothing
+and is recorded as None): encoder.pre_net.fc1, encoder.pre_net.fc2, encoder.cbhg.bank (behind the pooled bank, the
+[B,Tx,K*128] buffer), encoder.cbhg.conv_project1 ([B,Tx,128]), decoder.prenet.fc1, decoder.prenet.fc2 (time-major, as
+above), decoder.res_rnn1, decoder.res_rnn2 (zoneout, [S,B,lstm_dims] time-major), postnet.bank ([B,T,K*postnet_dims]),
+postnet.conv_project1 ([B,T,256]).  model.last_seeds maps these names to the seeds of the last call, so every mask can
+be rebuilt on the host (tests/dropout_cpu.site_mask).  Zoneout (models/tacotron.py:119-122): h_s = m_s h_{s-1} +
+(1 - m_s) LSTMCell(x_s, (h_{s-1}, c_{s-1})).h with m = 1 exactly where the site's ft_dropout mask of probability
+model.zoneout (a plain attribute, 0.1, not in the state_dict) is 0 -- P(m = 1) = p, no rescaling; the cell state is not
+zoned, the zoned h is the residual output and the next step's recurrent input.  mel_proj runs on the 80 * r rows the
+[:, :, :r] slice keeps and its gradient has exact zeros in the other rows; attn_rnn.weight_ih gets one [768,384] gradient,
+columns :256 from the recurrence and 256: from the batched prenet projection.
 """
 import math
 from pathlib import Path
@@ -52,6 +72,8 @@ import torch.nn as nn
 
 from . import _lib
 from . import hip as H
+from . import ops
+from . import taco_ops as TO
 from .hip import _p, _stream
 from .base import PAD_VALUE
 from .model import CBHG
@@ -142,7 +164,7 @@ class Decoder(nn.Module):
 
 
 class Tacotron(nn.Module):
-    """Drop-in for models/tacotron.py:177-373 (teacher-forced forward and align; no training, no generate)."""
+    """Drop-in for models/tacotron.py:177-373 (teacher-forced forward, align, generate and the training forward)."""
 
     def __init__(self, embed_dims: int, num_chars: int, encoder_dims: int, decoder_dims: int, n_mels: int,
                  postnet_dims: int, encoder_k: int, lstm_dims: int, postnet_k: int, num_highways: int,
@@ -167,6 +189,9 @@ class Tacotron(nn.Module):
         self.register_buffer('step', torch.zeros(1, dtype=torch.long))
         self.register_buffer('stop_threshold', torch.tensor(stop_threshold, dtype=torch.float32))
         self._packs = {}
+        self.zoneout = 0.1           # Decoder.zoneout's p in forward_train (models/tacotron.py:119); not in the state_dict
+        self.last_seeds = {}         # site name -> seed of the last forward_train call (None: p = 0, nothing drawn)
+        self._forced_seeds = None    # tests: site name -> seed to use instead of a draw
 
     def __repr__(self):
         return f'Tacotron, num params: {sum(p.numel() for p in self.parameters())}'
@@ -415,16 +440,23 @@ class Tacotron(nn.Module):
         dropout_ok = {id(m) for pn in (self.encoder.pre_net, self.decoder.prenet) for m in pn.modules()}
         for name, m in self.named_modules():
             if m.training and id(m) not in dropout_ok:
-                raise FtError(f'Tacotron: module {name or "<root>"} is in training mode; training the teacher is not '
-                              'implemented here (use model.eval(), optionally with model.decoder.prenet.train() for '
-                              'the extraction mode of train_tacotron.py)')
+                raise FtError(f'Tacotron: module {name or "<root>"} is in training mode; forward / align are '
+                              'inference paths, training the teacher goes through Tacotron.forward_train (use '
+                              'model.eval(), optionally with model.decoder.prenet.train() for the extraction mode of '
+                              'train_tacotron.py)')
         w = self.encoder.embedding.weight
         if not w.is_cuda:
             raise FtError('Tacotron runs on an MI355X (HIP) device only: move the model with .cuda()')
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             # as model._eval_needs_no_grad: refuse rather than hand back tensors that silently carry no gradient
             raise FtError('Tacotron.forward / align is an inference path (no autograd graph): call it under '
-                          'torch.no_grad(), or with parameters that do not require grad')
+                          'torch.no_grad(), or with parameters that do not require grad (Tacotron.forward_train is the '
+                          'differentiable forward)')
+        return self._check_batch(batch)
+
+    def _check_batch(self, batch) -> Tuple[torch.Tensor, torch.Tensor, Any]:
+        """the batch conditions of forward / align / forward_train -> (x int64, mel fp32, speaker_emb or None) on the device"""
+        w = self.encoder.embedding.weight
         x = batch['x'].to(w.device, non_blocking=True)
         mel = batch['mel'].to(w.device, non_blocking=True)
         if x.dim() != 2 or mel.dim() != 3 or mel.shape[0] != x.shape[0] or mel.shape[1] != self.n_mels:
@@ -524,6 +556,84 @@ class Tacotron(nn.Module):
         mel_out, linear = self._mel_path(hist)
         return mel_out, linear, attn
 
+    # -- training ------------------------------------------------------------------------------------------------------
+    SITES = ('encoder.pre_net.fc1', 'encoder.pre_net.fc2', 'encoder.cbhg.bank', 'encoder.cbhg.conv_project1',
+             'decoder.prenet.fc1', 'decoder.prenet.fc2', 'decoder.res_rnn1', 'decoder.res_rnn2', 'postnet.bank',
+             'postnet.conv_project1')
+
+    def _site_p(self) -> Dict[str, float]:
+        ep, dp = self.encoder.pre_net.p, self.decoder.prenet.p
+        ec, pc = self.encoder.cbhg.dropout, self.postnet.dropout
+        return dict(zip(self.SITES, (ep, ep, ec, ec, dp, dp, self.zoneout, self.zoneout, pc, pc)))
+
+    def _draw_seeds(self) -> Dict[str, Any]:
+        """one dropout_seed() per random site with p > 0, in SITES order (host integers, no device sync)"""
+        forced = self._forced_seeds
+        seeds = {}
+        for name, p in self._site_p().items():
+            if not 0.0 <= p < 1.0:
+                raise FtError(f'Tacotron.forward_train: the probability of site {name} must be in [0, 1) (got {p})')
+            seeds[name] = None if p <= 0.0 else (int(forced[name]) if forced is not None else dropout_seed())
+        return seeds
+
+    def forward_train(self, batch: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """models/tacotron.py:219-280 in training mode -> (mel_outputs [B,80,S*r], linear [B,80,S*r], attn_scores
+        [B,S,Tx]), S = ceil(steps / r).  mel_outputs and linear carry an autograd graph whose nodes are HIP kernel
+        sequences (ops.py, taco_ops.py); attn_scores is NOT differentiable (the reference's trainer only scores it,
+        taco_trainer.py:100).  Needs the whole module tree in training mode and a HIP device.  As the reference's train()
+        forward it adds 1 to `step` and updates every BatchNorm's running statistics and num_batches_tracked.  The ten
+        random sites (eight dropouts, two zoneouts; module docstring) draw their seeds from torch's host generator;
+        self.last_seeds holds them afterwards."""
+        for name, m in self.named_modules():
+            if not m.training:
+                raise FtError(f'Tacotron.forward_train: module {name or "<root>"} is in eval mode; call model.train() '
+                              '(forward / align are the inference paths)')
+        w = self.encoder.embedding.weight
+        if not w.is_cuda:
+            raise FtError('Tacotron.forward_train runs on an MI355X (HIP) device only: move the model with .cuda()')
+        x, mel, semb = self._check_batch(batch)
+        seeds = self._draw_seeds()
+        p = self._site_p()
+        self.last_seeds = dict(seeds)
+        self.step += 1
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm1d):
+                m.num_batches_tracked += 1
+        B, Tx = x.shape
+        r, steps = self.r, mel.shape[2]
+        S = math.ceil(steps / r)
+        enc, dec = self.encoder, self.decoder
+
+        def prenet(pn, y, site):
+            y = TO.PreNetLayerFn.apply(y, pn.fc1.weight, pn.fc1.bias, p[site + '.fc1'], seeds[site + '.fc1'])
+            return TO.PreNetLayerFn.apply(y, pn.fc2.weight, pn.fc2.bias, p[site + '.fc2'], seeds[site + '.fc2'])
+
+        y = ops.EmbeddingFn.apply(x, enc.embedding.weight)
+        y = prenet(enc.pre_net, y, 'encoder.pre_net')
+        e = enc.cbhg(y, seeds=(seeds['encoder.cbhg.bank'], seeds['encoder.cbhg.conv_project1']))     # [B,Tx,256]
+        if semb is not None:
+            e = ops.ConcatColsFn.apply(e, None, semb, B, Tx, False)
+        ep = ops.LinearFn.apply(e, self.encoder_proj.weight, None)
+        epq = ops.LinearFn.apply(e, self.encoder_proj_query.weight, None)
+        frames = torch.empty(S, B, self.n_mels, device=x.device, dtype=torch.float32)
+        _lib.call('ft_taco_frames', _p(mel), B, self.n_mels, steps, r, S, _p(frames), _stream())
+        pre = prenet(dec.prenet, frames, 'decoder.prenet')                                            # [S,B,128]
+        gru, lsa = dec.attn_rnn, dec.attn_net
+        hist, attn = TO.TacoAttendFn.apply(ep, epq, pre, gru.weight_ih, gru.bias_ih, gru.weight_hh, gru.bias_hh,
+                                           lsa.W.weight, lsa.W.bias, lsa.conv.weight, lsa.L.weight, lsa.L.bias,
+                                           lsa.v.weight)
+        h = ops.LinearFn.apply(hist, dec.rnn_input.weight, dec.rnn_input.bias)                        # [S,B,L]
+        for cell, site in ((dec.res_rnn1, 'decoder.res_rnn1'), (dec.res_rnn2, 'decoder.res_rnn2')):
+            h = TO.AddFn.apply(h, TO.ZoneoutLSTMFn.apply(h, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh,
+                                                         p[site], seeds[site] or 0))
+        yv = TO.MelProjFn.apply(h, dec.mel_proj.weight, self.n_mels, Decoder.max_r, r)                # [S,B,r*80]
+        mel_cl = ops.BTTransposeFn.apply(yv, False).reshape(B, S * r, self.n_mels)                    # frame i*r + k
+        post = self.postnet(mel_cl, time_major_out=True,
+                            seeds=(seeds['postnet.bank'], seeds['postnet.conv_project1']))            # [T,B,2*dims]
+        lin = ops.LinearFn.apply(post, self.post_proj.weight, None, B)                                # [B,T,80]
+        T = S * r
+        return ops.TransposePadFn.apply(mel_cl, T, 0.0), ops.TransposePadFn.apply(lin, T, 0.0), attn
+
     def _mel_path(self, hist: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """history [S,B,512] -> (mel_outputs, linear) [B,80,S*r]"""
         S, B = hist.shape[:2]
@@ -555,3 +665,10 @@ class Tacotron(nn.Module):
         post = self.postnet.forward_lens(mel_cl, mel_len, time_major_out=True)
         lin = H.linear_fwd(post, self.post_proj.weight, x_tm_B=B, y_tm_B=0)
         return H.transpose_pad_lens_fwd(mel_cl, mel_len, T, PAD_VALUE), H.transpose_pad_lens_fwd(lin, mel_len, T, PAD_VALUE)
+
+
+def l1_loss(x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """F.l1_loss(x, target) (mean) of [B,C,T] tensors on the HIP loss kernel: ops.masked_l1 with full lengths.  The
+    reference loop's loss is l1_loss(m1_hat, m) + l1_loss(m2_hat, m) (taco_trainer.py:96-98)."""
+    lens = torch.full((x.shape[0],), x.shape[2], dtype=torch.int64, device=x.device)
+    return ops.masked_l1(x, target, lens)

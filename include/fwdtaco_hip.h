@@ -817,6 +817,43 @@ int ft_taco_frames(const float* mel, int B, int n_mels, int Tm, int r, int S, fl
 /* out = x + y over n floats (the decoder's residual adds) */
 int ft_taco_add(const float* x, const float* y, float* out, long n, void* stream);
 
+/* ---- Tacotron teacher training: attention BPTT and the zoneout LSTMCells (csrc/ft_taco_train.hip) ---------------- */
+/* Backward of ft_taco_attend (models/tacotron.py:124-146, :65-99), s = S-1 .. 0, five plain launches per step, then the
+ * factorised weight gradients on ft_linear_bwd_weight / ft_colsum.  Inputs: ft_taco_attend's operands; hist [S,B,512]
+ * and attn [B,S,Tx] as it wrote them; dhist [S,B,512] = the gradient of the [context | h_attn] rows.  attn itself gets
+ * no gradient (the trainer only scores it).  The cumulative attention is rebuilt as a prefix sum of attn, tanh and the
+ * GRU gates are recomputed.  Outputs (every element written): dep, depq [B,Tx,256] (gradients of enc_proj / enc_pq);
+ * dP [S,B,768]; dw_ih_ctx [768,256] = the gradient of w_ih[:, :256]; dw_hh [768,256]; db_hh [768]; dW [256,256];
+ * dbW, dbL [256] (equal); dconv_w [32,2,31]; dL [256,32]; dv [256].  No atomics, fixed summation order: one input
+ * gives one output bit pattern.  enc_pq, the weights, hist, depq, dP and ws 16-byte aligned.  1 <= Tx <= 1024, B >= 1,
+ * S >= 1; ws: ft_taco_attend_bwd_workspace(B, Tx, S) bytes (0: bad dims). */
+size_t ft_taco_attend_bwd_workspace(int B, int Tx, int S);
+int ft_taco_attend_bwd(const float* enc_proj, const float* enc_pq, const float* P, const float* w_ih, long ld_w_ih,
+                       const float* w_hh, const float* b_hh, const float* W, const float* b_W, const float* conv_w,
+                       const float* L, const float* b_L, const float* v, const float* hist, const float* attn,
+                       const float* dhist, float* dep, float* depq, float* dP, float* dw_ih_ctx, float* dw_hh,
+                       float* db_hh, float* dW, float* dbW, float* dconv_w, float* dL, float* dbL, float* dv, int B,
+                       int Tx, int S, void* ws, size_t ws_bytes, void* stream);
+/* nn.LSTMCell over S steps from zero states with the reference's zoneout (models/tacotron.py:119-122, :152-166):
+ * h_s = m_s h_{s-1} + (1 - m_s) cell(x_s, (h_{s-1}, c_{s-1})).h, c_s = the cell's c (not zoned); the zoned h_s is the
+ * output and the next step's recurrent input.  m_s[b,u] = 1 exactly where ft_dropout's mask of (p, seed) is 0 at flat
+ * index (s B + b) L + u of [S,B,L], no rescaling; p = 0 zones nothing, p = 1 everything (ft_dropout's seed contract).
+ * One launch per step.  fwd: xp [S,B,4L] = x W_ih^T + b_ih (gates i, f, g, o), w_hh [4L,L], b_hh [4L] -> gates [S,B,4L]
+ * (activated), c, h [S,B,L].  bwd: dout [S,B,L] = the gradient of h, w_hhT [L,4L] = w_hh^T -> dxp [S,B,4L], the
+ * gradient of the pre-activations (dw_hh = dxp^T h_{s-1}, db = column sums, dx = dxp W_ih follow on the GEMM kernels).
+ * L % 4 == 0, B >= 1, S >= 1; w_hh, w_hhT, h and dxp 16-byte aligned; ws: ft_taco_lstm_zone_workspace(B, L) bytes. */
+size_t ft_taco_lstm_zone_workspace(int B, int L);
+int ft_taco_lstm_zone_fwd(const float* xp, const float* w_hh, const float* b_hh, float p, uint64_t seed, float* gates,
+                          float* c, float* h, int B, int S, int L, void* stream);
+int ft_taco_lstm_zone_bwd(const float* dout, const float* gates, const float* c, const float* w_hhT, float p,
+                          uint64_t seed, float* dxp, int B, int S, int L, void* ws, size_t ws_bytes, void* stream);
+/* PreNet layer backward (models/tacotron.py:29-45: fc -> ReLU -> dropout): y = the layer's stored output, 0 where the
+ * ReLU clipped or the dropout dropped -> dz = y > 0 ? dy / (1 - p) : 0, the gradient of the Linear's output; 0 <= p < 1 */
+int ft_relu_dropout_bwd(const float* dy, const float* y, float* dz, long n, float p, void* stream);
+/* mel_proj weight gradient (models/tacotron.py:169-170): dwp [r * n_mels, L], packed rows k * n_mels + n (the rows the
+ * [:, :, :r] slice keeps) -> dw [n_mels * max_r, L] at rows n * max_r + k, exact zeros in the rows with k >= r */
+int ft_taco_mel_scatter(const float* dwp, float* dw, int n_mels, int max_r, int r, int L, void* stream);
+
 /* ---- Tacotron autoregressive generate (models/tacotron.py:283-349 Tacotron.generate, :124-174 Decoder.forward) --- */
 /* Decoder steps [s0, s0 + n) of generate at B = 1 in eval mode (no dropout, no zoneout), eight launches per step on
  * `stream` (csrc/ft_taco.hip), all enqueued here: decoder prenet (fc1 80 -> 256, fc2 256 -> 128, ReLU) of the last
