@@ -1713,3 +1713,82 @@ def taco_mel_scatter(dwp: torch.Tensor, dw: torch.Tensor, n_mels: int, max_r: in
     if tuple(dwp.shape) != (r * n_mels, L) or dw.shape[0] != n_mels * max_r:
         raise _lib.FtError(f'taco_mel_scatter: dwp {tuple(dwp.shape)}, dw {tuple(dw.shape)}, r = {r}')
     _lib.call('ft_taco_mel_scatter', _p(dwp), _p(dw), n_mels, max_r, r, L, _stream())
+
+
+# ---------------------------------------------------------------------------------------------------
+# MelGAN generator on a ragged batch (csrc/ft_melgan.hip; the public interface is melgan.MelGAN).  Activations are
+# channels-last [B * (Tmax + tail) * scale, C]; mel_len int64 [B] on the device, or None: every item has Tmax frames.
+# Weights and biases come packed from melgan.pack_*.
+# ---------------------------------------------------------------------------------------------------
+def melgan_tile_rows(kind: str, c: int) -> int:
+    """rows per workgroup tile of the launch plan for width c: kind 'conv_in' (c = n_mels), 'upsample' (c = cin, input
+    rows), 'resblock', 'conv_out' (samples); 0 where the width is not supported"""
+    return int(_lib.query('ft_melgan_tile_rows', ('conv_in', 'upsample', 'resblock', 'conv_out').index(kind), int(c)))
+
+
+def melgan_conv_in(mel: torch.Tensor, mel_len: Optional[torch.Tensor], tail: int, pad_value: float, w: torch.Tensor,
+                   bias: torch.Tensor, cout: int, err: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
+    """mel [B, n_mels, Tmax] -> [B * (Tmax + tail), cout]: normalise, append the tail, reflect 3, Conv1d(k = 7)"""
+    _chk(mel, 'mel'); _chk(w, 'w'); _chk(bias, 'bias')
+    B, C, Tmax = mel.shape
+    CP = -(-cout // 32) * 32
+    if tuple(w.shape) != (7, C, CP) or bias.numel() != CP:
+        raise _lib.FtError(f'melgan_conv_in: w {tuple(w.shape)} / bias {tuple(bias.shape)} for [7, {C}, {CP}]')
+    if mel_len is not None:
+        _chk(mel_len, 'mel_len', torch.int64)
+    out = alloc(B * (Tmax + tail), cout, dtype=torch.float32, device=mel.device)
+    _lib.call('ft_melgan_conv_in', _p(mel), _p(mel_len), B, C, Tmax, tail, float(pad_value), _p(w), _p(bias), cout, _p(out),
+              _p(err), _stream())
+    return out
+
+
+def melgan_upsample(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, tail: int, scale: int,
+                    stride: int, w: torch.Tensor, bias: torch.Tensor, cout: int, alloc=torch.empty) -> torch.Tensor:
+    """x [B * (Tmax + tail) * scale, cin] -> [B * (Tmax + tail) * scale * stride, cout]: LeakyReLU + ConvTranspose1d"""
+    _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias')
+    rows, cin = x.shape
+    CP = -(-cout // 32) * 32
+    if rows != B * (Tmax + tail) * scale or tuple(w.shape) != (2 * stride, cin, CP) or bias.numel() != CP:
+        raise _lib.FtError(f'melgan_upsample: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} for '
+                           f'{B * (Tmax + tail) * scale} rows and w [{2 * stride}, {cin}, {CP}]')
+    out = alloc(rows * stride, cout, dtype=torch.float32, device=x.device)
+    _lib.call('ft_melgan_upsample', _p(x), _p(mel_len), B, Tmax, tail, scale, cin, cout, stride, _p(w), _p(bias), _p(out),
+              _stream())
+    return out
+
+
+def melgan_resblock(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, tail: int, scale: int,
+                    dilation: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                    ws: torch.Tensor, bs: torch.Tensor, out: Optional[torch.Tensor] = None, alloc=torch.empty
+                    ) -> torch.Tensor:
+    """x [B * (Tmax + tail) * scale, C] -> the residual block at `dilation`, one launch (out: a buffer of x's shape)"""
+    for t in (x, w1, b1, w2, b2, ws, bs):
+        _chk(t, 'melgan_resblock operand')
+    rows, C = x.shape
+    CP = -(-C // 32) * 32
+    if rows != B * (Tmax + tail) * scale or tuple(w1.shape) != (3, C, CP) or tuple(w2.shape) != (C, CP) or \
+            tuple(ws.shape) != (C, CP) or any(b.numel() != CP for b in (b1, b2, bs)):
+        raise _lib.FtError(f'melgan_resblock: x {tuple(x.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}, ws '
+                           f'{tuple(ws.shape)} for {B * (Tmax + tail) * scale} rows and [{C}, {CP}] panels')
+    if out is None:
+        out = alloc(rows, C, dtype=torch.float32, device=x.device)
+    elif _chk(out, 'out').shape != x.shape or out.data_ptr() == x.data_ptr():
+        raise _lib.FtError('melgan_resblock: out must be another buffer of the shape of x')
+    _lib.call('ft_melgan_resblock', _p(x), _p(mel_len), B, Tmax, tail, scale, C, dilation, _p(w1), _p(b1), _p(w2), _p(b2),
+              _p(ws), _p(bs), _p(out), _stream())
+    return out
+
+
+def melgan_conv_out(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, tail: int, scale: int,
+                    w: torch.Tensor, bias: float, alloc=torch.empty):
+    """x [B * (Tmax + tail) * scale, C] -> (wav float32 [B, Tmax * scale], zero at j >= mel_len[b] * scale; wav_int16)"""
+    _chk(x, 'x'); _chk(w, 'w')
+    rows, C = x.shape
+    if rows != B * (Tmax + tail) * scale or tuple(w.shape) != (C, 32):
+        raise _lib.FtError(f'melgan_conv_out: x {tuple(x.shape)}, w {tuple(w.shape)} for {B * (Tmax + tail) * scale} rows '
+                           f'and w [{C}, 32]')
+    wav = alloc(B, Tmax * scale, dtype=torch.float32, device=x.device)
+    i16 = alloc(B, Tmax * scale, dtype=torch.int16, device=x.device)
+    _lib.call('ft_melgan_conv_out', _p(x), _p(mel_len), B, Tmax, tail, scale, C, _p(w), float(bias), _p(wav), _p(i16),
+              _stream())
+    return wav, i16

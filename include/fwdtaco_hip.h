@@ -1008,6 +1008,37 @@ int ft_spk_gather_partials(const float* mel, int rows_per_item, int n_mels, cons
 int ft_spk_segment_mean_norm(const float* rows, int N, int E, const long* index, const long* offsets, const long* count,
                              int S, int normalize_rows, float* out, float* rows_out, void* stream);
 
+/* ---- MelGAN vocoder (notebook_utils/synthesize.py:46-48: the hub generator's inference(mel_post); melgan.MelGAN; the
+ *      definition is DESIGN.md section 7, "MelGAN vocoder") ----------------------------------------------------------- */
+/* A ragged batch of mels: len [B] int64 on the device, 1 <= len[b] <= Tmax (clamped into that range; ft_melgan_conv_in
+ * sets *err_flag = 1 for a length outside it, NULL = no report); len == NULL: every item has Tmax frames.  `tail` frames
+ * of pad_value are appended to every item (10 in inference, 0 in forward).  Activations are channels-last [row, C] fp32;
+ * at upsampling `scale` item b owns rows [b (Tmax + tail) scale, (b + 1) (Tmax + tail) scale) and rows at >= L = (len[b] +
+ * tail) scale are neither written nor read.  Reflection is per item: row -j is row j, row L - 1 + j is row L - 1 - j.
+ * Widths are multiples of 8.  Weights are packed [k][CP] fp32 with CP = the output width rounded up to 32 and zeros in
+ * the added columns; biases are [CP], zero-padded likewise.  All products are exact-fp32 MFMA fma chains.
+ * ft_melgan_tile_rows(kind, c): the rows per workgroup tile the plan gives width c (kind 0: conv_in, c = n_mels; 1:
+ * upsample, c = cin, in INPUT rows; 2: resblock; 3: conv_out, in samples); 0 where the width is not supported.
+ * ft_melgan_conv_in: mel [B, n_mels, Tmax] as it is -> out [B (Tmax + tail), cout]: Conv1d(k = 7) over the reflection by 3
+ *   of x[t] = (mel[t] + 5) / 5 (t < len[b]) and (pad_value + 5) / 5 (the tail); w [7][n_mels][CP].  n_mels <= 128.
+ * ft_melgan_upsample: LeakyReLU(0.2), ConvTranspose1d(cin, cout, k = 2 stride, stride, padding = stride / 2), stride
+ *   even: x at `scale` -> out at scale * stride; w [2 stride][cin][CP] with w[j][ci][co] = weight[ci][co][j].  cin <= 512.
+ * ft_melgan_resblock: out = shortcut(x) + conv1x1(lrelu(conv3 at `dilation` (reflect(lrelu(x))))), all three biases; w1
+ *   [3][ch][CP], w2 and ws [ch][CP] (w[ci][co] = weight[co][ci]); x != out.  ch <= 256, dilation <= 9.
+ * ft_melgan_conv_out: LeakyReLU, reflect 3, Conv1d(ch, 1, k = 7), tanh: x at `scale` -> wav [B, Tmax scale], exactly 0 at
+ *   j >= len[b] scale (the tail's samples are dropped), and wav_i16 = truncate(clamp(32768 wav, -32768, 32767)) in the
+ *   same pass; w [ch][32] with column = tap.  ch <= 32. */
+int ft_melgan_tile_rows(int kind, int c);
+int ft_melgan_conv_in(const float* mel, const long* lens, int B, int n_mels, int Tmax, int tail, float pad_value,
+                      const float* w, const float* bias, int cout, float* out, int* err_flag, void* stream);
+int ft_melgan_upsample(const float* x, const long* lens, int B, int Tmax, int tail, int scale, int cin, int cout,
+                       int stride, const float* w, const float* bias, float* out, void* stream);
+int ft_melgan_resblock(const float* x, const long* lens, int B, int Tmax, int tail, int scale, int ch, int dilation,
+                       const float* w1, const float* b1, const float* w2, const float* b2, const float* ws,
+                       const float* bs, float* out, void* stream);
+int ft_melgan_conv_out(const float* x, const long* lens, int B, int Tmax, int tail, int scale, int ch, const float* w,
+                       float bias, float* wav, short* wav_i16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
