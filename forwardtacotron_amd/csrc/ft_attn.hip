@@ -21,6 +21,7 @@
 // on the lane: dV^T += dO^T P, dK^T += Q^T dS), each recomputing S and dP = dO V^T; no atomics, nothing summed across
 // workgroups: bitwise reproducible.
 #include "ft_attn_tile.h"
+#include "ft_reduce_plan.h"
 
 namespace {
 
@@ -335,7 +336,7 @@ __global__ __launch_bounds__(256, 1) void ft_attn_bwd_dkv_kernel(const float* __
 
 extern "C" {
 
-size_t ft_attn_workspace(int B, int T, int nheads) { return (size_t)B * nheads * T * sizeof(float); }
+size_t ft_attn_workspace(int B, int T, int nheads) { return reduce_plan::attn_bwd_bytes(B, T, nheads); }
 
 int ft_attn_fwd(const float* qkv, const unsigned char* key_pad, float* att, float* lse2, int B, int T, int nheads, int hd,
                 float scale, float p_drop, uint64_t seed, void* stream) {

@@ -8,9 +8,8 @@
 //
 // All reductions are two-stage (per-block double partials -> ordered finalize), so results are bitwise
 // reproducible run to run.  These kernels are HBM-bound: one pass over the activation per stage.
-#include <string.h>
-
 #include "ft_common.h"
+#include "ft_reduce_plan.h"      // the chunk plan and every scratch size below: host-only, tested on the CPU
 
 namespace {
 
@@ -497,13 +496,12 @@ bool all16(P... ptrs) {
 // ---- several column sums over matrices with the SAME row count in one partial + one finalize launch -----------------
 // (a FastPitch step computed 255 bias / LayerNorm gradients as 255 pairs of 5-8 us launches: 1.7 ms of kernel time).
 // Every task keeps the chunking and the summation order of its stand-alone ft_colsum call: bit-identical results.
-constexpr int CSB_MAX = 16;
-struct ColsumBatch {
+using reduce_plan::CSB_MAX;
+struct ColsumBatch : reduce_plan::ColsumBatchLayout {     // (ws_off, nchunks, rpc, tile64, tile32: the host-side plan)
   const float* x[CSB_MAX];
   float* out[CSB_MAX];
-  long ld[CSB_MAX], ws_off[CSB_MAX];       // ws_off in doubles
-  int C[CSB_MAX], nchunks[CSB_MAX], rpc[CSB_MAX];
-  int tile64[CSB_MAX + 1], tile32[CSB_MAX + 1];   // prefix sums of the tasks' 64- / 32-column tiles
+  long ld[CSB_MAX];
+  int C[CSB_MAX];
   int n;
   long rows;
 };
@@ -568,76 +566,129 @@ __global__ __launch_bounds__(256) void ft_colsum_batch_finalize_kernel(ColsumBat
   b.out[t][c] = (float)s0;
 }
 
-struct ChunkPlan {
-  int nchunks, rows_per_chunk;
-};
-ChunkPlan plan_chunks(long rows, int C) {
-  int cb = ft_cdiv(C, 64);
-  // enough blocks to fill the chip, few enough chunks that the per-channel ordered finalize stays short
-  long want = 1024 / (cb > 0 ? cb : 1);
-  if (want < 16) want = 16;
-  if (want > 64) want = 64;
-  long maxc = (rows + 63) / 64;
-  if (maxc < 1) maxc = 1;
-  long n = want < maxc ? want : maxc;
-  if (n > 65535) n = 65535;
-  long rpc = (rows + n - 1) / n;
-  rpc = ((rpc + 3) / 4) * 4;
-  if (rpc < 4) rpc = 4;
-  n = (rows + rpc - 1) / rpc;
-  if (n < 1) n = 1;
-  ChunkPlan p = {(int)n, (int)rpc};
-  return p;
+// ---- launchers: one per phase, shared by every entry point below ----------------------------------------------------
+using reduce_plan::ChunkPlan;
+using reduce_plan::plan_chunks;
+
+// the chunk partials of plan p fit the caller's workspace (the bound of every "workspace too small" check)
+bool fits(const ChunkPlan& p, int C, const void* workspace, size_t workspace_bytes) {
+  return workspace && workspace_bytes >= reduce_plan::partial_bytes(p.nchunks, C);
+}
+// 16-byte lanes never straddle a channel group
+bool lanes16(int C, int group) { return C % 4 == 0 && (group == 0 || group % 4 == 0); }
+
+// Partial sums of one BatchNorm pass over y[B,Tbuf,C].  MODE 0: statistics, 1: backward, 2: backward through the fused
+// pool (16-byte form only: gamma / beta are read there alone).  vec: the 16-byte kernel; the buffers whose alignment
+// decides it differ per entry point.
+template <int MODE>
+void launch_bn_partials(bool vec, const ChunkPlan& p, const float* y, const float* dout, const float* mean,
+                        const float* rstd, int B, int Tbuf, int Tout, int C, int group, double* partial,
+                        const float* gamma, const float* beta, hipStream_t s) {
+  const dim3 grid(ft_cdiv(C, 64), p.nchunks);
+  if (vec || MODE == 2)
+    hipLaunchKernelGGL(ft_col_partial4_kernel<MODE>, grid, dim3(256), 0, s, y, dout, mean, rstd, B, Tbuf, Tout, C, group,
+                       p.rows_per_chunk, partial, gamma, beta);
+  else if constexpr (MODE != 2)
+    hipLaunchKernelGGL(ft_col_partial_kernel<MODE>, grid, dim3(256), 0, s, y, (long)C, dout, mean, rstd, B, Tbuf, Tout, C,
+                       group, p.rows_per_chunk, partial);
+}
+
+// column-sum partials of x[rows, ldx] -- and of x1 into slot 1 when given (the two-matrix form: 16-byte lanes only)
+void launch_colsum_partials(bool vec, const ChunkPlan& p, const float* x, const float* x1, long ldx, int rows, int C,
+                            double* partial, hipStream_t s) {
+  if (vec)
+    hipLaunchKernelGGL(ft_colsum4_partial_kernel, dim3(ft_cdiv(C, 64), p.nchunks, x1 ? 2 : 1), dim3(256), 0, s, x, ldx,
+                       (long)rows, C, p.rows_per_chunk, partial, x1);
+  else
+    hipLaunchKernelGGL(ft_col_partial_kernel<2>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, x, ldx, nullptr, nullptr,
+                       nullptr, 1, rows, rows, C, 0, p.rows_per_chunk, partial);
+}
+bool colsum_vec(int C, long ldx, const float* x) { return C % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x) % 16 == 0; }
+
+// ordered sum of the chunk partials: out0[c] (+)= scale0 * sum0, out1[c] (+)= sum1
+void launch_col_finalize(const double* partial, int nchunks, int C, float* out0, float* out1, float scale0, int accumulate,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(ft_col_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, partial, nchunks, C, out0, out1, scale0,
+                     accumulate);
+}
+
+// the forward's tail: statistics from the partials (+ running statistics), then the normalised output -- through
+// MaxPool1d(2,1,1) when pool is set (16-byte form only, no residual)
+void launch_bn_finalize_apply(bool pool, const double* partial, int nchunks, const float* y, const float* gamma,
+                              const float* beta, const float* residual, float* out, float* running_mean,
+                              float* running_var, long* num_batches_tracked, float* save_mean, float* save_rstd, int B,
+                              int Tbuf, int Tout, int C, int group, float momentum, float eps, hipStream_t s) {
+  hipLaunchKernelGGL(ft_bn_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, partial, nchunks, B, Tbuf, C, group,
+                     momentum, eps, running_mean, running_var, num_batches_tracked, save_mean, save_rstd);
+  const long total = (long)B * Tout * C;
+  if (pool)
+    hipLaunchKernelGGL(ft_bn_apply_pool4_kernel, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, y, save_mean, save_rstd,
+                       gamma, beta, (float4*)out, total / 4, Tbuf, Tout, C);
+  else if (!out || Tout <= 0)
+    return;
+  else if (C % 4 == 0 && all16(y, save_mean, save_rstd, gamma, beta, residual, out))
+    hipLaunchKernelGGL(ft_bn_apply4_kernel, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, (const float4*)y,
+                       (const float4*)save_mean, (const float4*)save_rstd, (const float4*)gamma, (const float4*)beta,
+                       (const float4*)residual, (float4*)out, total / 4, Tbuf, Tout, C / 4);
+  else
+    hipLaunchKernelGGL(ft_bn_apply_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, s, y, save_mean, save_rstd, gamma, beta,
+                       residual, out, B, Tbuf, Tout, C);
+}
+
+// the whole backward: gradient partials, dgamma / dbeta, dy.  POOL: dout is the gradient of the pooled output (the entry
+// point has required the 16-byte form)
+template <bool POOL>
+void launch_bn_bwd(const ChunkPlan& p, const float* dout, const float* y, const float* gamma, const float* beta,
+                   const float* save_mean, const float* save_rstd, float* dy, float* dgamma, float* dbeta, int B, int Tbuf,
+                   int Tout, int C, int group, int relu, double* partial, hipStream_t s) {
+  launch_bn_partials<POOL ? 2 : 1>(lanes16(C, group) && all16(y, dout, save_mean, save_rstd), p, y, dout, save_mean,
+                                   save_rstd, B, Tbuf, Tout, C, group, partial, POOL ? gamma : nullptr,
+                                   POOL ? beta : nullptr, s);
+  launch_col_finalize(partial, p.nchunks, C, dbeta, dgamma, 1.0f, 0, s);
+  const long total = (long)B * Tbuf * C;
+  if (POOL || (lanes16(C, group) && all16(dout, y, save_mean, save_rstd, gamma, dgamma, dbeta, dy)))
+    hipLaunchKernelGGL(ft_bn_bwd_apply4_kernel<POOL>, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, (const float4*)dout,
+                       (const float4*)y, (const float4*)save_mean, (const float4*)save_rstd, (const float4*)gamma,
+                       (const float4*)dgamma, (const float4*)dbeta, (float4*)dy, total / 4, B, Tbuf, Tout, C / 4, group, relu,
+                       (const float4*)(POOL ? beta : nullptr));
+  else
+    hipLaunchKernelGGL(ft_bn_bwd_apply_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, s, dout, y, save_mean, save_rstd,
+                       gamma, dgamma, dbeta, dy, B, Tbuf, Tout, C, group, relu);
+}
+
+// (sum, sum of squares) partials of y[B,Tbuf,C].  Tout only travels to the kernel, which does not read it in this mode:
+// ft_bn_stat_partials passes Tbuf, ft_bn_train_fwd its own Tout, as they always have.
+void launch_stat_partials(const ChunkPlan& p, const float* y, int B, int Tbuf, int Tout, int C, int group, double* partial,
+                          hipStream_t s) {
+  launch_bn_partials<0>(lanes16(C, group) && all16(y), p, y, nullptr, nullptr, nullptr, B, Tbuf, Tout, C, group, partial,
+                        nullptr, nullptr, s);
 }
 
 }  // namespace
 
 // (sum, sum of squares) partials of y[B,Tbuf,C] by the stand-alone pass; returns the number of chunks written
 int ft_bn_stat_partials(const float* y, int B, int Tbuf, int C, int group, double* partial, hipStream_t s) {
-  ChunkPlan p = plan_chunks((long)B * Tbuf, C);
-  if (C % 4 == 0 && (group == 0 || group % 4 == 0) && all16(y))
-    hipLaunchKernelGGL(ft_col_partial4_kernel<0>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, y, nullptr, nullptr,
-                       nullptr, B, Tbuf, Tbuf, C, group, p.rows_per_chunk, partial);
-  else
-    hipLaunchKernelGGL(ft_col_partial_kernel<0>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, y, (long)C, nullptr,
-                       nullptr, nullptr, B, Tbuf, Tbuf, C, group, p.rows_per_chunk, partial);
+  const ChunkPlan p = plan_chunks((long)B * Tbuf, C);
+  launch_stat_partials(p, y, B, Tbuf, Tbuf, C, group, partial, s);
   return p.nchunks;
 }
 
 extern "C" {
 
-size_t ft_bn_workspace(int B, int Tbuf, int C);
-
-size_t ft_conv_stats_workspace(int B, int Tbuf, int C) {
-  const size_t tiles = (size_t)ft_cdiv((long)B * Tbuf, 128) * C * 2 * sizeof(double);      // one partial per 128-row GEMM tile
-  const size_t chunks = ft_bn_workspace(B, Tbuf, C);
-  return tiles > chunks ? tiles : chunks;
-}
+size_t ft_bn_workspace(int B, int Tbuf, int C) { return reduce_plan::bn_bytes((long)B * Tbuf, C); }
+size_t ft_conv_stats_workspace(int B, int Tbuf, int C) { return reduce_plan::conv_stats_bytes(B, Tbuf, C); }
+size_t ft_colsum_workspace(int rows, int C) { return reduce_plan::colsum_bytes(rows, C); }
+size_t ft_colsum_batch_workspace(int n, const int* C, int rows) { return reduce_plan::colsum_batch_bytes(n, C, rows); }
 
 int ft_bn_train_from_partials(const double* partial, int nchunks, const float* y, const float* gamma, const float* beta,
                               const float* residual, float* out, float* running_mean, float* running_var,
                               long* num_batches_tracked, float* save_mean, float* save_rstd, int B, int Tbuf, int Tout,
                               int C, int group, float momentum, float eps, void* stream) {
   FT_REQUIRE(B > 0 && Tbuf > 0 && C > 0 && Tout <= Tbuf && nchunks >= 1, "bn_train_from_partials: bad dims");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ft_bn_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, partial, nchunks, B, Tbuf, C, group,
-                     momentum, eps, running_mean, running_var, num_batches_tracked, save_mean, save_rstd);
-  if (out && Tout > 0) {
-    long total = (long)B * Tout * C;
-    if (C % 4 == 0 && all16(y, save_mean, save_rstd, gamma, beta, residual, out))
-      hipLaunchKernelGGL(ft_bn_apply4_kernel, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, (const float4*)y,
-                         (const float4*)save_mean, (const float4*)save_rstd, (const float4*)gamma, (const float4*)beta,
-                         (const float4*)residual, (float4*)out, total / 4, Tbuf, Tout, C / 4);
-    else
-      hipLaunchKernelGGL(ft_bn_apply_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, s, y, save_mean, save_rstd, gamma,
-                         beta, residual, out, B, Tbuf, Tout, C);
-  }
+  launch_bn_finalize_apply(false, partial, nchunks, y, gamma, beta, residual, out, running_mean, running_var,
+                           num_batches_tracked, save_mean, save_rstd, B, Tbuf, Tout, C, group, momentum, eps,
+                           (hipStream_t)stream);
   return ft_check_launch("bn_train_from_partials");
-}
-
-size_t ft_bn_workspace(int B, int Tbuf, int C) {
-  ChunkPlan p = plan_chunks((long)B * Tbuf, C);
-  return (size_t)p.nchunks * C * 2 * sizeof(double);
 }
 
 int ft_bn_train_fwd(const float* y, const float* gamma, const float* beta, const float* residual, float* out,
@@ -645,28 +696,12 @@ int ft_bn_train_fwd(const float* y, const float* gamma, const float* beta, const
                     float* save_rstd, int B, int Tbuf, int Tout, int C, int group, float momentum, float eps,
                     void* workspace, size_t workspace_bytes, void* stream) {
   FT_REQUIRE(B > 0 && Tbuf > 0 && C > 0 && Tout <= Tbuf, "bn_train_fwd: bad dims");
-  FT_REQUIRE(workspace && workspace_bytes >= ft_bn_workspace(B, Tbuf, C), "bn_train_fwd: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  ChunkPlan p = plan_chunks((long)B * Tbuf, C);
-  if (C % 4 == 0 && (group == 0 || group % 4 == 0) && all16(y))
-    hipLaunchKernelGGL(ft_col_partial4_kernel<0>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, y, nullptr, nullptr,
-                       nullptr, B, Tbuf, Tout, C, group, p.rows_per_chunk, (double*)workspace);
-  else
-    hipLaunchKernelGGL(ft_col_partial_kernel<0>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, y, (long)C, nullptr,
-                       nullptr, nullptr, B, Tbuf, Tout, C, group, p.rows_per_chunk, (double*)workspace);
-  hipLaunchKernelGGL(ft_bn_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, (const double*)workspace,
-                     p.nchunks, B, Tbuf, C, group, momentum, eps, running_mean, running_var, num_batches_tracked,
-                     save_mean, save_rstd);
-  if (out && Tout > 0) {
-    long total = (long)B * Tout * C;
-    if (C % 4 == 0 && all16(y, save_mean, save_rstd, gamma, beta, residual, out))
-      hipLaunchKernelGGL(ft_bn_apply4_kernel, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, (const float4*)y,
-                         (const float4*)save_mean, (const float4*)save_rstd, (const float4*)gamma, (const float4*)beta,
-                         (const float4*)residual, (float4*)out, total / 4, Tbuf, Tout, C / 4);
-    else
-      hipLaunchKernelGGL(ft_bn_apply_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, s, y, save_mean, save_rstd, gamma,
-                         beta, residual, out, B, Tbuf, Tout, C);
-  }
+  const ChunkPlan p = plan_chunks((long)B * Tbuf, C);
+  FT_REQUIRE(fits(p, C, workspace, workspace_bytes), "bn_train_fwd: workspace too small");
+  launch_stat_partials(p, y, B, Tbuf, Tout, C, group, (double*)workspace, (hipStream_t)stream);
+  launch_bn_finalize_apply(false, (const double*)workspace, p.nchunks, y, gamma, beta, residual, out, running_mean,
+                           running_var, num_batches_tracked, save_mean, save_rstd, B, Tbuf, Tout, C, group, momentum, eps,
+                           (hipStream_t)stream);
   return ft_check_launch("bn_train_fwd");
 }
 
@@ -674,26 +709,10 @@ int ft_bn_bwd(const float* dout, const float* y, const float* gamma, const float
               float* dy, float* dgamma, float* dbeta, int B, int Tbuf, int Tout, int C, int group, int relu,
               void* workspace, size_t workspace_bytes, void* stream) {
   FT_REQUIRE(B > 0 && Tbuf > 0 && C > 0 && Tout <= Tbuf, "bn_bwd: bad dims");
-  FT_REQUIRE(workspace && workspace_bytes >= ft_bn_workspace(B, Tbuf, C), "bn_bwd: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  ChunkPlan p = plan_chunks((long)B * Tbuf, C);
-  if (C % 4 == 0 && (group == 0 || group % 4 == 0) && all16(y, dout, save_mean, save_rstd))
-    hipLaunchKernelGGL(ft_col_partial4_kernel<1>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, y, dout, save_mean,
-                       save_rstd, B, Tbuf, Tout, C, group, p.rows_per_chunk, (double*)workspace);
-  else
-    hipLaunchKernelGGL(ft_col_partial_kernel<1>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, y, (long)C, dout,
-                       save_mean, save_rstd, B, Tbuf, Tout, C, group, p.rows_per_chunk, (double*)workspace);
-  hipLaunchKernelGGL(ft_col_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, (const double*)workspace,
-                     p.nchunks, C, dbeta, dgamma, 1.0f, 0);
-  long total = (long)B * Tbuf * C;
-  if (C % 4 == 0 && (group == 0 || group % 4 == 0) && all16(dout, y, save_mean, save_rstd, gamma, dgamma, dbeta, dy))
-    hipLaunchKernelGGL(ft_bn_bwd_apply4_kernel<false>, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, (const float4*)dout,
-                       (const float4*)y, (const float4*)save_mean, (const float4*)save_rstd, (const float4*)gamma,
-                       (const float4*)dgamma, (const float4*)dbeta, (float4*)dy, total / 4, B, Tbuf, Tout, C / 4, group,
-                       relu, nullptr);
-  else
-    hipLaunchKernelGGL(ft_bn_bwd_apply_kernel, dim3(ft_cdiv(total, 256)), dim3(256), 0, s, dout, y, save_mean, save_rstd,
-                       gamma, dgamma, dbeta, dy, B, Tbuf, Tout, C, group, relu);
+  const ChunkPlan p = plan_chunks((long)B * Tbuf, C);
+  FT_REQUIRE(fits(p, C, workspace, workspace_bytes), "bn_bwd: workspace too small");
+  launch_bn_bwd<false>(p, dout, y, gamma, nullptr, save_mean, save_rstd, dy, dgamma, dbeta, B, Tbuf, Tout, C, group, relu,
+                       (double*)workspace, (hipStream_t)stream);
   return ft_check_launch("bn_bwd");
 }
 
@@ -704,14 +723,11 @@ int ft_bn_pool_from_partials(const double* partial, int nchunks, const float* y,
                              float* save_mean, float* save_rstd, int B, int Tbuf, int Tout, int C, int group,
                              float momentum, float eps, void* stream) {
   FT_REQUIRE(B > 0 && Tbuf > 0 && C > 0 && Tout > 0 && Tout <= Tbuf && nchunks >= 1, "bn_pool_from_partials: bad dims");
-  FT_REQUIRE(C % 4 == 0 && (group == 0 || group % 4 == 0) && all16(y, save_mean, save_rstd, gamma, beta, out),
+  FT_REQUIRE(lanes16(C, group) && all16(y, save_mean, save_rstd, gamma, beta, out),
              "bn_pool_from_partials: needs C %% 4 == 0 and 16-byte aligned buffers");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ft_bn_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, partial, nchunks, B, Tbuf, C, group,
-                     momentum, eps, running_mean, running_var, num_batches_tracked, save_mean, save_rstd);
-  const long total = (long)B * Tout * C;
-  hipLaunchKernelGGL(ft_bn_apply_pool4_kernel, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, y, save_mean, save_rstd,
-                     gamma, beta, (float4*)out, total / 4, Tbuf, Tout, C);
+  launch_bn_finalize_apply(true, partial, nchunks, y, gamma, beta, nullptr, out, running_mean, running_var,
+                           num_batches_tracked, save_mean, save_rstd, B, Tbuf, Tout, C, group, momentum, eps,
+                           (hipStream_t)stream);
   return ft_check_launch("bn_pool_from_partials");
 }
 
@@ -720,21 +736,12 @@ int ft_bn_pool_bwd(const float* dout, const float* y, const float* gamma, const 
                    const float* save_rstd, float* dy, float* dgamma, float* dbeta, int B, int Tbuf, int Tout, int C,
                    int group, int relu, void* workspace, size_t workspace_bytes, void* stream) {
   FT_REQUIRE(B > 0 && Tbuf > 0 && C > 0 && Tout > 0 && Tout <= Tbuf, "bn_pool_bwd: bad dims");
-  FT_REQUIRE(workspace && workspace_bytes >= ft_bn_workspace(B, Tbuf, C), "bn_pool_bwd: workspace too small");
-  FT_REQUIRE(C % 4 == 0 && (group == 0 || group % 4 == 0) &&
-                 all16(dout, y, save_mean, save_rstd, gamma, beta, dgamma, dbeta, dy),
+  const ChunkPlan p = plan_chunks((long)B * Tbuf, C);
+  FT_REQUIRE(fits(p, C, workspace, workspace_bytes), "bn_pool_bwd: workspace too small");
+  FT_REQUIRE(lanes16(C, group) && all16(dout, y, save_mean, save_rstd, gamma, beta, dgamma, dbeta, dy),
              "bn_pool_bwd: needs C %% 4 == 0 and 16-byte aligned buffers");
-  hipStream_t s = (hipStream_t)stream;
-  ChunkPlan p = plan_chunks((long)B * Tbuf, C);
-  hipLaunchKernelGGL(ft_col_partial4_kernel<2>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, y, dout, save_mean,
-                     save_rstd, B, Tbuf, Tout, C, group, p.rows_per_chunk, (double*)workspace, gamma, beta);
-  hipLaunchKernelGGL(ft_col_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, (const double*)workspace,
-                     p.nchunks, C, dbeta, dgamma, 1.0f, 0);
-  const long total = (long)B * Tbuf * C;
-  hipLaunchKernelGGL(ft_bn_bwd_apply4_kernel<true>, dim3(ft_cdiv(total / 4, 256)), dim3(256), 0, s, (const float4*)dout,
-                     (const float4*)y, (const float4*)save_mean, (const float4*)save_rstd, (const float4*)gamma,
-                     (const float4*)dgamma, (const float4*)dbeta, (float4*)dy, total / 4, B, Tbuf, Tout, C / 4, group, relu,
-                     (const float4*)beta);
+  launch_bn_bwd<true>(p, dout, y, gamma, beta, save_mean, save_rstd, dy, dgamma, dbeta, B, Tbuf, Tout, C, group, relu,
+                      (double*)workspace, (hipStream_t)stream);
   return ft_check_launch("bn_pool_bwd");
 }
 
@@ -746,8 +753,6 @@ int ft_bn_fold_eval(const float* gamma, const float* beta, const float* running_
   return ft_check_launch("bn_fold_eval");
 }
 
-size_t ft_colsum_workspace(int rows, int C) { return ft_bn_workspace(1, rows > 0 ? rows : 1, C > 0 ? C : 1); }
-
 int ft_colsum(const float* x, long ldx, float* out, int rows, int C, float scale, int accumulate, void* workspace,
               size_t workspace_bytes, void* stream) {
   FT_REQUIRE(rows >= 0 && C >= 0, "colsum: bad dims");
@@ -757,16 +762,10 @@ int ft_colsum(const float* x, long ldx, float* out, int rows, int C, float scale
     if (!accumulate) (void)hipMemsetAsync(out, 0, sizeof(float) * C, s);
     return FT_OK;
   }
-  FT_REQUIRE(workspace && workspace_bytes >= ft_colsum_workspace(rows, C), "colsum: workspace too small");
-  ChunkPlan p = plan_chunks(rows, C);
-  if (C % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x) % 16 == 0)
-    hipLaunchKernelGGL(ft_colsum4_partial_kernel, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, x, ldx, (long)rows, C,
-                       p.rows_per_chunk, (double*)workspace, (const float*)nullptr);
-  else
-    hipLaunchKernelGGL(ft_col_partial_kernel<2>, dim3(ft_cdiv(C, 64), p.nchunks), dim3(256), 0, s, x, ldx, nullptr,
-                       nullptr, nullptr, 1, rows, rows, C, 0, p.rows_per_chunk, (double*)workspace);
-  hipLaunchKernelGGL(ft_col_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, (const double*)workspace,
-                     p.nchunks, C, out, nullptr, scale, accumulate);
+  const ChunkPlan p = plan_chunks(rows, C);
+  FT_REQUIRE(fits(p, C, workspace, workspace_bytes), "colsum: workspace too small");
+  launch_colsum_partials(colsum_vec(C, ldx, x), p, x, nullptr, ldx, rows, C, (double*)workspace, s);
+  launch_col_finalize((const double*)workspace, p.nchunks, C, out, nullptr, scale, accumulate, s);
   return ft_check_launch("colsum");
 }
 
@@ -775,25 +774,16 @@ int ft_colsum2(const float* x0, const float* x1, long ldx, float* out0, float* o
                size_t workspace_bytes, void* stream) {
   FT_REQUIRE(rows >= 0 && C >= 0, "colsum2: bad dims");
   if (C == 0) return FT_OK;
-  const bool vec = C % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x0) % 16 == 0 && ((uintptr_t)x1) % 16 == 0;
-  if (rows == 0 || !vec) {     // rare shapes: two plain calls
+  if (rows == 0 || !colsum_vec(C, ldx, x0) || !colsum_vec(C, ldx, x1)) {     // rare shapes: two plain calls
     int rc = ft_colsum(x0, ldx, out0, rows, C, 1.0f, 0, workspace, workspace_bytes, stream);
     return rc ? rc : ft_colsum(x1, ldx, out1, rows, C, 1.0f, 0, workspace, workspace_bytes, stream);
   }
   hipStream_t s = (hipStream_t)stream;
-  FT_REQUIRE(workspace && workspace_bytes >= ft_colsum_workspace(rows, C), "colsum2: workspace too small");
-  ChunkPlan p = plan_chunks(rows, C);
-  hipLaunchKernelGGL(ft_colsum4_partial_kernel, dim3(ft_cdiv(C, 64), p.nchunks, 2), dim3(256), 0, s, x0, ldx, (long)rows,
-                     C, p.rows_per_chunk, (double*)workspace, x1);
-  hipLaunchKernelGGL(ft_col_finalize_kernel, dim3(ft_cdiv(C, 32)), dim3(256), 0, s, (const double*)workspace,
-                     p.nchunks, C, out0, out1, 1.0f, 0);
+  const ChunkPlan p = plan_chunks(rows, C);
+  FT_REQUIRE(fits(p, C, workspace, workspace_bytes), "colsum2: workspace too small");
+  launch_colsum_partials(true, p, x0, x1, ldx, rows, C, (double*)workspace, s);
+  launch_col_finalize((const double*)workspace, p.nchunks, C, out0, out1, 1.0f, 0, s);
   return ft_check_launch("colsum2");
-}
-
-size_t ft_colsum_batch_workspace(int n, const int* C, int rows) {
-  size_t total = 0;
-  for (int i = 0; i < n; ++i) total += ft_colsum_workspace(rows, C[i]);
-  return total;
 }
 
 // out[i][c] = sum over rows of x[i][r * ld[i] + c], i < n <= 16, all with `rows` rows: one partial and one finalize launch
@@ -803,8 +793,7 @@ int ft_colsum_batch(int n, const float* const* x, const long* ld, float* const* 
   FT_REQUIRE(n >= 0 && n <= CSB_MAX && rows >= 0, "colsum_batch: n = %d (max %d), rows = %d", n, CSB_MAX, rows);
   if (n == 0) return FT_OK;
   bool vec = rows > 0;
-  for (int i = 0; i < n; ++i)
-    vec = vec && C[i] > 0 && C[i] % 4 == 0 && ld[i] % 4 == 0 && ((uintptr_t)x[i]) % 16 == 0;
+  for (int i = 0; i < n; ++i) vec = vec && C[i] > 0 && colsum_vec(C[i], ld[i], x[i]);
   if (!vec) {                   // rare shapes: one call each
     for (int i = 0; i < n; ++i) {
       const int rc = ft_colsum(x[i], ld[i], out[i], rows, C[i], 1.0f, 0, workspace, workspace_bytes, stream);
@@ -812,27 +801,19 @@ int ft_colsum_batch(int n, const float* const* x, const long* ld, float* const* 
     }
     return FT_OK;
   }
-  FT_REQUIRE(workspace && workspace_bytes >= ft_colsum_batch_workspace(n, C, rows), "colsum_batch: workspace too small");
-  ColsumBatch b;
-  memset(&b, 0, sizeof(b));
+  ColsumBatch b = {};
+  static_cast<reduce_plan::ColsumBatchLayout&>(b) = reduce_plan::colsum_batch(n, C, rows);
+  FT_REQUIRE(workspace && workspace_bytes >= b.bytes, "colsum_batch: workspace too small");
   b.n = n;
   b.rows = rows;
-  long off = 0;
-  int maxchunks = 1;
   for (int i = 0; i < n; ++i) {
-    const ChunkPlan p = plan_chunks(rows, C[i]);
     b.x[i] = x[i]; b.out[i] = out[i]; b.ld[i] = ld[i]; b.C[i] = C[i];
-    b.nchunks[i] = p.nchunks; b.rpc[i] = p.rows_per_chunk;
-    b.ws_off[i] = off;
-    off += (long)(ft_colsum_workspace(rows, C[i]) / sizeof(double));
-    b.tile64[i + 1] = b.tile64[i] + ft_cdiv(C[i], 64);
-    b.tile32[i + 1] = b.tile32[i] + ft_cdiv(C[i], 32);
-    if (p.nchunks > maxchunks) maxchunks = p.nchunks;
   }
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ft_colsum_batch_partial_kernel, dim3(b.tile64[n], maxchunks), dim3(256), 0, s, b, (double*)workspace);
+  hipLaunchKernelGGL(ft_colsum_batch_partial_kernel, dim3(b.tile64[n], b.maxchunks), dim3(256), 0, s, b, (double*)workspace);
   hipLaunchKernelGGL(ft_colsum_batch_finalize_kernel, dim3(b.tile32[n]), dim3(256), 0, s, b, (const double*)workspace);
   return ft_check_launch("colsum_batch");
 }
 
 }  // extern "C"
+

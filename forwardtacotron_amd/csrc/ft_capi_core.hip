@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ft_gemm.h"
+#include "ft_reduce_plan.h"
 
 static thread_local char g_err[512] = "";
 
@@ -34,9 +35,8 @@ int ft_gen_durations_impl(float*, const long*, int, int, long*, int*, hipStream_
 int ft_lr_expand_impl(const float*, const int*, float*, int*, int, int, int, int, hipStream_t, int = 0, const float* = nullptr);
 int ft_lr_bwd_impl(const float*, const int*, float*, int, int, int, int, hipStream_t, int = 0, float* = nullptr);
 
-// ft_bn.hip: statistics partials by the stand-alone column pass (C++ linkage), and the partial-buffer size query
+// ft_bn.hip: statistics partials by the stand-alone column pass (C++ linkage)
 int ft_bn_stat_partials(const float* y, int B, int Tbuf, int C, int group, double* partial, hipStream_t s);
-extern "C" size_t ft_conv_stats_workspace(int B, int Tbuf, int C);
 
 // Workgroup slots of the 2-per-CU GEMM kernels on a stream (512 on an unrestricted one): the weight-gradient planner sizes
 // its one-wave grids by it (ft_gemm_plan.h: plan_tn).
@@ -284,32 +284,8 @@ int ft_linear_bwd_data_multi_ws(int ntasks, const float* const* dy, long lddy, c
   return ft_launch_gemm_rows(&b, ntasks, !w_transposed, (hipStream_t)stream);
 }
 
-static FtGemmTNTask linear_bw_task(const float* dy, long lddy, const float* x, long ldx, float* dw, int rows,
-                                   int in_f, int out_f, int B, int T, int x_shift, int accumulate, int dy_tm,
-                                   int x_tm) {
-  FtGemmTNTask t;
-  memset(&t, 0, sizeof(t));
-  t.A = dy; t.B = x; t.dst = dw;
-  t.lda = lddy; t.ldb = ldx;
-  t.ldm = in_f; t.ldn = 1; t.ldj = 0;
-  t.M = out_f; t.N = in_f; t.R = rows; t.taps = 1;
-  if (x_shift == 0 && !dy_tm && !x_tm) {
-    t.amap = ft_rowmap_identity(rows);
-    t.bmap = ft_rowmap_identity(rows);
-  } else {          // both maps share the logical (b, t) decomposition with Tlog = T
-    int Tl = T > 0 ? T : 1;
-    FtRowMap am = {Tl, dy_tm ? 1 : Tl, dy_tm ? B : 1, Tl, 0, 0};
-    FtRowMap bm = {Tl, x_tm ? 1 : Tl, x_tm ? B : 1, Tl, x_shift, 0};
-    t.amap = am;
-    t.bmap = bm;
-  }
-  t.accumulate = accumulate;
-  return t;
-}
-
 size_t ft_linear_bwd_weight_workspace(int rows, int in_f, int out_f) {
-  FtGemmTNTask t = linear_bw_task(nullptr, out_f, nullptr, in_f, nullptr, rows, in_f, out_f, 1, rows, 0, 0, 0, 0);
-  return ft_gemm_tn_workspace_floats(t) * sizeof(float);
+  return gemm_plan::linear_wgrad_query_bytes(rows, in_f, out_f, ft_gemm_switches());
 }
 
 int ft_linear_bwd_weight(const float* dy, long lddy, const float* x, long ldx, float* dw, int rows, int in_f,
@@ -317,7 +293,7 @@ int ft_linear_bwd_weight(const float* dy, long lddy, const float* x, long ldx, f
                          void* workspace, size_t workspace_bytes, void* stream) {
   FT_REQUIRE((x_shift == 0 && !dy_time_major && !x_time_major) || (long)B * T == rows,
              "linear_bwd_weight: rows != B*T with a row shift / time-major operand");
-  FtGemmTNTask t = linear_bw_task(dy, lddy, x, ldx, dw, rows, in_f, out_f, B, T, x_shift, accumulate, dy_time_major,
+  FtGemmTNTask t = gemm_plan::linear_wgrad_task(dy, lddy, x, ldx, dw, rows, in_f, out_f, B, T, x_shift, accumulate, dy_time_major,
                                   x_time_major);
   return ft_launch_gemm_tn(t, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
@@ -400,18 +376,14 @@ static bool stats_in_epilogue() {
 // INDEPENDENT tasks of one launch instead -- tiles x k >= 192 workgroups on the pipelined split kernel, each writing its
 // own fp32 slab -- followed by one ordered sum (+ReLU) over the k slabs: deterministic, the taps are merely added in tap
 // order after instead of inside the accumulator.  FT_CONV_TAP_SPLIT=0 disables.
-static bool conv_tap_split(int B, int Tout, int Cout, int k) {
+// The one answer ft_conv1d_fwd_stats_workspace and ft_conv1d_fwd_stats both read (ft_reduce_plan.h: conv_fwd_stats).
+static reduce_plan::ConvFwdStats conv_fwd_stats_plan(int B, int Tout, int Cout, int k) {
   static int on = -1;
   if (on < 0) {
     const char* e = getenv("FT_CONV_TAP_SPLIT");
     on = (e && e[0] == '0') ? 0 : 1;
   }
-  const long tiles = (long)ft_cdiv((long)B * Tout, 128) * ft_cdiv(Cout, 128);
-  return on && k >= 2 && k <= FT_MAX_TASKS && Cout > 64 && Cout % 4 == 0 && (long)B * Tout > 64 && tiles < 192 &&
-         tiles * k >= 192;
-}
-static size_t conv_stats_bytes_aligned(int B, int Tout, int Cout) {
-  return (ft_conv_stats_workspace(B, Tout, Cout) + 255) & ~(size_t)255;
+  return reduce_plan::conv_fwd_stats(B, Tout, Cout, k, on == 1);
 }
 
 __global__ __launch_bounds__(256) void ft_tap_slab_sum4_kernel(const float4* __restrict__ slab, float4* __restrict__ y,
@@ -430,9 +402,7 @@ __global__ __launch_bounds__(256) void ft_tap_slab_sum4_kernel(const float4* __r
 }
 
 size_t ft_conv1d_fwd_stats_workspace(int B, int Tout, int Cout, int k) {
-  size_t n = conv_stats_bytes_aligned(B, Tout, Cout);
-  if (conv_tap_split(B, Tout, Cout, k)) n += (size_t)k * B * Tout * Cout * sizeof(float);
-  return n;
+  return conv_fwd_stats_plan(B, Tout, Cout, k).bytes;
 }
 
 int ft_conv1d_fwd_stats(const float* x, long ldx, const float* wp, float* y, long ldy, int B, int T, int Cin, int Cout,
@@ -440,12 +410,12 @@ int ft_conv1d_fwd_stats(const float* x, long ldx, const float* wp, float* y, lon
                         void* stream) {
   FT_REQUIRE(k >= 1 && Tout >= 1 && Tout <= T + 1 && nchunks && partial, "conv1d_fwd_stats: bad arguments");
   FT_REQUIRE(ldy == Cout, "conv1d_fwd_stats: y must be contiguous [B,Tout,Cout]");
-  FT_REQUIRE(partial_bytes >= ft_conv_stats_workspace(B, Tout, Cout), "conv1d_fwd_stats: partial buffer too small");
+  const reduce_plan::ConvFwdStats plan = conv_fwd_stats_plan(B, Tout, Cout, k);
+  FT_REQUIRE(partial_bytes >= plan.stats_bytes, "conv1d_fwd_stats: partial buffer too small");
   FtGemmBatch b;
   memset(&b, 0, sizeof(b));
-  if (conv_tap_split(B, Tout, Cout, k) && partial_bytes >= ft_conv1d_fwd_stats_workspace(B, Tout, Cout, k) &&
-      ((uintptr_t)y % 16 == 0)) {
-    float* slab = reinterpret_cast<float*>(reinterpret_cast<char*>(partial) + conv_stats_bytes_aligned(B, Tout, Cout));
+  if (plan.tap_split.on && partial_bytes >= plan.bytes && ((uintptr_t)y % 16 == 0)) {
+    float* slab = reinterpret_cast<float*>(reinterpret_cast<char*>(partial) + plan.slab_offset);
     const long mn = (long)B * Tout * Cout;
     for (int j = 0; j < k; ++j) {
       FtGemmTask& t = b.t[j];
@@ -480,7 +450,7 @@ int ft_conv_bank_fwd_stats(const float* x, long ldx, const float* wp_all, float*
                            int K, int relu, double* partial, size_t partial_bytes, int* nchunks, void* stream) {
   FT_REQUIRE(K >= 1 && K <= FT_MAX_TASKS && nchunks && partial, "conv_bank_fwd_stats: bad arguments");
   const int Tout = T + 1;           // the training-mode bank buffer: even-k members own T+1 rows (common_layers.py:97-99)
-  FT_REQUIRE(partial_bytes >= ft_conv_stats_workspace(B, Tout, K * C), "conv_bank_fwd_stats: partial buffer too small");
+  FT_REQUIRE(partial_bytes >= reduce_plan::conv_stats_bytes(B, Tout, K * C), "conv_bank_fwd_stats: partial buffer too small");
   FtGemmBatch b;
   memset(&b, 0, sizeof(b));
   long woff = 0;
@@ -540,14 +510,10 @@ static int conv1d_bwd_data_impl(const float* dy, long lddy, const float* wp, flo
 // data gradient of the whole conv bank in ONE launch: dx[b,t,:] = sum_k sum_tap dy_k[b, t - tap + k/2, :] * W_k,tap
 // (member k's rows t >= Tvalid_k of dy are not part of its output).  Chained: the K tasks are accumulated in registers.
 // With few output tiles (prenet: 4096 x 256 = 64 tiles of 128x128) a chain would leave 3/4 of the CUs idle, so there the
-// members run as K independent tasks into per-member partials and an ordered sum follows.
-static bool bank_bwd_partials(int B, int T, int Cin, int K) {
-  const long tiles = (long)ft_cdiv((long)B * T, 128) * ft_cdiv(Cin, 128);
-  return K >= 2 && Cin > 64 && (long)B * T > 64 && tiles < 192 && tiles * K >= 192;
-}
-
+// members run as K independent tasks into per-member partials and an ordered sum follows (ft_reduce_plan.h:
+// bank_bwd_partials, the one answer the query and the launcher read).
 size_t ft_conv_bank_bwd_data_workspace(int B, int T, int Cin, int K) {
-  return bank_bwd_partials(B, T, Cin, K) ? (size_t)K * B * T * Cin * sizeof(float) : 0;
+  return reduce_plan::bank_bwd_partials(B, T, Cin, K).extra_bytes;
 }
 
 int ft_conv_bank_bwd_data(const float* dy, long lddy, const float* wp_all, float* dx, long lddx, int B, int T, int Cin,
@@ -555,10 +521,10 @@ int ft_conv_bank_bwd_data(const float* dy, long lddy, const float* wp_all, float
                           void* stream) {
   FT_REQUIRE(K >= 1 && K <= FT_MAX_TASKS, "conv_bank_bwd_data: K=%d unsupported (max %d)", K, FT_MAX_TASKS);
   FT_REQUIRE(Tbuf == T || Tbuf == T + 1, "conv_bank_bwd_data: Tbuf must be T or T+1");
-  const bool partials = bank_bwd_partials(B, T, Cin, K);
+  const reduce_plan::Extra plan = reduce_plan::bank_bwd_partials(B, T, Cin, K);
+  const bool partials = plan.on;
   if (partials)
-    FT_REQUIRE(workspace && workspace_bytes >= ft_conv_bank_bwd_data_workspace(B, T, Cin, K),
-               "conv_bank_bwd_data: workspace too small");
+    FT_REQUIRE(workspace && workspace_bytes >= plan.extra_bytes, "conv_bank_bwd_data: workspace too small");
   float* part = static_cast<float*>(workspace);
   FtGemmBatch b;
   memset(&b, 0, sizeof(b));
@@ -594,22 +560,6 @@ int ft_conv_bank_bwd_data(const float* dy, long lddy, const float* wp_all, float
   int rc = ft_launch_gemm_rows(&b, K, !wp_transposed, (hipStream_t)stream);
   if (rc || !partials) return rc;
   return ft_launch_slab_sum(part, dx, B * T, Cin, K, lddx, (hipStream_t)stream);
-}
-
-static FtGemmTNTask conv_bw_task(const float* dy, long lddy, const float* x, long ldx, float* dw, int B, int T,
-                                 int Cin, int Cout, int k, int Tbuf, int Tvalid) {
-  FtGemmTNTask t;
-  memset(&t, 0, sizeof(t));
-  t.A = dy; t.B = x; t.dst = dw;
-  t.lda = lddy; t.ldb = ldx;
-  t.ldm = (long)Cin * k; t.ldn = k; t.ldj = 1;       // torch layout [Cout][Cin][k]
-  t.M = Cout; t.N = Cin; t.R = B * Tvalid; t.taps = k;
-  int Tl = Tvalid > 0 ? Tvalid : 1;
-  FtRowMap am = {Tl, Tbuf, 1, Tvalid, 0, 0};
-  FtRowMap bm = {Tl, T, 1, T, -(k / 2), 1};
-  t.amap = am;
-  t.bmap = bm;
-  return t;
 }
 
 // weight gradients of ALL members of a conv bank in one launch (FtGemmTNTask conv-bank mode): dy [B,Tbuf,K*C] is the
@@ -649,15 +599,14 @@ int ft_conv_bank_bwd_weight(const float* dy, long lddy, const float* x, long ldx
 }
 
 size_t ft_conv1d_bwd_weight_workspace(int B, int T, int Cin, int Cout, int k, int Tvalid) {
-  FtGemmTNTask t = conv_bw_task(nullptr, Cout, nullptr, Cin, nullptr, B, T, Cin, Cout, k, Tvalid, Tvalid);
-  return ft_gemm_tn_workspace_floats(t) * sizeof(float);
+  return gemm_plan::conv_wgrad_query_bytes(B, T, Cin, Cout, k, Tvalid, ft_gemm_switches());
 }
 
 int ft_conv1d_bwd_weight(const float* dy, long lddy, const float* x, long ldx, float* dw, int B, int T, int Cin,
                          int Cout, int k, int Tbuf, int Tvalid, void* workspace, size_t workspace_bytes,
                          void* stream) {
   FT_REQUIRE(k >= 1 && Tvalid <= Tbuf, "conv1d_bwd_weight: bad k/Tvalid");
-  FtGemmTNTask t = conv_bw_task(dy, lddy, x, ldx, dw, B, T, Cin, Cout, k, Tbuf, Tvalid);
+  FtGemmTNTask t = gemm_plan::conv_wgrad_task(dy, lddy, x, ldx, dw, B, T, Cin, Cout, k, Tbuf, Tvalid);
   return ft_launch_gemm_tn(t, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 

@@ -6,7 +6,8 @@
 
 #include <stdlib.h>
 
-#include "ft_common.h"
+#include "ft_gemm.h"
+#include "ft_reduce_plan.h"
 #include "fwdtaco_hip.h"
 
 namespace {
@@ -113,29 +114,17 @@ int ft_fft_blocks_fwd(const FtFFTBlock* blocks, int n, void* stream) {
   return FT_OK;
 }
 
-size_t ft_fft_block_wgrad_workspace(int B, int T, int d, int dfft, int k1, int k2) {
-  const int rows = B * T;
-  size_t m = ft_conv1d_bwd_weight_workspace(B, T, d, dfft, k1, T);
-  auto up = [&](size_t v) { if (v > m) m = v; };
-  up(ft_conv1d_bwd_weight_workspace(B, T, dfft, d, k2, T));
-  up(ft_linear_bwd_weight_workspace(rows, d, d));
-  up(ft_linear_bwd_weight_workspace(rows, d, 3 * d));
-  return m;
+// the bytes each of the three workspaces of ft_fft_blocks_bwd must have (ft_reduce_plan.h: fft_block): what the two queries
+// answer and what the entry point checks
+static reduce_plan::FftBlockPlan block_plan(int B, int T, int d, int nheads, int dfft, int k1, int k2) {
+  return reduce_plan::fft_block(B, T, d, nheads, dfft, k1, k2, ft_gemm_switches());
 }
 
-size_t ft_fft_block_sums_workspace(int B, int T, int d, int dfft) {
-  const int rows = B * T;
-  {
-    const int C[8] = {d, d, d, dfft, d, d, d, 3 * d};
-    const size_t batched = ft_colsum_batch_workspace(8, C, rows);
-    if (batched > 0) return batched;            // (covers the per-sum calls too: it is their sum)
-  }
-  size_t m = ft_colsum_workspace(rows, 3 * d);
-  auto up = [&](size_t v) { if (v > m) m = v; };
-  up(ft_colsum_workspace(rows, dfft));
-  up(2 * ft_colsum_workspace(rows, d));
-  return m;
+size_t ft_fft_block_wgrad_workspace(int B, int T, int d, int dfft, int k1, int k2) {
+  return block_plan(B, T, d, 1, dfft, k1, k2).wgrad;
 }
+
+size_t ft_fft_block_sums_workspace(int B, int T, int d, int dfft) { return block_plan(B, T, d, 1, dfft, 1, 1).sums; }
 
 int ft_fft_blocks_bwd(const FtFFTBlock* blocks, const FtFFTBlockGrads* grads, int n, void* workspace,
                       size_t workspace_bytes, void* wgrad_workspace, size_t wgrad_workspace_bytes, void* sums_workspace,
@@ -151,6 +140,19 @@ int ft_fft_blocks_bwd(const FtFFTBlock* blocks, const FtFFTBlockGrads* grads, in
   const bool fork = wgrad_stream != stream || sums_stream != stream;
   hipEvent_t ev = fork ? fork_event() : nullptr;
   FT_REQUIRE(!fork || ev != nullptr, "fft_blocks_bwd: could not create the fork event");
+  for (int i = 0; i < n; ++i) {
+    const FtFFTBlock& b = blocks[i];
+    FT_REQUIRE(b.nheads >= 1, "fft_blocks_bwd: block %d has %d heads", i, b.nheads);
+    const reduce_plan::FftBlockPlan p = block_plan(b.B, b.T, b.d, b.nheads, b.dfft, b.k1, b.k2);
+    FT_REQUIRE(workspace && workspace_bytes >= p.attn, "fft_blocks_bwd: workspace too small (%zu < %zu bytes)",
+               workspace_bytes, p.attn);
+    // without a sums workspace the column sums run in the weight-gradient one
+    const size_t wneed = sums_workspace ? p.tn_slabs : p.wgrad;
+    FT_REQUIRE(wgrad_workspace && wgrad_workspace_bytes >= wneed,
+               "fft_blocks_bwd: wgrad workspace too small (%zu < %zu bytes)", wgrad_workspace_bytes, wneed);
+    FT_REQUIRE(!sums_workspace || sums_workspace_bytes >= p.sums, "fft_blocks_bwd: sums workspace too small (%zu < %zu bytes)",
+               sums_workspace_bytes, p.sums);
+  }
   if (!sums_workspace) {
     sums_workspace = wgrad_workspace;
     sums_workspace_bytes = wgrad_workspace_bytes;

@@ -624,17 +624,7 @@ static long g_tn_pipelined = 0;
 extern "C" int ft_gemm_tn_pipelined_launches(void) { return (int)g_tn_pipelined; }
 
 size_t ft_gemm_tn_workspace_floats(const FtGemmTNTask& task) {
-  // the query does not know the operands yet: the larger of the plan of unaligned operands and the plan of aligned
-  // ones with padded rows, one of which the launcher will make
-  FtGemmTNTask t = task;
-  gemm_plan::normalise(t);
-  t.a_vec = t.b_vec = 0;
-  const size_t slow = gemm_plan::plan_tn(t, 0, 512, ft_gemm_switches()).need_floats;
-  t.a_vec = t.b_vec = t.rowpad = 1;
-  t.lda = t.lda > t.M + 3 ? t.lda : t.M + 3;
-  t.ldb = t.ldb > t.N + 3 ? t.ldb : t.N + 3;
-  const size_t fast = gemm_plan::plan_tn(t, 0, 512, ft_gemm_switches()).need_floats;
-  return slow > fast ? slow : fast;
+  return gemm_plan::tn_query_floats(task, ft_gemm_switches());
 }
 
 size_t ft_rows_ksplit_floats(const FtGemmBatch& batch, int ntasks, hipStream_t stream) {

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 // logical row r = (b, t), b = r / Tlog, t = r % Tlog:
 //   physical row = b*bstride + (t+shift)*tstride, valid iff 0 <= t+shift < Tvalid ; invalid rows read as zeros.
@@ -398,6 +399,67 @@ inline TnPlan plan_tn(const FtGemmTNTask& t, int precision, long slots, const Sw
   else p.variant = (p.tm == 2 ? FT_GV_TN_F32_128_FAST : FT_GV_TN_F32_64_FAST) + (p.fast ? 0 : 1);
   p.reduce = t.bankC > 0 ? TN_REDUCE_BANK : (t.taps * p.S <= 16 ? TN_REDUCE_PLAIN : TN_REDUCE_TAP);
   return p;
+}
+
+// the slabs a scratch query answers: it does not know the operands yet, so the larger of the plan of unaligned operands
+// and the plan of aligned ones with padded rows, one of which the launcher will make
+inline size_t tn_query_floats(const FtGemmTNTask& task, const Switches& sw) {
+  FtGemmTNTask t = task;
+  normalise(t);
+  t.a_vec = t.b_vec = 0;
+  const size_t slow = plan_tn(t, 0, 512, sw).need_floats;
+  t.a_vec = t.b_vec = t.rowpad = 1;
+  t.lda = t.lda > t.M + 3 ? t.lda : t.M + 3;
+  t.ldb = t.ldb > t.N + 3 ? t.ldb : t.N + 3;
+  const size_t fast = plan_tn(t, 0, 512, sw).need_floats;
+  return slow > fast ? slow : fast;
+}
+
+// the weight gradients of nn.Linear and of a channels-last Conv1d as TN tasks (the C entry points and their scratch
+// queries build the same task: the query with null operands and the dense leading dimensions)
+inline FtGemmTNTask linear_wgrad_task(const float* dy, long lddy, const float* x, long ldx, float* dw, int rows, int in_f,
+                                      int out_f, int B, int T, int x_shift, int accumulate, int dy_tm, int x_tm) {
+  FtGemmTNTask t;
+  memset(&t, 0, sizeof(t));
+  t.A = dy; t.B = x; t.dst = dw;
+  t.lda = lddy; t.ldb = ldx;
+  t.ldm = in_f; t.ldn = 1; t.ldj = 0;
+  t.M = out_f; t.N = in_f; t.R = rows; t.taps = 1;
+  if (x_shift == 0 && !dy_tm && !x_tm) {
+    t.amap = ft_rowmap_identity(rows);
+    t.bmap = ft_rowmap_identity(rows);
+  } else {          // both maps share the logical (b, t) decomposition with Tlog = T
+    int Tl = T > 0 ? T : 1;
+    FtRowMap am = {Tl, dy_tm ? 1 : Tl, dy_tm ? B : 1, Tl, 0, 0};
+    FtRowMap bm = {Tl, x_tm ? 1 : Tl, x_tm ? B : 1, Tl, x_shift, 0};
+    t.amap = am;
+    t.bmap = bm;
+  }
+  t.accumulate = accumulate;
+  return t;
+}
+inline FtGemmTNTask conv_wgrad_task(const float* dy, long lddy, const float* x, long ldx, float* dw, int B, int T, int Cin,
+                                    int Cout, int k, int Tbuf, int Tvalid) {
+  FtGemmTNTask t;
+  memset(&t, 0, sizeof(t));
+  t.A = dy; t.B = x; t.dst = dw;
+  t.lda = lddy; t.ldb = ldx;
+  t.ldm = (long)Cin * k; t.ldn = k; t.ldj = 1;       // torch layout [Cout][Cin][k]
+  t.M = Cout; t.N = Cin; t.R = B * Tvalid; t.taps = k;
+  int Tl = Tvalid > 0 ? Tvalid : 1;
+  FtRowMap am = {Tl, Tbuf, 1, Tvalid, 0, 0};
+  FtRowMap bm = {Tl, T, 1, T, -(k / 2), 1};
+  t.amap = am;
+  t.bmap = bm;
+  return t;
+}
+inline size_t linear_wgrad_query_bytes(int rows, int in_f, int out_f, const Switches& sw) {
+  return tn_query_floats(linear_wgrad_task(nullptr, out_f, nullptr, in_f, nullptr, rows, in_f, out_f, 1, rows, 0, 0, 0, 0),
+                         sw) * sizeof(float);
+}
+inline size_t conv_wgrad_query_bytes(int B, int T, int Cin, int Cout, int k, int Tvalid, const Switches& sw) {
+  return tn_query_floats(conv_wgrad_task(nullptr, Cout, nullptr, Cin, nullptr, B, T, Cin, Cout, k, Tvalid, Tvalid), sw) *
+         sizeof(float);
 }
 
 }  // namespace gemm_plan

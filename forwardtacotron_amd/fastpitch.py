@@ -34,10 +34,8 @@ def _bgemm(kind, A_ptr, lda, sA0, sA1, B_ptr, ldb, sB0, sB1, C_ptr, ldc, sC0, sC
            padded: bool = False):
     """padded: the [T,T]-shaped operand is stored with its row stride rounded up to 4 (see MHAFn)"""
     if kind == 'tn':
-        nbytes = _lib.query('ft_bgemm_tn_workspace', M, N, K, nb0, nb1)
-        ws = H.workspace(nbytes, device)
         _lib.call('ft_bgemm_tn', A_ptr, lda, sA0, sA1, B_ptr, ldb, sB0, sB1, C_ptr, ldc, sC0, sC1, M, N, K, nb0, nb1,
-                  int(padded), ws.data_ptr(), ws.numel(), H._stream())
+                  int(padded), *H.scratch('ft_bgemm_tn_workspace', M, N, K, nb0, nb1, device=device), H._stream())
     elif kind == 'nn':
         _lib.call('ft_bgemm_nn', A_ptr, lda, sA0, sA1, B_ptr, ldb, sB0, sB1, C_ptr, ldc, sC0, sC1, M, N, K, nb0, nb1,
                   int(padded), H._stream())
@@ -321,9 +319,8 @@ def posenc_bwd_scale(dout, pe, scale):
     B, T, D = dout.shape
 
     def dscale(o):
-        ws = H.workspace(_lib.query('ft_posenc_workspace'), dout.device)
-        _lib.call('ft_posenc_bwd_scale', dout.data_ptr(), pe.data_ptr(), o.data_ptr(), B, T, D, ws.data_ptr(),
-                  ws.numel(), H._stream())
+        _lib.call('ft_posenc_bwd_scale', dout.data_ptr(), pe.data_ptr(), o.data_ptr(), B, T, D,
+                  *H.scratch('ft_posenc_workspace', device=dout.device), H._stream())
 
     return emit(scale, dscale, heavy=False)
 
@@ -380,7 +377,6 @@ def _sums_stream(device) -> 'torch.cuda.Stream':
 
 _GRAD_FIELDS = ('g_in_w', 'g_in_b', 'g_out_w', 'g_out_b', 'g_c1_w', 'g_c1_b', 'g_c2_w', 'g_c2_b', 'g_n1_g', 'g_n1_b', 'g_n2_g',
                 'g_n2_b')
-_side_ws = {}
 
 
 def _block_params(l: nn.Module):
@@ -487,26 +483,21 @@ def blocks_bwd_composite(state, dy, params):
                 t = torch.empty_like(ps[j])
                 outs[12 * i + j] = t
                 setattr(g, name, t.data_ptr())
-    ws = H.workspace(_lib.query('ft_attn_workspace', B, T, nhead), dev)
     side = sink.stream if (sink is not None and sink.stream is not None) else None
     side_raw = side.cuda_stream if side is not None else H._stream()
-    def side_buffer(raw, nbytes):
-        key = (dev.index or 0, raw)
-        buf = _side_ws.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = _side_ws[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        return buf
-
-    wws = side_buffer(side_raw, _lib.query('ft_fft_block_wgrad_workspace', B, T, d, f, k1, k2))
     # FT_FFT_SUMS_STREAM=1: the blocks' bias / LayerNorm column sums on a stream of their own instead of behind the weight-
     # gradient GEMMs, which finish 1.9 ms after the main stream (lab/steady_segments_fp.py).  Measured: 15.9 -> 17.3 ms per
     # step, at default and at high priority alike -- 240 more small launches on a fourth stream cost more than the tail
     # they remove (profiles/r03_fastpitch_ab.txt).  Off.
     sums = _sums_stream(dev) if side is not None and os.environ.get('FT_FFT_SUMS_STREAM', '0') == '1' else None
     sums_raw = sums.cuda_stream if sums is not None else None
-    sws = side_buffer(('sums', sums_raw), _lib.query('ft_fft_block_sums_workspace', B, T, d, f)) if sums is not None else None
-    _lib.call('ft_fft_blocks_bwd', _ct.byref(blocks), _ct.byref(grads), n, ws.data_ptr(), ws.numel(), wws.data_ptr(),
-              wws.numel(), _p(sws), sws.numel() if sws is not None else 0, H._stream(), side_raw, sums_raw)
+    # three buffers, never shared: the attention's on this stream, the weight gradients' and the sums' named after theirs
+    sws = H.scratch('ft_fft_block_sums_workspace', B, T, d, f, device=dev, stream=('sums', sums_raw)) if sums is not None \
+        else (None, 0)
+    _lib.call('ft_fft_blocks_bwd', _ct.byref(blocks), _ct.byref(grads), n,
+              *H.scratch('ft_attn_workspace', B, T, nhead, device=dev),
+              *H.scratch('ft_fft_block_wgrad_workspace', B, T, d, f, k1, k2, device=dev, stream=('wgrad', side_raw)),
+              *sws, H._stream(), side_raw, sums_raw)
     if sums is not None:
         sink.wrote_on(sums, tell_reducer=True)
     dx = last_dh[0][last_dh[1]:last_dh[1] + R * d].view(B, T, d)     # d wrt the first block's input, in place

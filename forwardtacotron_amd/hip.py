@@ -46,15 +46,23 @@ def _chk(t: torch.Tensor, name: str, dtype=torch.float32):
 _workspaces = {}
 
 
-def workspace(nbytes: int, device) -> torch.Tensor:
+def workspace(nbytes: int, device, stream=None) -> torch.Tensor:
     """Grow-only scratch buffer per (device, stream): kernels of one stream run in order, so they can share
-    it; concurrent streams (the predictors' side stream) get their own."""
-    key = (torch.device(device).index or 0, _stream())
+    it; concurrent streams (the predictors' side stream) get their own.  stream: the raw stream the buffer is for (or
+    any hashable that names a buffer of its own next to that stream's), default torch's current stream."""
+    key = (torch.device(device).index or 0, _stream() if stream is None else stream)
     buf = _workspaces.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         _workspaces[key] = buf
     return buf
+
+
+def scratch(query_name: str, *dims, device, stream=None):
+    """(address, bytes) of the stream's workspace, grown to what the library's size query `query_name` answers for the
+    integers `dims`: the two scratch arguments of the entry point the query belongs to"""
+    buf = workspace(_lib.query(query_name, *dims), device, stream)
+    return buf.data_ptr(), buf.numel()
 
 
 def _ptr_array(ts: Sequence[Optional[torch.Tensor]]):
@@ -147,9 +155,9 @@ def attn_bwd(qkv, att, datt, key_pad, lse2, nheads: int, scale: float, p_drop: f
     B, T, d3 = qkv.shape
     d = d3 // 3
     dqkv = torch.empty_like(qkv)
-    ws = workspace(_lib.query('ft_attn_workspace', B, T, nheads), qkv.device)
     _lib.call('ft_attn_bwd', _p(qkv), _p(att), _p(datt), _p(key_pad), _p(lse2), _p(dqkv), B, T, nheads, d // nheads,
-              float(scale), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ws), ws.numel(), _stream())
+              float(scale), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
+              *scratch('ft_attn_workspace', B, T, nheads, device=qkv.device), _stream())
     return dqkv
 
 
@@ -290,10 +298,9 @@ def linear_bwd_data_multi(dy_ptrs: Sequence[int], lddy: int, ws: Sequence[torch.
 def linear_bwd_weight_raw(dy_ptr: int, lddy: int, x_ptr: int, ldx: int, dw: torch.Tensor, rows: int, in_f: int,
                           out_f: int, B: int = 1, T: int = 0, x_shift: int = 0, accumulate: bool = False,
                           dy_tm: bool = False, x_tm: bool = False) -> None:
-    nbytes = _lib.query('ft_linear_bwd_weight_workspace', rows, in_f, out_f)
-    ws = workspace(nbytes, dw.device)
     _lib.call('ft_linear_bwd_weight', dy_ptr, lddy, x_ptr, ldx, _p(dw), rows, in_f, out_f, B, T if T else rows,
-              x_shift, int(accumulate), int(dy_tm), int(x_tm), _p(ws), ws.numel(), _stream())
+              x_shift, int(accumulate), int(dy_tm), int(x_tm),
+              *scratch('ft_linear_bwd_weight_workspace', rows, in_f, out_f, device=dw.device), _stream())
 
 
 def linear_bwd_weight(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -606,19 +613,15 @@ def conv_bank_bwd_weight(dy: torch.Tensor, x: torch.Tensor, dws: Sequence[torch.
         _chk(d, 'dw')
         if tuple(d.shape) != (C, Cin, i + 1):
             raise _lib.FtError(f'conv_bank_bwd_weight: dw[{i}] has shape {tuple(d.shape)}')
-    nbytes = _lib.query('ft_conv_bank_bwd_weight_workspace', B, T, Cin, C, K, Tbuf)
-    ws = workspace(nbytes, x.device)
-    _lib.call('ft_conv_bank_bwd_weight', _p(dy), K * C, _p(x), Cin, _ptr_array(dws), B, T, Cin, C, K, Tbuf, _p(ws),
-              ws.numel(), _stream())
+    _lib.call('ft_conv_bank_bwd_weight', _p(dy), K * C, _p(x), Cin, _ptr_array(dws), B, T, Cin, C, K, Tbuf,
+              *scratch('ft_conv_bank_bwd_weight_workspace', B, T, Cin, C, K, Tbuf, device=x.device), _stream())
 
 
 def conv1d_bwd_weight_raw(dy_ptr: int, lddy: int, x: torch.Tensor, dw: torch.Tensor, Tbuf: int, Tvalid: int) -> None:
     B, T, Cin = x.shape
     Cout, _, k = dw.shape
-    nbytes = _lib.query('ft_conv1d_bwd_weight_workspace', B, T, Cin, Cout, k, Tvalid)
-    ws = workspace(nbytes, x.device)
-    _lib.call('ft_conv1d_bwd_weight', dy_ptr, lddy, _p(x), Cin, _p(dw), B, T, Cin, Cout, k, Tbuf, Tvalid, _p(ws),
-              ws.numel(), _stream())
+    _lib.call('ft_conv1d_bwd_weight', dy_ptr, lddy, _p(x), Cin, _p(dw), B, T, Cin, Cout, k, Tbuf, Tvalid,
+              *scratch('ft_conv1d_bwd_weight_workspace', B, T, Cin, Cout, k, Tvalid, device=x.device), _stream())
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -702,11 +705,9 @@ def bn_train_fwd(y: torch.Tensor, gamma, beta, running_mean, running_var, Tout: 
     out = torch.empty(B, Tout, C, device=y.device, dtype=y.dtype)
     mean = torch.empty(C, device=y.device, dtype=y.dtype)
     rstd = torch.empty(C, device=y.device, dtype=y.dtype)
-    nbytes = _lib.query('ft_bn_workspace', B, Tbuf, C)
-    ws = workspace(nbytes, y.device)
     _lib.call('ft_bn_train_fwd', _p(y), _p(gamma), _p(beta), _p(residual), _p(out), _p(running_mean),
-              _p(running_var), None, _p(mean), _p(rstd), B, Tbuf, Tout, C, group, momentum, eps, _p(ws), ws.numel(),
-              _stream())
+              _p(running_var), None, _p(mean), _p(rstd), B, Tbuf, Tout, C, group, momentum, eps,
+              *scratch('ft_bn_workspace', B, Tbuf, C, device=y.device), _stream())
     return out, mean, rstd
 
 
@@ -721,10 +722,8 @@ def bn_bwd(dout: torch.Tensor, y: torch.Tensor, gamma, mean, rstd, group: int, r
         dgamma = torch.empty(C, device=y.device, dtype=y.dtype)
     if dbeta is None:
         dbeta = torch.empty(C, device=y.device, dtype=y.dtype)
-    nbytes = _lib.query('ft_bn_workspace', B, Tbuf, C)
-    ws = workspace(nbytes, y.device)
     _lib.call('ft_bn_bwd', _p(dout), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dy), _p(dgamma), _p(dbeta), B, Tbuf,
-              Tout, C, group, int(relu), _p(ws), ws.numel(), _stream())
+              Tout, C, group, int(relu), *scratch('ft_bn_workspace', B, Tbuf, C, device=y.device), _stream())
     return dy, dgamma, dbeta
 
 
@@ -755,10 +754,8 @@ def bn_pool_bwd(dout: torch.Tensor, y: torch.Tensor, gamma, beta, mean, rstd, gr
     dy = torch.empty_like(y)
     dgamma = torch.empty(C, device=y.device, dtype=y.dtype)
     dbeta = torch.empty(C, device=y.device, dtype=y.dtype)
-    nbytes = _lib.query('ft_bn_workspace', B, Tbuf, C)
-    ws = workspace(nbytes, y.device)
     _lib.call('ft_bn_pool_bwd', _p(dout), _p(y), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dy), _p(dgamma), _p(dbeta),
-              B, Tbuf, Tout, C, group, int(relu), _p(ws), ws.numel(), _stream())
+              B, Tbuf, Tout, C, group, int(relu), *scratch('ft_bn_workspace', B, Tbuf, C, device=y.device), _stream())
     return dy, dgamma, dbeta
 
 
@@ -773,16 +770,14 @@ def bn_fold_eval(gamma, beta, running_mean, running_var, eps: float = BN_EPS):
 
 def colsum_raw(x_ptr: int, ldx: int, out: torch.Tensor, rows: int, C: int, scale: float = 1.0,
                accumulate: bool = False) -> None:
-    nbytes = _lib.query('ft_colsum_workspace', rows, C)
-    ws = workspace(nbytes, out.device)
-    _lib.call('ft_colsum', x_ptr, ldx, _p(out), rows, C, scale, int(accumulate), _p(ws), ws.numel(), _stream())
+    _lib.call('ft_colsum', x_ptr, ldx, _p(out), rows, C, scale, int(accumulate),
+              *scratch('ft_colsum_workspace', rows, C, device=out.device), _stream())
 
 
 def colsum2_raw(x0_ptr: int, x1_ptr: int, ldx: int, out0: torch.Tensor, out1: torch.Tensor, rows: int, C: int) -> None:
     """out0 = column sums of x0, out1 = of x1 (same [rows, C] shape, row stride ldx): one partial + one finalize launch"""
-    nbytes = _lib.query('ft_colsum_workspace', rows, C)
-    ws = workspace(nbytes, out0.device)
-    _lib.call('ft_colsum2', x0_ptr, x1_ptr, ldx, _p(out0), _p(out1), rows, C, _p(ws), ws.numel(), _stream())
+    _lib.call('ft_colsum2', x0_ptr, x1_ptr, ldx, _p(out0), _p(out1), rows, C,
+              *scratch('ft_colsum_workspace', rows, C, device=out0.device), _stream())
 
 
 def colsum(x: torch.Tensor) -> torch.Tensor:
@@ -1061,9 +1056,8 @@ def cross_entropy_fwd(logits: torch.Tensor, target: torch.Tensor, ignore_index: 
     rows = logits.numel() // K
     loss = torch.empty((), device=logits.device, dtype=logits.dtype)
     inv = torch.empty(1, device=logits.device, dtype=logits.dtype)
-    ws = workspace(_lib.query('ft_cross_entropy_workspace'), logits.device)
-    _lib.call('ft_cross_entropy_fwd', _p(logits), _p(target), rows, K, ignore_index, _p(loss), _p(inv), _p(ws),
-              ws.numel(), _stream())
+    _lib.call('ft_cross_entropy_fwd', _p(logits), _p(target), rows, K, ignore_index, _p(loss), _p(inv),
+              *scratch('ft_cross_entropy_workspace', device=logits.device), _stream())
     return loss, inv
 
 
@@ -1130,9 +1124,8 @@ def masked_l1_fwd(x: torch.Tensor, target: torch.Tensor, lens: torch.Tensor):
     B, C, T = x.shape
     loss = torch.empty((), device=x.device, dtype=x.dtype)
     inv = torch.empty(1, device=x.device, dtype=x.dtype)
-    ws = workspace(_lib.query('ft_masked_l1_workspace'), x.device)
-    _lib.call('ft_masked_l1_fwd', _p(x), _p(target), _p(lens), _p(loss), _p(inv), B, C, T, _p(ws), ws.numel(),
-              _stream())
+    _lib.call('ft_masked_l1_fwd', _p(x), _p(target), _p(lens), _p(loss), _p(inv), B, C, T,
+              *scratch('ft_masked_l1_workspace', device=x.device), _stream())
     return loss, inv
 
 

@@ -66,9 +66,9 @@ class TacoAttendFn(Function):
         P = H.linear_fwd(pre, w_pre, b_ih)                                      # [S,B,768]
         attn = torch.empty(B, S, Tx, device=ep.device, dtype=torch.float32)
         hist = torch.empty(S, B, 2 * D, device=ep.device, dtype=torch.float32)
-        ws = H.workspace(_lib.query('ft_taco_attend_workspace', B, Tx), ep.device)
         _lib.call('ft_taco_attend', _p(ep), _p(epq), _p(P), _p(w_ih), w_ih.shape[1], _p(w_hh), _p(b_hh), _p(W), _p(bW),
-                  _p(cw), _p(L), _p(bL), _p(v), _p(attn), _p(hist), B, Tx, S, _p(ws), ws.numel(), _stream())
+                  _p(cw), _p(L), _p(bL), _p(v), _p(attn), _p(hist), B, Tx, S,
+                  *H.scratch('ft_taco_attend_workspace', B, Tx, device=ep.device), _stream())
         ctx.save_for_backward(ep, epq, pre, P, w_pre, hist, attn, w_ih, b_ih, w_hh, b_hh, W, bW, cw, L, bL, v)
         ctx.mark_non_differentiable(attn)
         return hist, attn

@@ -518,11 +518,10 @@ class Tacotron(nn.Module):
         gru, lsa = self.decoder.attn_rnn, self.decoder.attn_net
         attn = torch.empty(B, S, Tx, device=ep.device, dtype=torch.float32)
         hist = torch.empty(S, B, 2 * self.decoder_dims, device=ep.device, dtype=torch.float32) if keep_history else None
-        ws = H.workspace(_lib.query('ft_taco_attend_workspace', B, Tx), ep.device)
         _lib.call('ft_taco_attend', _p(ep), _p(epq), _p(P), _p(gru.weight_ih), gru.weight_ih.shape[1],
                   _p(gru.weight_hh), _p(gru.bias_hh), _p(lsa.W.weight), _p(lsa.W.bias), _p(lsa.conv.weight),
-                  _p(lsa.L.weight), _p(lsa.L.bias), _p(lsa.v.weight), _p(attn), _p(hist), B, Tx, S, _p(ws), ws.numel(),
-                  _stream())
+                  _p(lsa.L.weight), _p(lsa.L.bias), _p(lsa.v.weight), _p(attn), _p(hist), B, Tx, S,
+                  *H.scratch('ft_taco_attend_workspace', B, Tx, device=ep.device), _stream())
         return attn, hist
 
     def align(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:

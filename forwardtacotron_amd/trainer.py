@@ -464,12 +464,11 @@ class TrainStep:
 
     def optimizer_step(self) -> None:
         f = self.flat
-        ws = H.workspace(_lib.query('ft_grad_norm_workspace'), f.flat.device)
         max_norm = self.cfg.get('clip_grad_norm') or 0.0
         lane = self.reducer.lane            # the all-reduced fault lane (None: no process group)
         _lib.call('ft_clip_grad_norm', f.grad.data_ptr(), f.total, float(max_norm), 1.0 / self.world,
-                  lane.data_ptr() if lane is not None else None, self.coef.data_ptr(), ws.data_ptr(), ws.numel(),
-                  H._stream())
+                  lane.data_ptr() if lane is not None else None, self.coef.data_ptr(),
+                  *H.scratch('ft_grad_norm_workspace', device=f.flat.device), H._stream())
         b = self.bufs                       # a faulted step leaves no trace in the forward-updated buffers either
         if b.stats.numel():
             _lib.call('ft_guarded_restore', b.stats.data_ptr(), b.stats_snap.data_ptr(), b.stats.numel(),

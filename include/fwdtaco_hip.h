@@ -631,7 +631,8 @@ int ft_fft_blocks_fwd(const FtFFTBlock* blocks, int n, void* stream);
 /* workspace: >= ft_attn_workspace(B,T,nheads) bytes (main stream); wgrad_workspace: >= ft_fft_block_wgrad_workspace(...)
  * bytes, used on wgrad_stream only (the four weight-gradient GEMMs of a block); sums_workspace: >=
  * ft_fft_block_sums_workspace(...) bytes, used on sums_stream only (its bias / LayerNorm column sums).  wgrad_stream /
- * sums_stream NULL = stream / wgrad_stream; sums_workspace NULL = the sums share wgrad_stream and its workspace. */
+ * sums_stream NULL = stream / wgrad_stream; sums_workspace NULL = the sums share wgrad_stream and its workspace, which
+ * ft_fft_block_wgrad_workspace sizes for both (the larger of the two needs).  All three sizes are checked on entry. */
 size_t ft_fft_block_wgrad_workspace(int B, int T, int d, int dfft, int k1, int k2);
 size_t ft_fft_block_sums_workspace(int B, int T, int d, int dfft);
 int ft_fft_blocks_bwd(const FtFFTBlock* blocks, const FtFFTBlockGrads* grads, int n, void* workspace,
