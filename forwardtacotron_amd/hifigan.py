@@ -1,0 +1,354 @@
+"""HiFi-GAN vocoder on the MI355X: the `Generator` of jik876/hifi-gan, the third vocoder the reference writes mels for
+(gen_forward.py:31-37,109-116) and the one behind its headline samples, taken by its published definition (DESIGN.md
+section 7, "HiFi-GAN vocoder").
+
+    voc = HiFiGAN.from_checkpoint(path, config='config.json').cuda().eval()
+    with torch.no_grad():
+        out = voc.inference_batch(gen['mel_post'], gen['mel_len'])        # generate_batch's output, on the device
+    out['wav_int16'][b, :out['wav_len'][b]]                                # what the published inference script writes
+
+**UNVERIFIED against the published model / checkpoint.**  Neither the published package nor a checkpoint of it is
+available where this was written: parity with the published generator and the loading of a real checkpoint are
+untested.  What is pinned is the written definition, restated from stock torch modules in tests/hifigan_cpu.py.
+
+The module's parameter tree and state_dict keys are the published generator's (`conv_pre.weight_g`,
+`ups.0.weight_v`, `resblocks.4.convs1.2.bias`, `conv_post.bias`, ...: 234 entries for V1 and V2, 69 for V3); it is built
+from the stock torch modules in the published order, so keys, shapes and initialisation under a seed are the stock
+tree's (torch's default initialisation: the published constructor's init_weights pass is not restated).  Those modules
+are parameter containers: their forward raises.  Every computation is a kernel of csrc/ft_hifigan.hip: the input
+convolution, LeakyReLU + transposed convolution in polyphase form, the residual convolution (or ResBlock1's fused pair
+where the plan picks it) with the average over a stage's parallel blocks folded into each block's last launch, and the
+output stage (tanh, zero padding behind wav_len and int16 in one pass).  Weight norm is folded into packed tap-major
+panels once per parameter version, by melgan's own fold and pack functions.
+
+A RAGGED batch goes through `inference_batch(mel, mel_len)`; how mel_len is taken from the host or the device is the
+contract of ragged.py.  An item's samples are bit-identical alone and inside any batch, at any position, and nothing at
+t >= mel_len[b] is ever loaded.
+"""
+import json
+import os
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import hip as H
+from . import ragged
+from .melgan import _wn, fold_weight_norm, pack_bias, pack_conv, pack_conv_out, pack_conv_transpose, padded_width
+
+MAX_WAV_VALUE = 32768.0
+LRELU_SLOPE = 0.1
+MAX_KERNEL = 11                 # taps of a residual convolution
+MAX_HALO = H.HIFIGAN_MAX_HALO   # rows a residual convolution reaches to either side: dilation * (k - 1) / 2 <= 40
+CONFIG_KEYS = ('resblock', 'upsample_rates', 'upsample_kernel_sizes', 'upsample_initial_channel', 'resblock_kernel_sizes',
+               'resblock_dilation_sizes', 'num_mels')
+V1 = dict(resblock='1', upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
+          resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5), (1, 3, 5), (1, 3, 5)), num_mels=80)
+V2 = dict(V1, upsample_initial_channel=128)
+V3 = dict(resblock='2', upsample_rates=(8, 8, 4), upsample_kernel_sizes=(16, 16, 8), upsample_initial_channel=256,
+          resblock_kernel_sizes=(3, 5, 7), resblock_dilation_sizes=((1, 2), (2, 6), (3, 12)), num_mels=80)
+
+
+def _empty(*shape, dtype=torch.float32, device=None) -> torch.Tensor:
+    """every device buffer of the vocoder is allocated here (tests replace it with a poison-filling allocator)"""
+    return torch.empty(*shape, dtype=dtype, device=device)
+
+
+def _alloc(*shape, **kw) -> torch.Tensor:
+    return _empty(*shape, **kw)               # looked up at call time, so a replaced _empty takes effect
+
+
+def _container(self, *a, **kw):
+    raise _lib.FtError('HiFiGAN: the stock modules are parameter containers; use HiFiGAN.forward / inference_batch')
+
+
+def _conv(ch: int, k: int, d: int) -> nn.Module:
+    return _wn(nn.Conv1d(ch, ch, k, 1, dilation=d, padding=d * (k - 1) // 2))
+
+
+class ResBlock1(nn.Module):
+    """for m: x = x + convs2[m](lrelu(convs1[m](lrelu(x)))), convs1[m] at dilation d[m], convs2[m] at dilation 1"""
+
+    def __init__(self, channels: int, kernel_size: int, dilation: Sequence[int]) -> None:
+        super().__init__()
+        self.convs1 = nn.ModuleList([_conv(channels, kernel_size, d) for d in dilation])
+        self.convs2 = nn.ModuleList([_conv(channels, kernel_size, 1) for _ in dilation])
+
+    forward = _container
+
+
+class ResBlock2(nn.Module):
+    """for m: x = x + convs[m](lrelu(x)), convs[m] at dilation d[m]"""
+
+    def __init__(self, channels: int, kernel_size: int, dilation: Sequence[int]) -> None:
+        super().__init__()
+        self.convs = nn.ModuleList([_conv(channels, kernel_size, d) for d in dilation])
+
+    forward = _container
+
+
+def pair_is_fused(width: int, k: int, d: int) -> bool:
+    """the plan for ResBlock1's (convs1[m], convs2[m]): one launch with the intermediate in LDS, or two launches of the
+    residual convolution.  Per width and (k, d) the winner of the same-process A/B of profiles/hifigan.txt section 2:
+    fused won every (k, d) at 32 channels (0.68-0.92 of the two launches' time) and k = 3 at 64 (0.93), and lost k = 7
+    and 11 at 64 (1.05, 1.12), where a tile gives 122 / 118 rows of the 128 it computes; d made no difference.  Above 64
+    channels the fused tile does not fit (csrc/ft_hifigan.hip)."""
+    if k < 3 or d * (k - 1) // 2 > H.HIFIGAN_PAIR_HALO:
+        return False
+    return width <= 32 or (width <= 64 and k == 3)
+
+
+class HiFiGAN(nn.Module):
+    def __init__(self, resblock: Union[str, int] = '1', upsample_rates: Sequence[int] = (8, 8, 2, 2),
+                 upsample_kernel_sizes: Sequence[int] = (16, 16, 4, 4), upsample_initial_channel: int = 512,
+                 resblock_kernel_sizes: Sequence[int] = (3, 7, 11),
+                 resblock_dilation_sizes: Sequence[Sequence[int]] = ((1, 3, 5), (1, 3, 5), (1, 3, 5)),
+                 num_mels: int = 80) -> None:
+        super().__init__()
+        resblock = str(resblock)
+        rates = tuple(int(u) for u in upsample_rates)
+        kernels = tuple(int(k) for k in upsample_kernel_sizes)
+        rk = tuple(int(k) for k in resblock_kernel_sizes)
+        rd = tuple(tuple(int(d) for d in ds) for ds in resblock_dilation_sizes)
+        C0, num_mels = int(upsample_initial_channel), int(num_mels)
+        if resblock not in ('1', '2'):
+            raise _lib.FtError(f"HiFiGAN: resblock must be '1' or '2', got {resblock!r}")
+        if not rates or len(rates) != len(kernels):
+            raise _lib.FtError('HiFiGAN: one upsample kernel size per upsample rate, at least one')
+        if any(k != 2 * u or u < 2 or u % 2 for u, k in zip(rates, kernels)):
+            raise _lib.FtError(f'HiFiGAN: every transposed convolution must have kernel = 2 rate with an even rate (the '
+                               f'two-tap polyphase form, padding = rate / 2), got rates {rates}, kernels {kernels}')
+        if not rk or len(rk) != len(rd) or any(len(ds) < 1 for ds in rd):
+            raise _lib.FtError('HiFiGAN: one non-empty dilation list per resblock kernel size, at least one')
+        if any(k < 1 or k % 2 == 0 or k > MAX_KERNEL for k in rk):
+            raise _lib.FtError(f'HiFiGAN: resblock kernel sizes must be odd and at most {MAX_KERNEL}, got {rk}')
+        for k, ds in zip(rk, rd):
+            if any(d < 1 or d * (k - 1) // 2 > MAX_HALO for d in ds):
+                raise _lib.FtError(f'HiFiGAN: a dilation of {ds} with {k} taps reaches {max(ds) * (k - 1) // 2} rows to '
+                                   f'either side; the plan supports a halo of at most {MAX_HALO} rows (dilation >= 1)')
+        widths = tuple(C0 >> (i + 1) for i in range(len(rates)))
+        if num_mels % 8 or not 8 <= num_mels <= 128 or C0 % 8 or not 8 <= C0 <= 512 or \
+                any(c % 8 or c < 8 or (c << (i + 1)) != C0 for i, c in enumerate(widths)) or max(widths) > 256 or \
+                widths[-1] > 32:
+            raise _lib.FtError(f'HiFiGAN: widths must be multiples of 8 with num_mels <= 128, upsample_initial_channel <= '
+                               f'512 at conv_pre, the residual stages <= 256 and the last <= 32 (got {num_mels}, {C0} -> '
+                               f'{widths})')
+        self.resblock, self.upsample_rates, self.upsample_kernel_sizes = resblock, rates, kernels
+        self.upsample_initial_channel, self.resblock_kernel_sizes, self.resblock_dilation_sizes = C0, rk, rd
+        self.num_mels, self.widths = num_mels, widths
+        self.hop_length = int(np.prod(rates))
+        block = ResBlock1 if resblock == '1' else ResBlock2
+        self.conv_pre = _wn(nn.Conv1d(num_mels, C0, 7, 1, padding=3))
+        self.ups = nn.ModuleList([_wn(nn.ConvTranspose1d(C0 >> i, C0 >> (i + 1), k, u, padding=(k - u) // 2))
+                                  for i, (u, k) in enumerate(zip(rates, kernels))])
+        self.resblocks = nn.ModuleList([block(c, k, ds) for c in widths for k, ds in zip(rk, rd)])
+        self.conv_post = _wn(nn.Conv1d(widths[-1], 1, 7, 1, padding=3))
+        self._packs: Dict[Any, Any] = {}
+        self._len_flag = ragged.LenFlag()                  # the pinned word a device-side mel_len check reports through
+
+    # ------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_config(cls, config: Union[Dict[str, Any], str, os.PathLike]) -> 'HiFiGAN':
+        """the published config.json, as a dict or a path: the generator's keys are taken, the training keys ignored"""
+        if not isinstance(config, dict):
+            with open(config) as f:
+                config = json.load(f)
+        return cls(**{k: config[k] for k in CONFIG_KEYS if k in config})
+
+    @classmethod
+    def v1(cls) -> 'HiFiGAN':
+        return cls(**V1)
+
+    @classmethod
+    def v2(cls) -> 'HiFiGAN':
+        return cls(**V2)
+
+    @classmethod
+    def v3(cls) -> 'HiFiGAN':
+        return cls(**V3)
+
+    @classmethod
+    def from_checkpoint(cls, path: Union[str, os.PathLike], config: Union[None, Dict[str, Any], str, os.PathLike] = None
+                        ) -> 'HiFiGAN':
+        """a file that holds the generator's state_dict directly or under 'generator' (the published checkpoint's key);
+        config: the published config.json as a dict or a path (default: V1).  Every entry must be there and none may be
+        unknown.  **Tested on a synthetic file of that layout only.**"""
+        ck = torch.load(path, map_location='cpu')
+        state = ck['generator'] if isinstance(ck, dict) and 'generator' in ck else ck
+        voc = cls.v1() if config is None else cls.from_config(config)
+        try:
+            missing, unexpected = voc.load_state_dict(state, strict=False)
+        except RuntimeError as e:                          # shapes of another configuration
+            raise _lib.FtError(f'HiFiGAN.from_checkpoint: {path} does not fit the configuration: {str(e)[:400]}') from None
+        if missing or unexpected:
+            raise _lib.FtError(f'HiFiGAN.from_checkpoint: {path} lacks {sorted(missing)} and has unknown {sorted(unexpected)}')
+        return voc
+
+    # ------------------------------------------------------------------------------------------------
+    def _pack(self, key, srcs: Sequence[torch.Tensor], make):
+        """weight-derived operands, rebuilt when a source tensor changes (in-place updates bump _version)"""
+        tag = tuple((s.data_ptr(), s._version, s.device) for s in srcs)
+        hit = self._packs.get(key)
+        if hit is None or hit[0] != tag:
+            hit = (tag, make())
+            self._packs[key] = hit
+        return hit[1]
+
+    def _panel(self, conv: nn.Module, pack=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(packed folded weight [k, cin, CP], padded bias) of one weight-normed convolution"""
+        v, g, b = conv.weight_v, conv.weight_g, conv.bias
+
+        def make():
+            with torch.no_grad():
+                w = fold_weight_norm(v, g)
+                if pack is not None:
+                    return pack(w), pack_bias(b)
+                return pack_conv(w).reshape(w.shape[2], w.shape[1], padded_width(w.shape[0])), pack_bias(b)
+        return self._pack(id(conv), (v, g, b), make)
+
+    def _out_panel(self) -> Tuple[torch.Tensor, float]:
+        v, g, b = self.conv_post.weight_v, self.conv_post.weight_g, self.conv_post.bias
+
+        def make():
+            with torch.no_grad():                          # (the one read-back: once per parameter version)
+                return pack_conv_out(fold_weight_norm(v, g)), float(b.detach().cpu()[0])
+        return self._pack('out', (v, g, b), make)
+
+    def _device(self) -> torch.device:
+        dev = self.conv_pre.bias.device
+        if dev.type != 'cuda' or any(p.device != dev or p.dtype != torch.float32 for p in self.parameters()):
+            raise _lib.FtError('HiFiGAN runs on an MI355X (HIP) device only, in float32; there is no CPU fallback: move '
+                               "it with .to('cuda')")
+        return dev
+
+    def _check_mel(self, what: str, mel) -> None:
+        if not isinstance(mel, torch.Tensor) or mel.dim() != 3:
+            raise _lib.FtError(f'{what}: mel must be a [B, n_mels, Tmax] tensor')
+        if mel.dtype != torch.float32:
+            raise _lib.FtError(f'{what}: mel must be float32, got {mel.dtype}')
+        if mel.shape[1] != self.num_mels:
+            raise _lib.FtError(f'{what}: expected {self.num_mels} mel channels, got {mel.shape[1]}')
+        if mel.shape[0] < 1 or mel.shape[2] < 1:
+            raise _lib.FtError(f'{what}: an empty batch')
+        if torch.is_grad_enabled() and (mel.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise _lib.FtError(f'HiFiGAN.{what} is an inference path (no autograd graph): call it under torch.no_grad(), '
+                               'or with an input and parameters that do not require grad')
+
+    def _stage(self, i: int, x: torch.Tensor, ml: Optional[torch.Tensor], B: int, Tmax: int, scale: int) -> torch.Tensor:
+        """(sum over j of resblocks[i nk + j](x), j ascending) / nk.  Each block's last launch writes the stage's buffer:
+        block 0 stores, the later ones add, the last one divides; the launches are ordered on the current stream."""
+        nk = len(self.resblock_kernel_sizes)
+        total = _alloc(*x.shape, dtype=torch.float32, device=x.device)
+        tmp: List[Optional[torch.Tensor]] = [None, None, None]          # two buffers in turn for the chain, one for mid
+
+        def buf(n: int) -> torch.Tensor:
+            if tmp[n] is None:
+                tmp[n] = _alloc(*x.shape, dtype=torch.float32, device=x.device)
+            return tmp[n]
+        for j, (k, ds) in enumerate(zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)):
+            blk = self.resblocks[i * nk + j]
+            y = x
+            for m, d in enumerate(ds):
+                last = m == len(ds) - 1
+                out = total if last else buf(m % 2)
+                acc = 0 if not last or j == 0 else 1
+                if last and j == nk - 1 and nk > 1:
+                    acc = 2
+                kw = dict(acc_mode=acc, nk=nk, out=out, alloc=_alloc)
+                if self.resblock == '2':
+                    w, b = self._panel(blk.convs[m])
+                    H.hifigan_resconv(y, ml, B, Tmax, scale, d, w, b, res='x', **kw)
+                else:
+                    w1, b1 = self._panel(blk.convs1[m])
+                    w2, b2 = self._panel(blk.convs2[m])
+                    if pair_is_fused(x.shape[1], k, d):
+                        H.hifigan_respair(y, ml, B, Tmax, scale, d, w1, b1, w2, b2, **kw)
+                    else:
+                        mid = H.hifigan_resconv(y, ml, B, Tmax, scale, d, w1, b1, out=buf(2), alloc=_alloc)
+                        H.hifigan_resconv(mid, ml, B, Tmax, scale, 1, w2, b2, res=y, **kw)
+                y = out
+        return total
+
+    def _generate(self, mel: torch.Tensor, ml: Optional[torch.Tensor], err: Optional[torch.Tensor], keep: bool
+                  ) -> Dict[str, Any]:
+        """the generator over a batch -> {'wav', 'wav_int16'} and, with keep, 'stages': the input convolution's output,
+        then per upsampling stage the transposed convolution's and the averaged residual blocks'"""
+        B, _, Tmax = mel.shape
+        stages: List[torch.Tensor] = []
+        w, b = self._panel(self.conv_pre)
+        x = H.hifigan_conv_in(mel, ml, w, b, self.upsample_initial_channel, err, alloc=_alloc)
+        stages.append(x)
+        scale = 1
+        for i, u in enumerate(self.upsample_rates):
+            w, b = self._panel(self.ups[i], pack_conv_transpose)
+            x = H.hifigan_upsample(x, ml, B, Tmax, scale, u, w, b, self.widths[i], alloc=_alloc)
+            scale *= u
+            stages.append(x)
+            x = self._stage(i, x, ml, B, Tmax, scale)
+            stages.append(x)
+        wo, bo = self._out_panel()
+        wav, i16 = H.hifigan_conv_out(x, ml, B, Tmax, scale, wo, bo, alloc=_alloc)
+        out = {'wav': wav, 'wav_int16': i16}
+        if keep:
+            out['stages'] = stages
+        return out
+
+    # ------------------------------------------------------------------------------------------------
+    def inference_batch(self, mel: torch.Tensor, mel_len: torch.Tensor, keep_stages: bool = False) -> Dict[str, Any]:
+        """The published inference for a RAGGED batch (generate_batch's 'mel_post' and 'mel_len'): item b is what
+        `generator(mel[b:b+1, :, :mel_len[b]]).squeeze() * 32768` gives alone, clamped to [-32768, 32767] (the
+        published script does not clamp: DESIGN.md, "Deviations") and truncated to int16.
+
+        mel: float32 [B, n_mels, Tmax] on the device, as it is (no normalisation); what lies at t >= mel_len[b]
+        (padding, NaN, Inf) is never loaded.
+        mel_len: int64 [B], on the host or the device, 1 <= mel_len[b] <= Tmax.
+        -> {'wav': float32 [B, hop * Tmax], the tanh output before quantisation, exactly 0 at j >= wav_len[b];
+            'wav_len': int64 [B] = hop * mel_len on the device; 'wav_int16': int16 [B, hop * Tmax]}, hop = the product
+            of the upsample rates.
+        keep_stages adds 'stages' (for the tests): the outputs of conv_pre and, per upsampling stage, of the transposed
+        convolution and of the averaged residual blocks.
+
+        An item's samples are bit-identical alone (Tmax its own length) and in any batch at any position.  Lengths follow
+        ragged.py: a host-side mel_len is checked up front and nothing synchronises; a device-side one is clamped inside
+        the kernels and its FtError is raised at the end of the call, after one synchronisation, through ONE pinned host
+        word kept on this object."""
+        what = 'inference_batch'
+        self._check_mel(what, mel)
+        B, _, Tmax = mel.shape
+        if not isinstance(mel_len, torch.Tensor) or mel_len.dim() != 1 or mel_len.numel() != B or \
+                mel_len.dtype != torch.int64:
+            raise _lib.FtError(f'{what}: mel_len must be an int64 tensor [B = {B}]')
+        if not mel_len.is_cuda and (int(mel_len.min()) < 1 or int(mel_len.max()) > Tmax):
+            raise _lib.FtError(f"{ragged.range_message(what, 'mel_len', 1, Tmax, 'Tmax')} (got {mel_len.tolist()})")
+        dev = self._device()
+        if not mel.is_cuda:
+            raise _lib.FtError(f'{what}: mel must be on the HIP device')
+        mel = mel.contiguous()
+        ml, err = ragged.device_lens(mel_len, B, 1, Tmax, what, 'mel_len', 'Tmax', dev)
+        out = self._generate(mel, ml, err, keep_stages)
+        out['wav_len'] = ml * self.hop_length
+        self._len_flag.check(err, ragged.range_message(what, 'mel_len', 1, Tmax, 'Tmax'))
+        return out
+
+    def inference(self, mel: torch.Tensor) -> np.ndarray:
+        """the published inference of one mel, [n_mels, T] or [1, n_mels, T] on the device -> int16 numpy [hop * T]"""
+        if isinstance(mel, torch.Tensor) and mel.dim() == 2:
+            mel = mel.unsqueeze(0)
+        if not isinstance(mel, torch.Tensor) or mel.dim() != 3 or mel.shape[0] != 1:
+            raise _lib.FtError('inference: one mel, [n_mels, T] or [1, n_mels, T] (a batch goes through inference_batch)')
+        out = self.inference_batch(mel, torch.tensor([mel.shape[2]], dtype=torch.int64))
+        return out['wav_int16'][0].cpu().numpy()
+
+    def forward(self, mel: torch.Tensor) -> torch.Tensor:
+        """generator(mel): float32 [B, n_mels, T] on the device -> [B, 1, hop * T].  Inference only; every item has T
+        frames."""
+        self._check_mel('forward', mel)
+        self._device()
+        if not mel.is_cuda:
+            raise _lib.FtError('forward: mel must be on the HIP device')
+        return self._generate(mel.contiguous(), None, None, False)['wav'].unsqueeze(1)
+
+
+__all__ = ['HiFiGAN', 'ResBlock1', 'ResBlock2', 'pair_is_fused', 'V1', 'V2', 'V3', 'MAX_HALO', 'MAX_KERNEL']

@@ -7,7 +7,7 @@ tensors and raise if handed anything else -- there is no fallback path.
 import contextlib
 import ctypes
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Union
 
 import torch
 
@@ -1784,4 +1784,116 @@ def melgan_conv_out(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tm
     i16 = alloc(B, Tmax * scale, dtype=torch.int16, device=x.device)
     _lib.call('ft_melgan_conv_out', _p(x), _p(mel_len), B, Tmax, tail, scale, C, _p(w), float(bias), _p(wav), _p(i16),
               _stream())
+    return wav, i16
+
+
+# ---------------------------------------------------------------------------------------------------
+# HiFi-GAN generator on a ragged batch (csrc/ft_hifigan.hip; the public interface is hifigan.HiFiGAN).  Activations are
+# channels-last [B * Tmax * scale, C]; mel_len int64 [B] on the device, or None: every item has Tmax frames.  Weights and
+# biases come packed from melgan.pack_*.  Edges are zeros.
+# ---------------------------------------------------------------------------------------------------
+_HIFIGAN_KINDS = ('conv_in', 'upsample', 'resconv', 'conv_out', 'respair')
+HIFIGAN_MAX_HALO = 40           # resconv: dilation * (k - 1) / 2 rows on either side of a tile
+HIFIGAN_PAIR_HALO = 25          # respair: the same for its first convolution
+
+
+def hifigan_tile_rows(kind: str, c: int) -> int:
+    """rows per workgroup tile of the launch plan for width c: kind 'conv_in' (c = n_mels), 'upsample' (c = cin, input
+    rows), 'resconv', 'conv_out' (samples), 'respair' (rows of the intermediate: a tile's output is that minus k - 1); 0
+    where the width is not supported"""
+    return int(_lib.query('ft_hifigan_tile_rows', _HIFIGAN_KINDS.index(kind), int(c)))
+
+
+def hifigan_conv_in(mel: torch.Tensor, mel_len: Optional[torch.Tensor], w: torch.Tensor, bias: torch.Tensor, cout: int,
+                    err: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
+    """mel [B, n_mels, Tmax] -> [B * Tmax, cout]: Conv1d(k = 7, padding 3) of the mel as it is"""
+    _chk(mel, 'mel'); _chk(w, 'w'); _chk(bias, 'bias')
+    B, C, Tmax = mel.shape
+    CP = -(-cout // 32) * 32
+    if tuple(w.shape) != (7, C, CP) or bias.numel() != CP:
+        raise _lib.FtError(f'hifigan_conv_in: w {tuple(w.shape)} / bias {tuple(bias.shape)} for [7, {C}, {CP}]')
+    if mel_len is not None:
+        _chk(mel_len, 'mel_len', torch.int64)
+    out = alloc(B * Tmax, cout, dtype=torch.float32, device=mel.device)
+    _lib.call('ft_hifigan_conv_in', _p(mel), _p(mel_len), B, C, Tmax, _p(w), _p(bias), cout, _p(out), _p(err), _stream())
+    return out
+
+
+def hifigan_upsample(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, stride: int,
+                     w: torch.Tensor, bias: torch.Tensor, cout: int, alloc=torch.empty) -> torch.Tensor:
+    """x [B * Tmax * scale, cin] -> [B * Tmax * scale * stride, cout]: LeakyReLU(0.1) + ConvTranspose1d"""
+    _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias')
+    rows, cin = x.shape
+    CP = -(-cout // 32) * 32
+    if rows != B * Tmax * scale or tuple(w.shape) != (2 * stride, cin, CP) or bias.numel() != CP:
+        raise _lib.FtError(f'hifigan_upsample: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} for '
+                           f'{B * Tmax * scale} rows and w [{2 * stride}, {cin}, {CP}]')
+    out = alloc(rows * stride, cout, dtype=torch.float32, device=x.device)
+    _lib.call('ft_hifigan_upsample', _p(x), _p(mel_len), B, Tmax, scale, cin, cout, stride, _p(w), _p(bias), _p(out),
+              _stream())
+    return out
+
+
+def _hifigan_out(what: str, x: torch.Tensor, out: Optional[torch.Tensor], acc_mode: int, alloc) -> torch.Tensor:
+    if acc_mode not in (0, 1, 2):
+        raise _lib.FtError(f'{what}: acc_mode {acc_mode} (0 store, 1 add, 2 add and divide by nk)')
+    if out is None:
+        if acc_mode:
+            raise _lib.FtError(f'{what}: accumulating needs the buffer that holds the sum')
+        return alloc(*x.shape, dtype=torch.float32, device=x.device)
+    if _chk(out, 'out').shape != x.shape or out.data_ptr() == x.data_ptr():
+        raise _lib.FtError(f'{what}: out must be another buffer of the shape of x')
+    return out
+
+
+def hifigan_resconv(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, dilation: int,
+                    w: torch.Tensor, bias: torch.Tensor, res: Union[None, str, torch.Tensor] = None, acc_mode: int = 0,
+                    nk: int = 1, out: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
+    """x [B * Tmax * scale, C] -> res + bias + Conv1d(k, dilation, zero padding)(lrelu_0.1(x)); w [k, C, CP].  res: None,
+    'x' (the input itself) or another [rows, C] buffer.  acc_mode 0: out = value, 1: out += value, 2: out = (out +
+    value) / nk."""
+    _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias')
+    rows, C = x.shape
+    CP = -(-C // 32) * 32
+    if rows != B * Tmax * scale or w.dim() != 3 or tuple(w.shape[1:]) != (C, CP) or bias.numel() != CP:
+        raise _lib.FtError(f'hifigan_resconv: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} for '
+                           f'{B * Tmax * scale} rows and w [k, {C}, {CP}]')
+    res_mode = 0 if res is None else 1 if isinstance(res, str) and res == 'x' else 2
+    if res_mode == 2 and (not isinstance(res, torch.Tensor) or _chk(res, 'res').shape != x.shape):
+        raise _lib.FtError("hifigan_resconv: res must be None, 'x' or a buffer of the shape of x")
+    out = _hifigan_out('hifigan_resconv', x, out, acc_mode, alloc)
+    _lib.call('ft_hifigan_resconv', _p(x), _p(mel_len), B, Tmax, scale, C, int(w.shape[0]), dilation, _p(w), _p(bias),
+              _p(res) if res_mode == 2 else None, res_mode, acc_mode, nk, _p(out), _stream())
+    return out
+
+
+def hifigan_respair(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, dilation: int,
+                    w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, acc_mode: int = 0, nk: int = 1,
+                    out: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
+    """ResBlock1's pair in one launch: x + b2 + Conv1d(k)(lrelu(b1 + Conv1d(k, dilation)(lrelu(x)))); w1, w2 [k, C, CP]"""
+    for t in (x, w1, b1, w2, b2):
+        _chk(t, 'hifigan_respair operand')
+    rows, C = x.shape
+    CP = -(-C // 32) * 32
+    if rows != B * Tmax * scale or w1.dim() != 3 or tuple(w1.shape[1:]) != (C, CP) or w2.shape != w1.shape or \
+            b1.numel() != CP or b2.numel() != CP:
+        raise _lib.FtError(f'hifigan_respair: x {tuple(x.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)} for '
+                           f'{B * Tmax * scale} rows and [k, {C}, {CP}] panels')
+    out = _hifigan_out('hifigan_respair', x, out, acc_mode, alloc)
+    _lib.call('ft_hifigan_respair', _p(x), _p(mel_len), B, Tmax, scale, C, int(w1.shape[0]), dilation, _p(w1), _p(b1),
+              _p(w2), _p(b2), acc_mode, nk, _p(out), _stream())
+    return out
+
+
+def hifigan_conv_out(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, w: torch.Tensor,
+                     bias: float, alloc=torch.empty):
+    """x [B * Tmax * scale, C] -> (wav float32 [B, Tmax * scale], zero at j >= mel_len[b] * scale; wav_int16)"""
+    _chk(x, 'x'); _chk(w, 'w')
+    rows, C = x.shape
+    if rows != B * Tmax * scale or tuple(w.shape) != (C, 32):
+        raise _lib.FtError(f'hifigan_conv_out: x {tuple(x.shape)}, w {tuple(w.shape)} for {B * Tmax * scale} rows and w '
+                           f'[{C}, 32]')
+    wav = alloc(B, Tmax * scale, dtype=torch.float32, device=x.device)
+    i16 = alloc(B, Tmax * scale, dtype=torch.int16, device=x.device)
+    _lib.call('ft_hifigan_conv_out', _p(x), _p(mel_len), B, Tmax, scale, C, _p(w), float(bias), _p(wav), _p(i16), _stream())
     return wav, i16

@@ -1040,6 +1040,41 @@ int ft_melgan_resblock(const float* x, const long* lens, int B, int Tmax, int ta
 int ft_melgan_conv_out(const float* x, const long* lens, int B, int Tmax, int tail, int scale, int ch, const float* w,
                        float bias, float* wav, short* wav_i16, void* stream);
 
+/* ---- HiFi-GAN vocoder (gen_forward.py:31-37,109-116: the third vocoder target; hifigan.HiFiGAN; the definition is
+ *      DESIGN.md section 7, "HiFi-GAN vocoder") ---------------------------------------------------------------------- */
+/* The layout, the lengths and the packing are MelGAN's above with tail = 0 and ZERO edges instead of reflection: rows
+ * outside an item's [0, L), L = len[b] scale, are zeros, and rows at >= L are neither written nor read.
+ * ft_hifigan_tile_rows(kind, c): rows per workgroup tile for width c (kind 0: conv_in, c = n_mels; 1: upsample, c = cin,
+ *   in INPUT rows; 2: resconv; 3: conv_out, in samples; 4: respair, in rows of the intermediate -- a tile's output is
+ *   that minus k - 1); 0 where the width is not supported.
+ * ft_hifigan_conv_in: mel [B, n_mels, Tmax] as it is, no normalisation -> out [B Tmax, cout]: Conv1d(k = 7, padding 3);
+ *   w [7][n_mels][CP].  n_mels <= 128.
+ * ft_hifigan_upsample: LeakyReLU(0.1), ConvTranspose1d(cin, cout, k = 2 stride, stride, padding = stride / 2), stride
+ *   even: x at `scale` -> out at scale * stride; w [2 stride][cin][CP].  cin <= 512.
+ * ft_hifigan_resconv: out = res + bias + Conv1d(ch, ch, k, dilation, padding = dilation (k - 1) / 2)(lrelu_0.1(x)); w
+ *   [k][ch][CP]; k odd <= 11, dilation (k - 1) / 2 <= 40, ch <= 256, x != out.  res_mode 0: no res; 1: res = x; 2: res
+ *   [rows, ch] from memory.  acc_mode 0: out = value; 1: out += value; 2: out = (out + value) / nk (the average over a
+ *   stage's nk parallel blocks: launches on one stream, block 0 stores, later ones add, the last divides).
+ * ft_hifigan_respair: ResBlock1's pair in one launch, out = x + b2 + Conv1d(k, padding (k - 1) / 2)(lrelu(b1 + Conv1d(k,
+ *   dilation)(lrelu(x)))), the intermediate zero outside [0, L) and kept in LDS; acc_mode as above.  ch <= 64, dilation
+ *   (k - 1) / 2 <= 25.
+ * ft_hifigan_conv_out: LeakyReLU(0.01), Conv1d(ch, 1, k = 7, padding 3), tanh: x at `scale` -> wav [B, Tmax scale],
+ *   exactly 0 at j >= len[b] scale, and wav_i16 = truncate(clamp(32768 wav, -32768, 32767)); w [ch][32], column = tap.
+ *   ch <= 32. */
+int ft_hifigan_tile_rows(int kind, int c);
+int ft_hifigan_conv_in(const float* mel, const long* lens, int B, int n_mels, int Tmax, const float* w, const float* bias,
+                       int cout, float* out, int* err_flag, void* stream);
+int ft_hifigan_upsample(const float* x, const long* lens, int B, int Tmax, int scale, int cin, int cout, int stride,
+                        const float* w, const float* bias, float* out, void* stream);
+int ft_hifigan_resconv(const float* x, const long* lens, int B, int Tmax, int scale, int ch, int k, int dilation,
+                       const float* w, const float* bias, const float* res, int res_mode, int acc_mode, int nk, float* out,
+                       void* stream);
+int ft_hifigan_respair(const float* x, const long* lens, int B, int Tmax, int scale, int ch, int k, int dilation,
+                       const float* w1, const float* b1, const float* w2, const float* b2, int acc_mode, int nk, float* out,
+                       void* stream);
+int ft_hifigan_conv_out(const float* x, const long* lens, int B, int Tmax, int scale, int ch, const float* w, float bias,
+                        float* wav, short* wav_i16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
