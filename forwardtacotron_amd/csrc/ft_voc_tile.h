@@ -2,12 +2,14 @@
 // routine, the workgroup arrangements, the staging of a channels-last tile into LDS under either edge rule, and the
 // three kernels both generators run -- the input convolution, LeakyReLU + transposed convolution in polyphase form, and
 // the output stage.  The LeakyReLU slope (an Act type) and the edge rule (EDGE_REFLECT / EDGE_ZERO) are template
-// parameters; the layout and the rules common to every kernel are stated in the header of ft_melgan.hip.
+// parameters; the layout and the rules common to every kernel are stated in the header of ft_melgan.hip.  The arrangements
+// themselves, the LDS they need and every limit are ft_voc_plan.h's (host-only); the launchers are in ft_voc_launch.h.
 // Everything is a template or __forceinline__, in a named namespace that the two files open with a using-directive.
 #pragma once
 #include <math.h>
 
 #include "ft_common.h"
+#include "ft_voc_plan.h"
 
 namespace ft_voc_tile {
 
@@ -100,15 +102,18 @@ __device__ __forceinline__ void fill(f32x16 (&acc)[RT], float v) {
     for (int e = 0; e < 16; ++e) acc[r][e] = v;
 }
 
-// The arrangement of a workgroup: CMAX the widest input it stages, WR x WC waves (4 or 8), RT row tiles per wave.
+// The arrangement of a workgroup as a type: voc_plan::Arr's CMAX the widest input it stages, WR x WC waves (4 or 8), RT
+// row tiles per wave.  PlanCfg<kind, i> is arrangement i of the plan's table for a kind; no other Cfg is instantiated.
 template <int CMAX_, int WR_, int WC_, int RT_>
 struct Cfg {
+  static constexpr voc_plan::Arr ARR = {CMAX_, WR_, WC_, RT_};
   static constexpr int CMAX = CMAX_, WR = WR_, WC = WC_, RT = RT_;
-  static constexpr int ROWS = 32 * RT_ * WR_;          // output rows (input rows of the transposed convolution) per tile
-  static constexpr int XS = CMAX_ + 4;                 // (the kernels use the runtime width + 4; this sizes the LDS)
-  static constexpr int THREADS = 64 * WR_ * WC_;
-  static_assert(WR_ * WC_ == 4 || WR_ * WC_ == 8, "four or eight waves");
+  static constexpr int ROWS = ARR.rows();              // output rows (input rows of the transposed convolution) per tile
+  static constexpr int XS = ARR.xs();                  // (the kernels use the runtime width + 4; this sizes the LDS)
+  static constexpr int THREADS = ARR.threads();
 };
+template <int KIND, int I>
+using PlanCfg = Cfg<voc_plan::arr(KIND, I).cmax, voc_plan::arr(KIND, I).wr, voc_plan::arr(KIND, I).wc, voc_plan::arr(KIND, I).rt>;
 
 struct Wave {
   int lane, l31, hf, wr, wc;
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_in_kernel(const float* __rest
                                                       int tail, float pad_value, int n_mels, const float* __restrict__ w,
                                                       const float* __restrict__ bias, int cout, int CP, float* __restrict__ out,
                                                       int* err) {
-  __shared__ __attribute__((aligned(16))) float xs[(C::ROWS + 6) * C::XS];
+  __shared__ __attribute__((aligned(16))) float xs[voc_plan::lds_floats(voc_plan::CONV_IN, C::ARR)];
   const int b = blockIdx.y;
   const long t0 = (long)blockIdx.x * C::ROWS;
   const long n = item_rows(lens, b, Tmax, 0, 1, (blockIdx.x == 0 && threadIdx.x == 0) ? err : nullptr);
@@ -215,7 +220,7 @@ __global__ __launch_bounds__(C::THREADS) void upsample_kernel(const float* __res
                                                        int tail, int scale, int cin, int cout, int CP, int s,
                                                        const float* __restrict__ w, const float* __restrict__ bias,
                                                        float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float xs[(C::ROWS + 1) * C::XS];
+  __shared__ __attribute__((aligned(16))) float xs[voc_plan::lds_floats(voc_plan::UPSAMPLE, C::ARR)];
   const int b = blockIdx.y;
   const long q0 = (long)blockIdx.x * C::ROWS;
   const long Lin = item_rows(lens, b, Tmax, tail, scale, nullptr);
@@ -259,15 +264,18 @@ __global__ __launch_bounds__(C::THREADS) void upsample_kernel(const float* __res
 //    generator's FLOP), P goes to LDS, and sample t0 + o adds P[o + tap][tap] over the taps in ascending order.
 //    w: [C][32], column = tap.
 // ---------------------------------------------------------------------------------------------------
-constexpr int OUT_ROWS = 256, OUT_TILE = OUT_ROWS - 6, OUT_CMAX = 32;
+using voc_plan::OUT_ROWS;
+using voc_plan::OUT_TILE;
+typedef PlanCfg<voc_plan::CONV_OUT, 0> OutCfg;
 
 template <class Act, int EDGE>
-__global__ __launch_bounds__(256) void conv_out_kernel(const float* __restrict__ x, const long* __restrict__ lens, int Tmax,
+__global__ __launch_bounds__(OutCfg::THREADS) void conv_out_kernel(const float* __restrict__ x, const long* __restrict__ lens, int Tmax,
                                                        int tail, int scale, int ch, const float* __restrict__ w, float bias,
                                                        float* __restrict__ wav, short* __restrict__ wav_i16) {
-  typedef Cfg<OUT_CMAX, 4, 1, 2> C;
+  typedef OutCfg C;
   __shared__ __attribute__((aligned(16))) float xs[OUT_ROWS * C::XS];
   __shared__ float ps[OUT_ROWS * 8];
+  static_assert(sizeof(xs) + sizeof(ps) == voc_plan::lds_bytes(voc_plan::CONV_OUT, C::ARR), "the plan's bytes");
   const int b = blockIdx.y;
   const long t0 = (long)blockIdx.x * OUT_TILE;
   const long nout = item_rows(lens, b, Tmax, 0, scale, nullptr);

@@ -19,7 +19,8 @@ are parameter containers: their forward raises.  Every computation is a kernel o
 convolution, LeakyReLU + transposed convolution in polyphase form, the residual convolution (or ResBlock1's fused pair
 where the plan picks it) with the average over a stage's parallel blocks folded into each block's last launch, and the
 output stage (tanh, zero padding behind wav_len and int16 in one pass).  Weight norm is folded into packed tap-major
-panels once per parameter version, by melgan's own fold and pack functions.
+panels once per parameter version; the fold and pack functions, the pack cache and the entry points are those of
+gan_vocoder.py, shared with melgan.MelGAN.
 
 A RAGGED batch goes through `inference_batch(mel, mel_len)`; how mel_len is taken from the host or the device is the
 contract of ragged.py.  An item's samples are bit-identical alone and inside any batch, at any position, and nothing at
@@ -27,7 +28,7 @@ t >= mel_len[b] is ever loaded.
 """
 import json
 import os
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -35,13 +36,13 @@ import torch.nn as nn
 
 from . import _lib
 from . import hip as H
-from . import ragged
-from .melgan import _wn, fold_weight_norm, pack_bias, pack_conv, pack_conv_out, pack_conv_transpose, padded_width
+from .gan_vocoder import GanVocoder, _wn, pack_conv_transpose
 
 MAX_WAV_VALUE = 32768.0
 LRELU_SLOPE = 0.1
-MAX_KERNEL = 11                 # taps of a residual convolution
-MAX_HALO = H.HIFIGAN_MAX_HALO   # rows a residual convolution reaches to either side: dilation * (k - 1) / 2 <= 40
+# the launch plan's limits (csrc/ft_voc_plan.h, read from the library)
+MAX_KERNEL = H.HIFIGAN_MAX_KERNEL   # taps of a residual convolution: odd, at most 11
+MAX_HALO = H.HIFIGAN_MAX_HALO       # rows a residual convolution reaches to either side: dilation * (k - 1) / 2 <= 40
 CONFIG_KEYS = ('resblock', 'upsample_rates', 'upsample_kernel_sizes', 'upsample_initial_channel', 'resblock_kernel_sizes',
                'resblock_dilation_sizes', 'num_mels')
 V1 = dict(resblock='1', upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
@@ -89,18 +90,17 @@ class ResBlock2(nn.Module):
     forward = _container
 
 
-def pair_is_fused(width: int, k: int, d: int) -> bool:
-    """the plan for ResBlock1's (convs1[m], convs2[m]): one launch with the intermediate in LDS, or two launches of the
-    residual convolution.  Per width and (k, d) the winner of the same-process A/B of profiles/hifigan.txt section 2:
-    fused won every (k, d) at 32 channels (0.68-0.92 of the two launches' time) and k = 3 at 64 (0.93), and lost k = 7
-    and 11 at 64 (1.05, 1.12), where a tile gives 122 / 118 rows of the 128 it computes; d made no difference.  Above 64
-    channels the fused tile does not fit (csrc/ft_hifigan.hip)."""
-    if k < 3 or d * (k - 1) // 2 > H.HIFIGAN_PAIR_HALO:
-        return False
-    return width <= 32 or (width <= 64 and k == 3)
+pair_is_fused = H.hifigan_pair_is_fused
 
 
-class HiFiGAN(nn.Module):
+class HiFiGAN(GanVocoder):
+    """`inference_batch` is the published inference per item: `generator(mel[b:b+1, :, :mel_len[b]]).squeeze() * 32768`
+    of the mel as it is (no normalisation), clamped to [-32768, 32767] (the published script does not clamp: DESIGN.md,
+    "Deviations"); `forward` is generator(mel).  'stages' holds the outputs of conv_pre and, per upsampling stage, of the
+    transposed convolution and of the averaged residual blocks.  The shared entry points are gan_vocoder.GanVocoder's."""
+    NAME = 'HiFiGAN'
+    CHECKPOINT_KEY = 'generator'            # the published checkpoint's key
+
     def __init__(self, resblock: Union[str, int] = '1', upsample_rates: Sequence[int] = (8, 8, 2, 2),
                  upsample_kernel_sizes: Sequence[int] = (16, 16, 4, 4), upsample_initial_channel: int = 512,
                  resblock_kernel_sizes: Sequence[int] = (3, 7, 11),
@@ -145,8 +145,9 @@ class HiFiGAN(nn.Module):
                                   for i, (u, k) in enumerate(zip(rates, kernels))])
         self.resblocks = nn.ModuleList([block(c, k, ds) for c in widths for k, ds in zip(rk, rd)])
         self.conv_post = _wn(nn.Conv1d(widths[-1], 1, 7, 1, padding=3))
-        self._packs: Dict[Any, Any] = {}
-        self._len_flag = ragged.LenFlag()                  # the pinned word a device-side mel_len check reports through
+
+    n_mels = property(lambda self: self.num_mels)
+    _conv_out = property(lambda self: self.conv_post)
 
     # ------------------------------------------------------------------------------------------------
     @classmethod
@@ -175,66 +176,7 @@ class HiFiGAN(nn.Module):
         """a file that holds the generator's state_dict directly or under 'generator' (the published checkpoint's key);
         config: the published config.json as a dict or a path (default: V1).  Every entry must be there and none may be
         unknown.  **Tested on a synthetic file of that layout only.**"""
-        ck = torch.load(path, map_location='cpu')
-        state = ck['generator'] if isinstance(ck, dict) and 'generator' in ck else ck
-        voc = cls.v1() if config is None else cls.from_config(config)
-        try:
-            missing, unexpected = voc.load_state_dict(state, strict=False)
-        except RuntimeError as e:                          # shapes of another configuration
-            raise _lib.FtError(f'HiFiGAN.from_checkpoint: {path} does not fit the configuration: {str(e)[:400]}') from None
-        if missing or unexpected:
-            raise _lib.FtError(f'HiFiGAN.from_checkpoint: {path} lacks {sorted(missing)} and has unknown {sorted(unexpected)}')
-        return voc
-
-    # ------------------------------------------------------------------------------------------------
-    def _pack(self, key, srcs: Sequence[torch.Tensor], make):
-        """weight-derived operands, rebuilt when a source tensor changes (in-place updates bump _version)"""
-        tag = tuple((s.data_ptr(), s._version, s.device) for s in srcs)
-        hit = self._packs.get(key)
-        if hit is None or hit[0] != tag:
-            hit = (tag, make())
-            self._packs[key] = hit
-        return hit[1]
-
-    def _panel(self, conv: nn.Module, pack=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(packed folded weight [k, cin, CP], padded bias) of one weight-normed convolution"""
-        v, g, b = conv.weight_v, conv.weight_g, conv.bias
-
-        def make():
-            with torch.no_grad():
-                w = fold_weight_norm(v, g)
-                if pack is not None:
-                    return pack(w), pack_bias(b)
-                return pack_conv(w).reshape(w.shape[2], w.shape[1], padded_width(w.shape[0])), pack_bias(b)
-        return self._pack(id(conv), (v, g, b), make)
-
-    def _out_panel(self) -> Tuple[torch.Tensor, float]:
-        v, g, b = self.conv_post.weight_v, self.conv_post.weight_g, self.conv_post.bias
-
-        def make():
-            with torch.no_grad():                          # (the one read-back: once per parameter version)
-                return pack_conv_out(fold_weight_norm(v, g)), float(b.detach().cpu()[0])
-        return self._pack('out', (v, g, b), make)
-
-    def _device(self) -> torch.device:
-        dev = self.conv_pre.bias.device
-        if dev.type != 'cuda' or any(p.device != dev or p.dtype != torch.float32 for p in self.parameters()):
-            raise _lib.FtError('HiFiGAN runs on an MI355X (HIP) device only, in float32; there is no CPU fallback: move '
-                               "it with .to('cuda')")
-        return dev
-
-    def _check_mel(self, what: str, mel) -> None:
-        if not isinstance(mel, torch.Tensor) or mel.dim() != 3:
-            raise _lib.FtError(f'{what}: mel must be a [B, n_mels, Tmax] tensor')
-        if mel.dtype != torch.float32:
-            raise _lib.FtError(f'{what}: mel must be float32, got {mel.dtype}')
-        if mel.shape[1] != self.num_mels:
-            raise _lib.FtError(f'{what}: expected {self.num_mels} mel channels, got {mel.shape[1]}')
-        if mel.shape[0] < 1 or mel.shape[2] < 1:
-            raise _lib.FtError(f'{what}: an empty batch')
-        if torch.is_grad_enabled() and (mel.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise _lib.FtError(f'HiFiGAN.{what} is an inference path (no autograd graph): call it under torch.no_grad(), '
-                               'or with an input and parameters that do not require grad')
+        return cls._load_checkpoint(path, lambda: cls.v1() if config is None else cls.from_config(config), fit_error=True)
 
     def _stage(self, i: int, x: torch.Tensor, ml: Optional[torch.Tensor], B: int, Tmax: int, scale: int) -> torch.Tensor:
         """(sum over j of resblocks[i nk + j](x), j ascending) / nk.  Each block's last launch writes the stage's buffer:
@@ -271,10 +213,10 @@ class HiFiGAN(nn.Module):
                 y = out
         return total
 
-    def _generate(self, mel: torch.Tensor, ml: Optional[torch.Tensor], err: Optional[torch.Tensor], keep: bool
-                  ) -> Dict[str, Any]:
-        """the generator over a batch -> {'wav', 'wav_int16'} and, with keep, 'stages': the input convolution's output,
-        then per upsampling stage the transposed convolution's and the averaged residual blocks'"""
+    def _generate(self, mel: torch.Tensor, ml: Optional[torch.Tensor], tail: int, err: Optional[torch.Tensor],
+                  keep: bool) -> Dict[str, Any]:
+        """the generator over a batch (tail is always 0) -> {'wav', 'wav_int16'} and, with keep, 'stages': the input
+        convolution's output, then per upsampling stage the transposed convolution's and the averaged residual blocks'"""
         B, _, Tmax = mel.shape
         stages: List[torch.Tensor] = []
         w, b = self._panel(self.conv_pre)
@@ -294,61 +236,6 @@ class HiFiGAN(nn.Module):
         if keep:
             out['stages'] = stages
         return out
-
-    # ------------------------------------------------------------------------------------------------
-    def inference_batch(self, mel: torch.Tensor, mel_len: torch.Tensor, keep_stages: bool = False) -> Dict[str, Any]:
-        """The published inference for a RAGGED batch (generate_batch's 'mel_post' and 'mel_len'): item b is what
-        `generator(mel[b:b+1, :, :mel_len[b]]).squeeze() * 32768` gives alone, clamped to [-32768, 32767] (the
-        published script does not clamp: DESIGN.md, "Deviations") and truncated to int16.
-
-        mel: float32 [B, n_mels, Tmax] on the device, as it is (no normalisation); what lies at t >= mel_len[b]
-        (padding, NaN, Inf) is never loaded.
-        mel_len: int64 [B], on the host or the device, 1 <= mel_len[b] <= Tmax.
-        -> {'wav': float32 [B, hop * Tmax], the tanh output before quantisation, exactly 0 at j >= wav_len[b];
-            'wav_len': int64 [B] = hop * mel_len on the device; 'wav_int16': int16 [B, hop * Tmax]}, hop = the product
-            of the upsample rates.
-        keep_stages adds 'stages' (for the tests): the outputs of conv_pre and, per upsampling stage, of the transposed
-        convolution and of the averaged residual blocks.
-
-        An item's samples are bit-identical alone (Tmax its own length) and in any batch at any position.  Lengths follow
-        ragged.py: a host-side mel_len is checked up front and nothing synchronises; a device-side one is clamped inside
-        the kernels and its FtError is raised at the end of the call, after one synchronisation, through ONE pinned host
-        word kept on this object."""
-        what = 'inference_batch'
-        self._check_mel(what, mel)
-        B, _, Tmax = mel.shape
-        if not isinstance(mel_len, torch.Tensor) or mel_len.dim() != 1 or mel_len.numel() != B or \
-                mel_len.dtype != torch.int64:
-            raise _lib.FtError(f'{what}: mel_len must be an int64 tensor [B = {B}]')
-        if not mel_len.is_cuda and (int(mel_len.min()) < 1 or int(mel_len.max()) > Tmax):
-            raise _lib.FtError(f"{ragged.range_message(what, 'mel_len', 1, Tmax, 'Tmax')} (got {mel_len.tolist()})")
-        dev = self._device()
-        if not mel.is_cuda:
-            raise _lib.FtError(f'{what}: mel must be on the HIP device')
-        mel = mel.contiguous()
-        ml, err = ragged.device_lens(mel_len, B, 1, Tmax, what, 'mel_len', 'Tmax', dev)
-        out = self._generate(mel, ml, err, keep_stages)
-        out['wav_len'] = ml * self.hop_length
-        self._len_flag.check(err, ragged.range_message(what, 'mel_len', 1, Tmax, 'Tmax'))
-        return out
-
-    def inference(self, mel: torch.Tensor) -> np.ndarray:
-        """the published inference of one mel, [n_mels, T] or [1, n_mels, T] on the device -> int16 numpy [hop * T]"""
-        if isinstance(mel, torch.Tensor) and mel.dim() == 2:
-            mel = mel.unsqueeze(0)
-        if not isinstance(mel, torch.Tensor) or mel.dim() != 3 or mel.shape[0] != 1:
-            raise _lib.FtError('inference: one mel, [n_mels, T] or [1, n_mels, T] (a batch goes through inference_batch)')
-        out = self.inference_batch(mel, torch.tensor([mel.shape[2]], dtype=torch.int64))
-        return out['wav_int16'][0].cpu().numpy()
-
-    def forward(self, mel: torch.Tensor) -> torch.Tensor:
-        """generator(mel): float32 [B, n_mels, T] on the device -> [B, 1, hop * T].  Inference only; every item has T
-        frames."""
-        self._check_mel('forward', mel)
-        self._device()
-        if not mel.is_cuda:
-            raise _lib.FtError('forward: mel must be on the HIP device')
-        return self._generate(mel.contiguous(), None, None, False)['wav'].unsqueeze(1)
 
 
 __all__ = ['HiFiGAN', 'ResBlock1', 'ResBlock2', 'pair_is_fused', 'V1', 'V2', 'V3', 'MAX_HALO', 'MAX_KERNEL']

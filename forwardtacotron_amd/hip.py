@@ -1709,45 +1709,131 @@ def taco_mel_scatter(dwp: torch.Tensor, dw: torch.Tensor, n_mels: int, max_r: in
 
 
 # ---------------------------------------------------------------------------------------------------
-# MelGAN generator on a ragged batch (csrc/ft_melgan.hip; the public interface is melgan.MelGAN).  Activations are
-# channels-last [B * (Tmax + tail) * scale, C]; mel_len int64 [B] on the device, or None: every item has Tmax frames.
-# Weights and biases come packed from melgan.pack_*.
+# The GAN vocoders on a ragged batch (csrc/ft_melgan.hip, ft_hifigan.hip; the public interfaces are melgan.MelGAN and
+# hifigan.HiFiGAN).  Activations are channels-last [B * (Tmax + tail) * scale, C]; mel_len int64 [B] on the device, or
+# None: every item has Tmax frames.  Weights and biases come packed from gan_vocoder.pack_*.  MelGAN reflects at an
+# item's edges and carries `tail` appended frames; HiFi-GAN's edges are zeros and its tail is 0.  The three kernels both
+# generators run have ONE wrapper each, taking the family; the melgan_* / hifigan_* names bind it.  Every limit and
+# every choice of the launch plan is csrc/ft_voc_plan.h's, read through ft_voc_plan.
 # ---------------------------------------------------------------------------------------------------
+_MELGAN_KINDS = ('conv_in', 'upsample', 'resblock', 'conv_out')
+_HIFIGAN_KINDS = ('conv_in', 'upsample', 'resconv', 'conv_out', 'respair')
+_VOC_LIMITS = {'HIFIGAN_MAX_KERNEL': 0, 'HIFIGAN_MAX_HALO': 1, 'HIFIGAN_PAIR_HALO': 2}      # name -> ft_voc_plan field
+_VOC_PAIR_IS_FUSED = 3
+_pair_plan = {}
+
+
+def __getattr__(name: str):
+    """HIFIGAN_MAX_KERNEL (taps of a residual convolution), HIFIGAN_MAX_HALO (resconv: dilation * (k - 1) / 2 rows on
+    either side of a tile) and HIFIGAN_PAIR_HALO (respair: the same for its first convolution), read from the library on
+    first use: importing this module loads nothing"""
+    if name in _VOC_LIMITS:
+        value = globals()[name] = int(_lib.query('ft_voc_plan', _VOC_LIMITS[name], 0, 0, 0))
+        return value
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
+
+
+def hifigan_pair_is_fused(width: int, k: int, d: int) -> bool:
+    """the plan for ResBlock1's (convs1[m], convs2[m]): True = one ft_hifigan_respair launch with the intermediate in
+    LDS, False = two launches of the residual convolution (the rule and its measurements: csrc/ft_voc_plan.h).  A pure
+    function of its arguments, asked of the library once each"""
+    key = (width, k, d)
+    hit = _pair_plan.get(key)
+    if hit is None:
+        hit = _pair_plan[key] = bool(_lib.query('ft_voc_plan', _VOC_PAIR_IS_FUSED, int(width), int(k), int(d)))
+    return hit
+
+
 def melgan_tile_rows(kind: str, c: int) -> int:
     """rows per workgroup tile of the launch plan for width c: kind 'conv_in' (c = n_mels), 'upsample' (c = cin, input
     rows), 'resblock', 'conv_out' (samples); 0 where the width is not supported"""
-    return int(_lib.query('ft_melgan_tile_rows', ('conv_in', 'upsample', 'resblock', 'conv_out').index(kind), int(c)))
+    return int(_lib.query('ft_melgan_tile_rows', _MELGAN_KINDS.index(kind), int(c)))
+
+
+def hifigan_tile_rows(kind: str, c: int) -> int:
+    """rows per workgroup tile of the launch plan for width c: kind 'conv_in' (c = n_mels), 'upsample' (c = cin, input
+    rows), 'resconv', 'conv_out' (samples), 'respair' (rows of the intermediate: a tile's output is that minus k - 1); 0
+    where the width is not supported"""
+    return int(_lib.query('ft_hifigan_tile_rows', _HIFIGAN_KINDS.index(kind), int(c)))
+
+
+def _voc_conv_in(family, mel, mel_len, tail, pad_value, w, bias, cout, err, alloc):
+    _chk(mel, 'mel'); _chk(w, 'w'); _chk(bias, 'bias')
+    B, C, Tmax = mel.shape
+    CP = -(-cout // 32) * 32
+    if tuple(w.shape) != (7, C, CP) or bias.numel() != CP:
+        raise _lib.FtError(f'{family}_conv_in: w {tuple(w.shape)} / bias {tuple(bias.shape)} for [7, {C}, {CP}]')
+    if mel_len is not None:
+        _chk(mel_len, 'mel_len', torch.int64)
+    out = alloc(B * (Tmax + tail), cout, dtype=torch.float32, device=mel.device)
+    extra = (tail, float(pad_value)) if family == 'melgan' else ()      # (HiFi-GAN's entry points take no tail)
+    _lib.call(f'ft_{family}_conv_in', _p(mel), _p(mel_len), B, C, Tmax, *extra, _p(w), _p(bias), cout, _p(out), _p(err),
+              _stream())
+    return out
+
+
+def _voc_upsample(family, x, mel_len, B, Tmax, tail, scale, stride, w, bias, cout, alloc):
+    _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias')
+    rows, cin = x.shape
+    CP = -(-cout // 32) * 32
+    if rows != B * (Tmax + tail) * scale or tuple(w.shape) != (2 * stride, cin, CP) or bias.numel() != CP:
+        raise _lib.FtError(f'{family}_upsample: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} for '
+                           f'{B * (Tmax + tail) * scale} rows and w [{2 * stride}, {cin}, {CP}]')
+    out = alloc(rows * stride, cout, dtype=torch.float32, device=x.device)
+    extra = (tail,) if family == 'melgan' else ()
+    _lib.call(f'ft_{family}_upsample', _p(x), _p(mel_len), B, Tmax, *extra, scale, cin, cout, stride, _p(w), _p(bias),
+              _p(out), _stream())
+    return out
+
+
+def _voc_conv_out(family, x, mel_len, B, Tmax, tail, scale, w, bias, alloc):
+    _chk(x, 'x'); _chk(w, 'w')
+    rows, C = x.shape
+    if rows != B * (Tmax + tail) * scale or tuple(w.shape) != (C, 32):
+        raise _lib.FtError(f'{family}_conv_out: x {tuple(x.shape)}, w {tuple(w.shape)} for {B * (Tmax + tail) * scale} rows '
+                           f'and w [{C}, 32]')
+    wav = alloc(B, Tmax * scale, dtype=torch.float32, device=x.device)
+    i16 = alloc(B, Tmax * scale, dtype=torch.int16, device=x.device)
+    extra = (tail,) if family == 'melgan' else ()
+    _lib.call(f'ft_{family}_conv_out', _p(x), _p(mel_len), B, Tmax, *extra, scale, C, _p(w), float(bias), _p(wav), _p(i16),
+              _stream())
+    return wav, i16
 
 
 def melgan_conv_in(mel: torch.Tensor, mel_len: Optional[torch.Tensor], tail: int, pad_value: float, w: torch.Tensor,
                    bias: torch.Tensor, cout: int, err: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
     """mel [B, n_mels, Tmax] -> [B * (Tmax + tail), cout]: normalise, append the tail, reflect 3, Conv1d(k = 7)"""
-    _chk(mel, 'mel'); _chk(w, 'w'); _chk(bias, 'bias')
-    B, C, Tmax = mel.shape
-    CP = -(-cout // 32) * 32
-    if tuple(w.shape) != (7, C, CP) or bias.numel() != CP:
-        raise _lib.FtError(f'melgan_conv_in: w {tuple(w.shape)} / bias {tuple(bias.shape)} for [7, {C}, {CP}]')
-    if mel_len is not None:
-        _chk(mel_len, 'mel_len', torch.int64)
-    out = alloc(B * (Tmax + tail), cout, dtype=torch.float32, device=mel.device)
-    _lib.call('ft_melgan_conv_in', _p(mel), _p(mel_len), B, C, Tmax, tail, float(pad_value), _p(w), _p(bias), cout, _p(out),
-              _p(err), _stream())
-    return out
+    return _voc_conv_in('melgan', mel, mel_len, tail, pad_value, w, bias, cout, err, alloc)
 
 
 def melgan_upsample(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, tail: int, scale: int,
                     stride: int, w: torch.Tensor, bias: torch.Tensor, cout: int, alloc=torch.empty) -> torch.Tensor:
     """x [B * (Tmax + tail) * scale, cin] -> [B * (Tmax + tail) * scale * stride, cout]: LeakyReLU + ConvTranspose1d"""
-    _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias')
-    rows, cin = x.shape
-    CP = -(-cout // 32) * 32
-    if rows != B * (Tmax + tail) * scale or tuple(w.shape) != (2 * stride, cin, CP) or bias.numel() != CP:
-        raise _lib.FtError(f'melgan_upsample: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} for '
-                           f'{B * (Tmax + tail) * scale} rows and w [{2 * stride}, {cin}, {CP}]')
-    out = alloc(rows * stride, cout, dtype=torch.float32, device=x.device)
-    _lib.call('ft_melgan_upsample', _p(x), _p(mel_len), B, Tmax, tail, scale, cin, cout, stride, _p(w), _p(bias), _p(out),
-              _stream())
-    return out
+    return _voc_upsample('melgan', x, mel_len, B, Tmax, tail, scale, stride, w, bias, cout, alloc)
+
+
+def melgan_conv_out(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, tail: int, scale: int,
+                    w: torch.Tensor, bias: float, alloc=torch.empty):
+    """x [B * (Tmax + tail) * scale, C] -> (wav float32 [B, Tmax * scale], zero at j >= mel_len[b] * scale; wav_int16)"""
+    return _voc_conv_out('melgan', x, mel_len, B, Tmax, tail, scale, w, bias, alloc)
+
+
+def hifigan_conv_in(mel: torch.Tensor, mel_len: Optional[torch.Tensor], w: torch.Tensor, bias: torch.Tensor, cout: int,
+                    err: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
+    """mel [B, n_mels, Tmax] -> [B * Tmax, cout]: Conv1d(k = 7, padding 3) of the mel as it is"""
+    return _voc_conv_in('hifigan', mel, mel_len, 0, 0.0, w, bias, cout, err, alloc)
+
+
+def hifigan_upsample(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, stride: int,
+                     w: torch.Tensor, bias: torch.Tensor, cout: int, alloc=torch.empty) -> torch.Tensor:
+    """x [B * Tmax * scale, cin] -> [B * Tmax * scale * stride, cout]: LeakyReLU(0.1) + ConvTranspose1d"""
+    return _voc_upsample('hifigan', x, mel_len, B, Tmax, 0, scale, stride, w, bias, cout, alloc)
+
+
+def hifigan_conv_out(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, w: torch.Tensor,
+                     bias: float, alloc=torch.empty):
+    """x [B * Tmax * scale, C] -> (wav float32 [B, Tmax * scale], zero at j >= mel_len[b] * scale; wav_int16)"""
+    return _voc_conv_out('hifigan', x, mel_len, B, Tmax, 0, scale, w, bias, alloc)
 
 
 def melgan_resblock(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, tail: int, scale: int,
@@ -1769,68 +1855,6 @@ def melgan_resblock(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tm
         raise _lib.FtError('melgan_resblock: out must be another buffer of the shape of x')
     _lib.call('ft_melgan_resblock', _p(x), _p(mel_len), B, Tmax, tail, scale, C, dilation, _p(w1), _p(b1), _p(w2), _p(b2),
               _p(ws), _p(bs), _p(out), _stream())
-    return out
-
-
-def melgan_conv_out(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, tail: int, scale: int,
-                    w: torch.Tensor, bias: float, alloc=torch.empty):
-    """x [B * (Tmax + tail) * scale, C] -> (wav float32 [B, Tmax * scale], zero at j >= mel_len[b] * scale; wav_int16)"""
-    _chk(x, 'x'); _chk(w, 'w')
-    rows, C = x.shape
-    if rows != B * (Tmax + tail) * scale or tuple(w.shape) != (C, 32):
-        raise _lib.FtError(f'melgan_conv_out: x {tuple(x.shape)}, w {tuple(w.shape)} for {B * (Tmax + tail) * scale} rows '
-                           f'and w [{C}, 32]')
-    wav = alloc(B, Tmax * scale, dtype=torch.float32, device=x.device)
-    i16 = alloc(B, Tmax * scale, dtype=torch.int16, device=x.device)
-    _lib.call('ft_melgan_conv_out', _p(x), _p(mel_len), B, Tmax, tail, scale, C, _p(w), float(bias), _p(wav), _p(i16),
-              _stream())
-    return wav, i16
-
-
-# ---------------------------------------------------------------------------------------------------
-# HiFi-GAN generator on a ragged batch (csrc/ft_hifigan.hip; the public interface is hifigan.HiFiGAN).  Activations are
-# channels-last [B * Tmax * scale, C]; mel_len int64 [B] on the device, or None: every item has Tmax frames.  Weights and
-# biases come packed from melgan.pack_*.  Edges are zeros.
-# ---------------------------------------------------------------------------------------------------
-_HIFIGAN_KINDS = ('conv_in', 'upsample', 'resconv', 'conv_out', 'respair')
-HIFIGAN_MAX_HALO = 40           # resconv: dilation * (k - 1) / 2 rows on either side of a tile
-HIFIGAN_PAIR_HALO = 25          # respair: the same for its first convolution
-
-
-def hifigan_tile_rows(kind: str, c: int) -> int:
-    """rows per workgroup tile of the launch plan for width c: kind 'conv_in' (c = n_mels), 'upsample' (c = cin, input
-    rows), 'resconv', 'conv_out' (samples), 'respair' (rows of the intermediate: a tile's output is that minus k - 1); 0
-    where the width is not supported"""
-    return int(_lib.query('ft_hifigan_tile_rows', _HIFIGAN_KINDS.index(kind), int(c)))
-
-
-def hifigan_conv_in(mel: torch.Tensor, mel_len: Optional[torch.Tensor], w: torch.Tensor, bias: torch.Tensor, cout: int,
-                    err: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
-    """mel [B, n_mels, Tmax] -> [B * Tmax, cout]: Conv1d(k = 7, padding 3) of the mel as it is"""
-    _chk(mel, 'mel'); _chk(w, 'w'); _chk(bias, 'bias')
-    B, C, Tmax = mel.shape
-    CP = -(-cout // 32) * 32
-    if tuple(w.shape) != (7, C, CP) or bias.numel() != CP:
-        raise _lib.FtError(f'hifigan_conv_in: w {tuple(w.shape)} / bias {tuple(bias.shape)} for [7, {C}, {CP}]')
-    if mel_len is not None:
-        _chk(mel_len, 'mel_len', torch.int64)
-    out = alloc(B * Tmax, cout, dtype=torch.float32, device=mel.device)
-    _lib.call('ft_hifigan_conv_in', _p(mel), _p(mel_len), B, C, Tmax, _p(w), _p(bias), cout, _p(out), _p(err), _stream())
-    return out
-
-
-def hifigan_upsample(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, stride: int,
-                     w: torch.Tensor, bias: torch.Tensor, cout: int, alloc=torch.empty) -> torch.Tensor:
-    """x [B * Tmax * scale, cin] -> [B * Tmax * scale * stride, cout]: LeakyReLU(0.1) + ConvTranspose1d"""
-    _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias')
-    rows, cin = x.shape
-    CP = -(-cout // 32) * 32
-    if rows != B * Tmax * scale or tuple(w.shape) != (2 * stride, cin, CP) or bias.numel() != CP:
-        raise _lib.FtError(f'hifigan_upsample: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} for '
-                           f'{B * Tmax * scale} rows and w [{2 * stride}, {cin}, {CP}]')
-    out = alloc(rows * stride, cout, dtype=torch.float32, device=x.device)
-    _lib.call('ft_hifigan_upsample', _p(x), _p(mel_len), B, Tmax, scale, cin, cout, stride, _p(w), _p(bias), _p(out),
-              _stream())
     return out
 
 
@@ -1883,17 +1907,3 @@ def hifigan_respair(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tm
     _lib.call('ft_hifigan_respair', _p(x), _p(mel_len), B, Tmax, scale, C, int(w1.shape[0]), dilation, _p(w1), _p(b1),
               _p(w2), _p(b2), acc_mode, nk, _p(out), _stream())
     return out
-
-
-def hifigan_conv_out(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, w: torch.Tensor,
-                     bias: float, alloc=torch.empty):
-    """x [B * Tmax * scale, C] -> (wav float32 [B, Tmax * scale], zero at j >= mel_len[b] * scale; wav_int16)"""
-    _chk(x, 'x'); _chk(w, 'w')
-    rows, C = x.shape
-    if rows != B * Tmax * scale or tuple(w.shape) != (C, 32):
-        raise _lib.FtError(f'hifigan_conv_out: x {tuple(x.shape)}, w {tuple(w.shape)} for {B * Tmax * scale} rows and w '
-                           f'[{C}, 32]')
-    wav = alloc(B, Tmax * scale, dtype=torch.float32, device=x.device)
-    i16 = alloc(B, Tmax * scale, dtype=torch.int16, device=x.device)
-    _lib.call('ft_hifigan_conv_out', _p(x), _p(mel_len), B, Tmax, scale, C, _p(w), float(bias), _p(wav), _p(i16), _stream())
-    return wav, i16

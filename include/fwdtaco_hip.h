@@ -1075,6 +1075,13 @@ int ft_hifigan_respair(const float* x, const long* lens, int B, int Tmax, int sc
 int ft_hifigan_conv_out(const float* x, const long* lens, int B, int Tmax, int scale, int ch, const float* w, float bias,
                         float* wav, short* wav_i16, void* stream);
 
+/* ---- the GAN vocoders' launch plan (csrc/ft_voc_plan.h, host-only) ------------------------------------------------------ */
+/* ft_voc_plan(field, a, b, c): one value of the plan both vocoders launch by; host-only, no device is touched.  field 0:
+ * residual taps at most (11); 1: resconv halo at most (40); 2: respair first-convolution halo at most (25); 3: 1 where
+ * ResBlock1's pair at width a, k = b taps, dilation c runs as ONE ft_hifigan_respair launch, 0 where it runs as two
+ * ft_hifigan_resconv launches.  Unused arguments are ignored; an unknown field answers -1. */
+int ft_voc_plan(int field, int a, int b, int c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,22 +10,17 @@ Bounds.  Each kernel alone: |err| <= (K + 4) 2^-24 sum |w| |x| per output, evalu
 fp32 input (melgan_cpu.*_stage; for the fused block plus the first convolution's bound carried through the second):
 a-priori, nothing measured.  End to end: the max abs error of wav against float64 is at most 2x that of the fp32
 stock-torch CPU route on the same weights and mels.  Every comparison prints its figure before it asserts."""
-import numpy as np
 import pytest
 import torch
 
 import melgan_cpu as R
+import vocoder_contract as VC
 
 pytestmark = pytest.mark.gpu
 
 LENS = [23, 1, 2, 7]
 HOP = 256
 TANH_ULPS = 4 * R.U            # tanhf: within 2 ulp of a value of magnitude <= 1, plus the rounding of its argument's last bit
-
-
-def _poison(*shape, dtype=torch.float32, device=None):
-    t = torch.empty(*shape, dtype=dtype, device=device)
-    return t.fill_(float('nan')) if dtype.is_floating_point else t.fill_(-12345)
 
 
 class Case:
@@ -143,18 +138,13 @@ def test_an_item_one_frame_past_a_tile_boundary_at_the_8x_stage():
     assert e_gpu <= 2.0 * e_cpu
 
 
-# ---- 3. quantisation --------------------------------------------------------------------------------------------------
+# ---- 3. the contract shared with the HiFi-GAN vocoder (tests/vocoder_contract.py) ---------------------------------------
 def test_int16_is_the_scale_clamp_and_truncate_of_the_returned_wav(case):
-    assert case.out['wav_int16'].dtype == torch.int16
-    assert torch.equal(case.out['wav_int16'], R.int16_of(case.out['wav']))
+    VC.check_int16_is_the_scale_clamp_and_truncate_of_the_returned_wav(case, R.int16_of)
 
 
 def test_inference_is_item_0_of_inference_batch(case):
-    n = case.lens[0]
-    with torch.no_grad():
-        got = case.voc.inference(case.mel[0:1, :, :n].cuda())
-    assert isinstance(got, np.ndarray) and got.dtype == np.int16 and got.shape == (HOP * n,)
-    assert np.array_equal(got, case.out['wav_int16'][0, :HOP * n].numpy())
+    VC.check_inference_is_item_0_of_inference_batch(case)
 
 
 def test_forward_is_the_generator_without_the_tail(narrow):
@@ -169,100 +159,28 @@ def test_forward_is_the_generator_without_the_tail(narrow):
     assert e_gpu <= 2.0 * e_cpu
 
 
-# ---- 4. bit-identical items -------------------------------------------------------------------------------------------
 def test_items_are_bit_identical_alone_and_at_any_position(case):
-    order = [2, 0, 3, 1]
-    mel = torch.stack([case.mel[i] for i in order]).cuda()
-    out = case.run(mel, torch.tensor([case.lens[i] for i in order]))
-    for pos, i in enumerate(order):
-        n = case.lens[i]
-        assert torch.equal(out['wav'][pos, :HOP * n].cpu(), case.out['wav'][i, :HOP * n]), i
-        alone = case.run(case.mel[i:i + 1, :, :n].cuda(), torch.tensor([n]))
-        assert alone['wav'].shape == (1, HOP * n)
-        assert torch.equal(alone['wav'][0].cpu(), case.out['wav'][i, :HOP * n]), i
-        assert torch.equal(alone['wav_int16'][0].cpu(), case.out['wav_int16'][i, :HOP * n]), i
+    VC.check_items_are_bit_identical_alone_and_at_any_position(case)
 
 
-# ---- 5. NaN isolation -------------------------------------------------------------------------------------------------
 def test_nan_padding_a_nan_item_and_poisoned_buffers_change_nothing(case, monkeypatch):
     from forwardtacotron_amd import melgan as M
-    monkeypatch.setattr(M, '_empty', _poison)
-    mel = case.mel.clone()
-    for b, n in enumerate(case.lens):
-        mel[b, :, n:] = float('nan') if b % 2 else float('inf')
-    mel[2] = float('nan')                                   # a whole NaN item
-    out = {k: v.cpu() for k, v in case.run(mel.cuda(), case.mel_len).items()}
-    for b, n in enumerate(case.lens):
-        assert not out['wav'][b, HOP * n:].any() and not out['wav_int16'][b, HOP * n:].any(), b     # exactly 0, NaN is not
-        if b != 2:
-            assert torch.equal(out['wav'][b], case.out['wav'][b]) and torch.equal(out['wav_int16'][b], case.out['wav_int16'][b])
-    assert torch.isnan(out['wav'][2, :HOP * case.lens[2]]).all()
-    assert not case.out['wav'][0, HOP * case.lens[0]:].any()
+    VC.check_nan_padding_a_nan_item_and_poisoned_buffers_change_nothing(case, M, monkeypatch)
 
 
-# ---- 6. device-side lengths -------------------------------------------------------------------------------------------
 def test_device_side_mel_len_gives_the_same_bits_and_reports_a_bad_length(case):
-    from forwardtacotron_amd._lib import FtError
-    mel = case.mel.cuda()
-    out = case.run(mel, case.mel_len.cuda())
-    assert torch.equal(out['wav'].cpu(), case.out['wav']) and torch.equal(out['wav_int16'].cpu(), case.out['wav_int16'])
-    assert torch.equal(out['wav_len'].cpu(), case.out['wav_len'])
-    for bad in ([23, 0, 2, 7], [24, 1, 2, 7], [23, 1, -5, 7], [23, 1, 2, 1 << 40]):
-        with pytest.raises(FtError, match='mel_len must be in'):
-            case.run(mel, torch.tensor(bad, dtype=torch.int64).cuda())
-    torch.cuda.synchronize()
-    again = case.run(mel, case.mel_len.cuda())               # the clamped runs indexed nothing out of bounds and broke nothing
-    assert torch.equal(again['wav'].cpu(), case.out['wav'])
+    VC.check_device_side_mel_len_gives_the_same_bits_and_reports_a_bad_length(case)
 
 
 def test_autograd_is_refused(narrow):
-    from forwardtacotron_amd._lib import FtError
-    with pytest.raises(FtError, match='no autograd'):
-        narrow.voc.inference_batch(narrow.mel.cuda(), narrow.mel_len)
+    VC.check_autograd_is_refused(narrow)
 
 
 def test_weights_are_repacked_when_a_parameter_changes(narrow):
     from forwardtacotron_amd.melgan import MelGAN
-    voc = MelGAN(**R.NARROW)
-    voc.load_state_dict(narrow.ref32.state_dict())
-    voc = voc.cuda().eval()
-    mel = narrow.mel.cuda()
-    with torch.no_grad():
-        a = voc.inference_batch(mel, narrow.mel_len)['wav'].cpu()
-        packs = {k: v[1] for k, v in voc._packs.items()}
-        b = voc.inference_batch(mel, narrow.mel_len)['wav'].cpu()
-        assert all(voc._packs[k][1] is v for k, v in packs.items())          # folded once, not per call
-        voc.generator[16].weight_g.mul_(0.5)
-        c = voc.inference_batch(mel, narrow.mel_len)['wav'].cpu()
-    assert torch.equal(a, narrow.out['wav']) and torch.equal(a, b) and not torch.equal(a, c)
+    VC.check_weights_are_repacked_when_a_parameter_changes(narrow, lambda: MelGAN(**R.NARROW),
+                                                           lambda voc: voc.generator[16].weight_g)
 
 
-# ---- 7. the real producer ---------------------------------------------------------------------------------------------
 def test_generate_batch_output_goes_straight_in(narrow):
-    from forwardtacotron_amd import hip
-    from forwardtacotron_amd.model import ForwardTacotron
-    from helpers import TINY
-    torch.manual_seed(4)
-    m = ForwardTacotron(**dict(TINY, n_mels=8)).cuda().eval()
-    x_len = torch.tensor([9, 4, 12])
-    x = torch.randint(1, 100, (3, 12))
-    for b, n in enumerate(x_len):
-        x[b, n:] = 0
-    with torch.no_grad():
-        gen = m.generate_batch(x.cuda(), x_len)
-        out = narrow.voc.inference_batch(gen['mel_post'], gen['mel_len'])
-    torch.cuda.synchronize()
-    hip.check_rnn_status()
-    mel, mel_len = gen['mel_post'].cpu(), gen['mel_len'].cpu()
-    assert out['wav'].shape == (3, HOP * mel.shape[2]) and torch.equal(out['wav_len'].cpu(), HOP * mel_len)
-    assert torch.equal(out['wav_int16'].cpu(), R.int16_of(out['wav'].cpu()))
-    e_gpu = e_cpu = 0.0
-    for b, n in enumerate(mel_len.tolist()):
-        with torch.no_grad():
-            want = narrow.ref64.stages(mel[b, :, :n].double())[2]
-            ref = narrow.ref32.stages(mel[b, :, :n])[2]
-        e_gpu = max(e_gpu, float((out['wav'][b, :HOP * n].cpu().double() - want).abs().max()))
-        e_cpu = max(e_cpu, float((ref.double() - want).abs().max()))
-        assert not out['wav'][b, HOP * n:].any()
-    print(f'mel_len {mel_len.tolist()}: max |err| {e_gpu:.3e} on the device, {e_cpu:.3e} stock fp32, ratio {e_gpu / e_cpu:.2f}')
-    assert e_gpu <= 2.0 * e_cpu
+    VC.check_generate_batch_output_goes_straight_in(narrow, 8, R.int16_of)
