@@ -22,6 +22,11 @@ output stage (tanh, zero padding behind wav_len and int16 in one pass).  Weight 
 panels once per parameter version; the fold and pack functions, the pack cache and the entry points are those of
 gan_vocoder.py, shared with melgan.MelGAN.
 
+`voc.matmul_dtype = 'fp16'` (default 'fp32') runs every residual convolution with fp16 matrix operands on
+csrc/ft_hifigan_h16.hip: a = fp16(clamp(lrelu(x))) and fp16 weights, fp32 accumulation, fp32 residual and fp32 activations
+in memory; ResBlock1's pairs are then two launches each.  conv_pre, the transposed convolutions and conv_post stay fp32.
+The arithmetic, its error and its measured time: DESIGN.md section 7, "fp16 mode".
+
 A RAGGED batch goes through `inference_batch(mel, mel_len)`; how mel_len is taken from the host or the device is the
 contract of ragged.py.  An item's samples are bit-identical alone and inside any batch, at any position, and nothing at
 t >= mel_len[b] is ever loaded.
@@ -36,7 +41,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import hip as H
-from .gan_vocoder import GanVocoder, _wn, pack_conv_transpose
+from .gan_vocoder import GanVocoder, _wn, fold_weight_norm, pack_bias, pack_conv_transpose
 
 MAX_WAV_VALUE = 32768.0
 LRELU_SLOPE = 0.1
@@ -91,6 +96,20 @@ class ResBlock2(nn.Module):
 
 
 pair_is_fused = H.hifigan_pair_is_fused
+MATMUL_DTYPES = ('fp32', 'fp16')
+FP16_MAX = 65504.0
+
+
+def pack_taps_h16(w: torch.Tensor) -> torch.Tensor:
+    """Conv1d weight [cout, cin, k] (fp32, folded) -> the fp16 pack of ft_hifigan_resconv_h16, [k, cpad / 8, CP, 8]:
+    element [tap, c // 8, co, c % 8] = fp16_rne(w[co, c, tap]), cpad = cin rounded up to 16 and CP = cout rounded up to
+    32, exact zeros behind cin and cout.  A lane's B fragment (8 consecutive input channels of one output channel) is
+    16 contiguous bytes, and the 32 output channels of a tile follow each other."""
+    cout, cin, k = w.shape
+    cpad, CP = -(-cin // 16) * 16, -(-cout // 32) * 32
+    full = torch.zeros(k, cpad, CP, dtype=torch.float16, device=w.device)
+    full[:, :cin, :cout] = w.permute(2, 1, 0).to(torch.float16)
+    return full.reshape(k, cpad // 8, 8, CP).permute(0, 1, 3, 2).contiguous()
 
 
 class HiFiGAN(GanVocoder):
@@ -149,6 +168,35 @@ class HiFiGAN(GanVocoder):
     n_mels = property(lambda self: self.num_mels)
     _conv_out = property(lambda self: self.conv_post)
 
+    @property
+    def matmul_dtype(self) -> str:
+        """'fp32' (default): every product on the exact-fp32 MFMA.  'fp16': the residual convolutions take fp16 operands
+        ("fp16 mode"); conv_pre, the transposed convolutions and conv_post stay fp32.  Not part of
+        the state_dict."""
+        return getattr(self, '_matmul_dtype', 'fp32')
+
+    @matmul_dtype.setter
+    def matmul_dtype(self, value: str) -> None:
+        if value not in MATMUL_DTYPES:
+            raise _lib.FtError(f"HiFiGAN.matmul_dtype must be one of {MATMUL_DTYPES}, got {value!r}")
+        object.__setattr__(self, '_matmul_dtype', value)
+
+    def _panel_h16(self, conv: nn.Module):
+        """(fp16 pack of the folded weight, padded fp32 bias) of one residual convolution: the fold stays in fp32, the
+        pack has its own cache key, and a folded weight beyond fp16's range is refused here (one read-back per
+        parameter version)"""
+        v, g, b = conv.weight_v, conv.weight_g, conv.bias
+
+        def make():
+            with torch.no_grad():
+                w = fold_weight_norm(v, g)
+                wh = w.to(torch.float16)
+                if not bool(torch.isfinite(wh).all()):
+                    raise _lib.FtError(f"HiFiGAN: matmul_dtype = 'fp16' needs folded weights that are finite in fp16 (|w| <= "
+                                       f'{FP16_MAX:.0f}); largest |w| here: {float(w.abs().max()):.4g}')
+                return pack_taps_h16(w), pack_bias(b)
+        return self._pack(('h16', id(conv)), (v, g, b), make)
+
     # ------------------------------------------------------------------------------------------------
     @classmethod
     def from_config(cls, config: Union[Dict[str, Any], str, os.PathLike]) -> 'HiFiGAN':
@@ -182,6 +230,7 @@ class HiFiGAN(GanVocoder):
         """(sum over j of resblocks[i nk + j](x), j ascending) / nk.  Each block's last launch writes the stage's buffer:
         block 0 stores, the later ones add, the last one divides; the launches are ordered on the current stream."""
         nk = len(self.resblock_kernel_sizes)
+        h16 = self.matmul_dtype == 'fp16'
         total = _alloc(*x.shape, dtype=torch.float32, device=x.device)
         tmp: List[Optional[torch.Tensor]] = [None, None, None]          # two buffers in turn for the chain, one for mid
 
@@ -199,7 +248,16 @@ class HiFiGAN(GanVocoder):
                 if last and j == nk - 1 and nk > 1:
                     acc = 2
                 kw = dict(acc_mode=acc, nk=nk, out=out, alloc=_alloc)
-                if self.resblock == '2':
+                if h16:                                       # fp16 operands: every convolution is its own launch
+                    if self.resblock == '2':
+                        w, b = self._panel_h16(blk.convs[m])
+                        H.hifigan_resconv_h16(y, ml, B, Tmax, scale, d, w, b, res='x', **kw)
+                    else:
+                        w1, b1 = self._panel_h16(blk.convs1[m])
+                        w2, b2 = self._panel_h16(blk.convs2[m])
+                        mid = H.hifigan_resconv_h16(y, ml, B, Tmax, scale, d, w1, b1, out=buf(2), alloc=_alloc)
+                        H.hifigan_resconv_h16(mid, ml, B, Tmax, scale, 1, w2, b2, res=y, **kw)
+                elif self.resblock == '2':
                     w, b = self._panel(blk.convs[m])
                     H.hifigan_resconv(y, ml, B, Tmax, scale, d, w, b, res='x', **kw)
                 else:
@@ -238,4 +296,4 @@ class HiFiGAN(GanVocoder):
         return out
 
 
-__all__ = ['HiFiGAN', 'ResBlock1', 'ResBlock2', 'pair_is_fused', 'V1', 'V2', 'V3', 'MAX_HALO', 'MAX_KERNEL']
+__all__ = ['HiFiGAN', 'ResBlock1', 'ResBlock2', 'pair_is_fused', 'pack_taps_h16', 'MATMUL_DTYPES', 'V1', 'V2', 'V3', 'MAX_HALO', 'MAX_KERNEL']

@@ -1907,3 +1907,35 @@ def hifigan_respair(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tm
     _lib.call('ft_hifigan_respair', _p(x), _p(mel_len), B, Tmax, scale, C, int(w1.shape[0]), dilation, _p(w1), _p(b1),
               _p(w2), _p(b2), acc_mode, nk, _p(out), _stream())
     return out
+
+
+_H16_FIELDS = ('tile_rows', 'lds_bytes', 'threads', 'staged', 'cpad')
+
+
+def hifigan_h16_plan(field: str, c: int) -> int:
+    """the launch plan of the fp16-operand residual convolution for width c (csrc/ft_voc_plan_h16.h): field 'tile_rows',
+    'lds_bytes' (static LDS of the workgroup), 'threads', 'staged' (the widest width the arrangement stages) or 'cpad' (c
+    rounded up to the 16 the MFMA contracts at a time); 0 where the width is not supported"""
+    return int(_lib.query('ft_hifigan_h16_plan', _H16_FIELDS.index(field), int(c)))
+
+
+def hifigan_resconv_h16(x: torch.Tensor, mel_len: Optional[torch.Tensor], B: int, Tmax: int, scale: int, dilation: int,
+                        w: torch.Tensor, bias: torch.Tensor, res: Union[None, str, torch.Tensor] = None, acc_mode: int = 0,
+                        nk: int = 1, out: Optional[torch.Tensor] = None, alloc=torch.empty) -> torch.Tensor:
+    """hifigan_resconv with fp16 matrix operands (HiFiGAN.matmul_dtype = 'fp16'): x [B * Tmax * scale, C] fp32 -> res + bias
+    + Conv1d(k, dilation, zero padding)(fp16(clamp(lrelu_0.1(x)))) accumulated in fp32; w: the fp16 pack of
+    hifigan.pack_taps_h16, [k, cpad / 8, CP, 8]; bias, res, acc_mode, nk and out as in hifigan_resconv."""
+    _chk(x, 'x'); _chk(w, 'w', torch.float16); _chk(bias, 'bias')
+    rows, C = x.shape
+    CP = -(-C // 32) * 32
+    cpad = -(-C // 16) * 16
+    if rows != B * Tmax * scale or w.dim() != 4 or tuple(w.shape[1:]) != (cpad // 8, CP, 8) or bias.numel() != CP:
+        raise _lib.FtError(f'hifigan_resconv_h16: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} for '
+                           f'{B * Tmax * scale} rows and w [k, {cpad // 8}, {CP}, 8]')
+    res_mode = 0 if res is None else 1 if isinstance(res, str) and res == 'x' else 2
+    if res_mode == 2 and (not isinstance(res, torch.Tensor) or _chk(res, 'res').shape != x.shape):
+        raise _lib.FtError("hifigan_resconv_h16: res must be None, 'x' or a buffer of the shape of x")
+    out = _hifigan_out('hifigan_resconv_h16', x, out, acc_mode, alloc)
+    _lib.call('ft_hifigan_resconv_h16', _p(x), _p(mel_len), B, Tmax, scale, C, int(w.shape[0]), dilation, _p(w), _p(bias),
+              _p(res) if res_mode == 2 else None, res_mode, acc_mode, nk, _p(out), _stream())
+    return out

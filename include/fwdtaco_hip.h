@@ -1075,6 +1075,20 @@ int ft_hifigan_respair(const float* x, const long* lens, int B, int Tmax, int sc
 int ft_hifigan_conv_out(const float* x, const long* lens, int B, int Tmax, int scale, int ch, const float* w, float bias,
                         float* wav, short* wav_i16, void* stream);
 
+/* ---- HiFi-GAN's residual convolution with fp16 matrix operands (hifigan.HiFiGAN.matmul_dtype = 'fp16'; csrc/
+ *      ft_hifigan_h16.hip; the arithmetic is DESIGN.md section 7, "fp16 mode") --------------------------------------- */
+/* ft_hifigan_resconv_h16: ft_hifigan_resconv's contract, arguments and limits with a = fp16(clamp(lrelu_0.1(x), +-65504))
+ *   and fp16 weights on v_mfma_f32_32x32x16_f16, fp32 accumulation from the fp32 bias, the residual (res_mode 1: x itself)
+ *   added in fp32 from memory.  x, bias, res, out fp32 as there; w: fp16 [k][cpad / 8][CP][8], cpad = ch rounded up to 16,
+ *   element [tap][c / 8][co][c % 8] = W[co][c][tap], zeros at c >= ch and co >= ch; 16-byte aligned.
+ * ft_hifigan_h16_plan(field, c): its launch plan for width c (csrc/ft_voc_plan_h16.h, host-only).  field 0: rows per
+ *   workgroup tile; 1: static LDS bytes; 2: threads; 3: the staged width of the arrangement; 4: cpad.  0 where the width
+ *   is not supported (multiples of 8 in 8..256); an unknown field answers -1. */
+int ft_hifigan_h16_plan(int field, int c);
+int ft_hifigan_resconv_h16(const float* x, const long* lens, int B, int Tmax, int scale, int ch, int k, int dilation,
+                           const void* w, const float* bias, const float* res, int res_mode, int acc_mode, int nk, float* out,
+                           void* stream);
+
 /* ---- the GAN vocoders' launch plan (csrc/ft_voc_plan.h, host-only) ------------------------------------------------------ */
 /* ft_voc_plan(field, a, b, c): one value of the plan both vocoders launch by; host-only, no device is touched.  field 0:
  * residual taps at most (11); 1: resconv halo at most (40); 2: respair first-convolution halo at most (25); 3: 1 where

@@ -21,6 +21,14 @@ per-item stock result item by item.  Then
   * the per-stage split of ours: device events around every launch of one call (median over --rounds calls), summed per
     stage, with the FLOP counted from the items' own lengths.
 Prints everything and one JSON line.  Needs a GPU: there is no CPU fallback.
+
+    python tools/bench_hifigan_batch.py --fp16-ab [--preset v1] [--rounds 8] [--window 0.5]
+
+times HiFiGAN.matmul_dtype = 'fp16' against 'fp32' instead: ONE module, the mode switched between alternating windows
+(fp32, fp16, fp32 again -- fp32 is measured twice, and the distance between its slowest and its fastest window is the
+margin below which a difference between the modes means nothing), then the per-stage split of one call per mode, and max |wav_fp16 - wav_fp32|
+with the signal-to-noise ratio of the fp16 wav against the fp32 wav over the valid samples of the batch.
+profiles/hifigan_fp16.txt is this output.
 """
 import argparse
 import json
@@ -61,6 +69,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--window', type=float, default=0.5, help='seconds of work per timed window')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--fp16-ab', action='store_true', help="time matmul_dtype 'fp16' against 'fp32' (twice) and stop")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_hifigan_batch: needs an MI355X (no CPU fallback, no time without a GPU)')
@@ -130,6 +139,103 @@ def main():
                 print(f'round {r}: ' + '   '.join(f'{k} {t[k][-1]:9.3f} ms' for k in fns))
         return t, reps
 
+    # ---- the per-stage split: device events around every launch of one call -------------------------------------------
+    names = ('hifigan_conv_in', 'hifigan_upsample', 'hifigan_resconv', 'hifigan_resconv_h16', 'hifigan_respair',
+             'hifigan_conv_out')
+
+    def stage_split(call, ref_ms):
+        """-> (rows, launches' total ms): `call` run a.rounds times with device events around every launch"""
+        real = {n: getattr(hip, n) for n in names}
+        marks = []
+
+        def wrap(name, fn):
+            def run(*args, **kw):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn(*args, **kw)
+                e1.record()
+                if name == 'hifigan_conv_in':
+                    key, flop = 'conv_in', frames * 2 * 7 * n_mels * args[4]
+                elif name == 'hifigan_upsample':
+                    cin, cout, sc, s = args[0].shape[1], args[8], args[4], args[5]
+                    key, flop = f'upsample x{sc * s} {cin}->{cout}', frames * sc * s * 2 * 2 * cin * cout
+                elif name == 'hifigan_conv_out':
+                    key, flop = 'conv_out', frames * args[4] * 2 * 7 * args[0].shape[1]
+                else:
+                    C, sc = args[0].shape[1], args[4]
+                    k = args[6].shape[0]
+                    key = f'residual x{sc} C{C}'
+                    flop = frames * sc * 2 * k * C * C * (2 if name == 'hifigan_respair' else 1)
+                marks.append((key, flop, e0, e1))
+                return out
+            return run
+        for n in names:
+            setattr(hip, n, wrap(n, real[n]))
+        per_call = []
+        with torch.no_grad():
+            for _ in range(a.rounds):
+                marks.clear()
+                call()
+                torch.cuda.synchronize()
+                per_call.append([(key, flop, e0.elapsed_time(e1)) for key, flop, e0, e1 in marks])
+        for n in names:
+            setattr(hip, n, real[n])
+        keys = []
+        for key, _, _ in per_call[0]:
+            if key not in keys:
+                keys.append(key)
+        print(f'per-stage split (median of {a.rounds} calls, device events around each launch; {len(per_call[0])} launches):')
+        print(f'  {"stage":26s} {"launches":>8s} {"ms":>8s} {"GFLOP":>8s} {"TFLOP/s":>8s}')
+        rows, total, total_ms = [], 0, 0.0
+        for key in keys:
+            ms = statistics.median(sum(t_ for k_, _, t_ in c if k_ == key) for c in per_call)
+            flop = sum(f_ for k_, f_, _ in per_call[0] if k_ == key)
+            n = sum(1 for k_, _, _ in per_call[0] if k_ == key)
+            total, total_ms = total + flop, total_ms + ms
+            rows.append({'stage': key, 'launches': n, 'ms': round(ms, 4), 'gflop': round(flop / 1e9, 3)})
+            print(f'  {key:26s} {n:8d} {ms:8.3f} {flop / 1e9:8.2f} {flop / ms / 1e9:8.1f}')
+        print(f'  sum of the launches {total_ms:.3f} ms; total {total / 1e9:.1f} GFLOP ({total / frames / 1e9:.3f} per frame): '
+              f'{total / ref_ms / 1e9:.1f} TFLOP/s over the whole call')
+        return rows, total
+
+    def in_mode(mode):
+        def run():
+            voc.matmul_dtype = mode
+            return voc.inference_batch(mel, mel_len_h)
+        return run
+
+    if a.fp16_ab:
+        with torch.no_grad():
+            w32, w16 = in_mode('fp32')()['wav'], in_mode('fp16')()['wav']
+            torch.cuda.synchronize()
+            valid = torch.cat([(w16[b, :hop * n] - w32[b, :hop * n]).double() for b, n in enumerate(mel_len)])
+            sig = torch.cat([w32[b, :hop * n].double() for b, n in enumerate(mel_len)])
+            diff = float(valid.abs().max())
+            snr = 10 * math.log10(float(sig.pow(2).sum() / valid.pow(2).sum()))
+            print(f"{a.preset}: {B} items, frames {min(mel_len)}..{max(mel_len)} (sum {frames}), Tmax {Tmax}; matmul_dtype "
+                  f"'fp16' against 'fp32': max |wav_fp16 - wav_fp32| {diff:.3e} (max |wav_fp32| {float(sig.abs().max()):.3e}, "
+                  f'rms {float(sig.pow(2).mean().sqrt()):.3e}), SNR {snr:.1f} dB')
+            t, reps = alternate({'fp32': in_mode('fp32'), 'fp16': in_mode('fp16'), 'fp32 again': in_mode('fp32')}, a.rounds)
+        print(f'window {a.window} s: repetitions {reps}')
+        med = {k: statistics.median(v) for k, v in t.items()}
+        for k in t:
+            print(f'{k:10s} median {med[k]:9.3f} ms (min {min(t[k]):.3f}, max {max(t[k]):.3f})')
+        both = t['fp32'] + t['fp32 again']
+        spread = max(both) - min(both)                      # of every fp32 window, first and second set
+        gain = min(med['fp32'], med['fp32 again']) - med['fp16']
+        print(f"fp32 / fp16 = {min(med['fp32'], med['fp32 again']) / med['fp16']:.3f}x; fp32's own spread {spread:.3f} ms, fp16 is "
+              f"{gain:+.3f} ms ahead: {'faster beyond the spread' if gain > spread else 'NOT faster beyond the spread'}")
+        splits = {}
+        for mode in ('fp32', 'fp16'):
+            print(f"matmul_dtype = '{mode}':")
+            splits[mode], _ = stage_split(in_mode(mode), med[mode])
+        voc.matmul_dtype = 'fp32'
+        print(json.dumps({'preset': a.preset, 'items': B, 'frames': frames, 'Tmax': Tmax, 'rounds': a.rounds,
+                          'repetitions': reps, 'fp32_ms_median': round(med['fp32'], 3), 'fp16_ms_median': round(med['fp16'], 3),
+                          'fp32_again_ms_median': round(med['fp32 again'], 3), 'max_wav_diff': diff, 'snr_db': round(snr, 2),
+                          'split': splits}))
+        return
+
     with torch.no_grad():
         oo, ol = ours(), per_item()
         torch.cuda.synchronize()
@@ -182,58 +288,7 @@ def main():
                               f'({flop / s2 / 1e9:6.1f} TFLOP/s)   fused / two {f / s2:.2f}   plan {plan}'
                               f'{"" if (f <= s2) == (plan == "fused") else "   <-- plan is not the winner"}')
 
-        # ---- the per-stage split: device events around every launch of one call ---------------------------------------
-        names = ('hifigan_conv_in', 'hifigan_upsample', 'hifigan_resconv', 'hifigan_respair', 'hifigan_conv_out')
-        real = {n: getattr(hip, n) for n in names}
-        marks = []
-
-        def wrap(name, fn):
-            def run(*args, **kw):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                out = fn(*args, **kw)
-                e1.record()
-                if name == 'hifigan_conv_in':
-                    key, flop = 'conv_in', frames * 2 * 7 * n_mels * args[4]
-                elif name == 'hifigan_upsample':
-                    cin, cout, sc, s = args[0].shape[1], args[8], args[4], args[5]
-                    key, flop = f'upsample x{sc * s} {cin}->{cout}', frames * sc * s * 2 * 2 * cin * cout
-                elif name == 'hifigan_conv_out':
-                    key, flop = 'conv_out', frames * args[4] * 2 * 7 * args[0].shape[1]
-                else:
-                    C, sc = args[0].shape[1], args[4]
-                    k = args[6].shape[0]
-                    key = f'residual x{sc} C{C}'
-                    flop = frames * sc * 2 * k * C * C * (2 if name == 'hifigan_respair' else 1)
-                marks.append((key, flop, e0, e1))
-                return out
-            return run
-        for n in names:
-            setattr(hip, n, wrap(n, real[n]))
-        per_call = []
-        for _ in range(a.rounds):
-            marks.clear()
-            ours()
-            torch.cuda.synchronize()
-            per_call.append([(key, flop, e0.elapsed_time(e1)) for key, flop, e0, e1 in marks])
-        for n in names:
-            setattr(hip, n, real[n])
-    keys = []
-    for key, _, _ in per_call[0]:
-        if key not in keys:
-            keys.append(key)
-    print(f'per-stage split (median of {a.rounds} calls, device events around each launch; {len(per_call[0])} launches):')
-    print(f'  {"stage":26s} {"launches":>8s} {"ms":>8s} {"GFLOP":>8s} {"TFLOP/s":>8s}')
-    rows, total, total_ms = [], 0, 0.0
-    for key in keys:
-        ms = statistics.median(sum(t_ for k_, _, t_ in c if k_ == key) for c in per_call)
-        flop = sum(f_ for k_, f_, _ in per_call[0] if k_ == key)
-        n = sum(1 for k_, _, _ in per_call[0] if k_ == key)
-        total, total_ms = total + flop, total_ms + ms
-        rows.append({'stage': key, 'launches': n, 'ms': round(ms, 4), 'gflop': round(flop / 1e9, 3)})
-        print(f'  {key:26s} {n:8d} {ms:8.3f} {flop / 1e9:8.2f} {flop / ms / 1e9:8.1f}')
-    print(f'  sum of the launches {total_ms:.3f} ms; total {total / 1e9:.1f} GFLOP ({total / frames / 1e9:.3f} per frame): '
-          f'{total / med["ours"] / 1e9:.1f} TFLOP/s over the whole call')
+    rows, total = stage_split(ours, med['ours'])
     print(json.dumps({'preset': a.preset, 'items': B, 'frames': frames, 'Tmax': Tmax, 'ours_ms_median': round(med['ours'], 3),
                       'stock_per_item_ms_median': round(med['per-item'], 3), 'stock_padded_ms_median': round(med['padded'], 3),
                       'rounds': a.rounds, 'repetitions': reps, 'max_int16_diff': worst, 'max_wav_diff': wf,
